@@ -6,7 +6,9 @@ A "step" is one frame: one sample per pixel over the whole image (maxSamples = 1
 accumulated into the RGBA32F framebuffer exactly like shaders/pathtrace.comp:122-133.  Scene, BVH, textures
 and environment are resident in HBM before the timed region starts.
 
-  python bench.py --gpus 1 --steps 256 --warmup 8
+  python bench.py --gpus 1 --steps 256 --warmup 8    (set up, warm up, ONE timed window of --steps frames, the JSON line: nothing else)
+  python bench.py ... --full                          (also every evidence leg below; the timed window is then run --repeats 5 times)
+  python bench.py ... --dump-outputs DIR              (after the timed steps: the accumulation image of the last step as DIR/image.npy)
   python bench.py --gpus N ...          (self-launching: spawns one process per GPU on 127.0.0.1 and relays rank 0's line; falls back to --single-process
                                          when those ranks fail to come up)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
@@ -22,10 +24,10 @@ says so.  `ranks_seen` is ncclCommCount of the communicator.  Every rank binds i
 than N devices fails with pt_create's device-count message.  The control plane (rendezvous of the launcher's ranks, barriers around the timed region,
 the MAX of the ranks' times, handing out the ncclUniqueId) is vk_raytrace_amd/rendezvous.py -- a Unix-domain socket between the ranks of this node;
 a rank imports nothing of torch, because the PyTorch wheel's bundled HIP / RCCL libraries break the system RCCL that libptmi opens (rendezvous.py).
-The image gathered after the FIRST timed window is what the parity leg compares: the line of an N > 1 run carries `parity`, `cpu_baseline` and
+With --full the image gathered after the FIRST timed window is what the parity leg compares: the line of an N > 1 run carries `parity`, `cpu_baseline` and
 `roofline` like the N = 1 line.  The JSON line is the last thing written to stdout.
 
-After the timed region (never part of `value`), rank 0 measures what the JSON line's evidence fields need, all in this run:
+With --full, after the timed region (never part of `value`), rank 0 measures what the JSON line's evidence fields need, all in this run:
   calibration        pt_measure_peaks: the VALU-issue and HBM-streaming ceilings of this box
   interactive        render + tonemap per frame (batch = 1, SampleExample's display loop)
   serialised         one batch on a second context with one frame slot and the SAME launch policy as the timed run (k_tail included):
@@ -64,8 +66,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--repeats", type=int, default=5, help="the timed window of --steps frames is run this many times back to back (each bracketed by a device synchronisation and the ranks' barrier); "
-                    "`value` is the median window, every window is printed in `repeats`")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed window of --steps frames is run this many times back to back (each bracketed by a device synchronisation and the ranks' barrier); "
+                    "`value` is the median window, every window is printed in `repeats` (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run everything the headline figure does not need: the CPU baseline and parity leg, "
+                    "the calibration, interactive and serialised profiling passes, the evidence fields and the N > 1 scaling prediction (off by default)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps write what the timed path computed in its last step as DIR/<name>.npy "
+                    "(float32; at most 64 MB, a fixed seeded pixel sample beyond that)")
     # development knobs (the defaults are the BASELINE configuration)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -83,7 +89,10 @@ def parse():
     ap.add_argument("--no-profile", action="store_true", help="skip the serialised profiling pass (roofline fields become null)")
     ap.add_argument("--no-interactive", action="store_true", help="skip the frame-by-frame (render + tonemap) measurement")
     ap.add_argument("--cpu-seconds", type=float, default=16.0, help="target duration of the CPU baseline sample (split between the compiled reference and the port)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def self_launch(n):
@@ -453,6 +462,30 @@ def evidence_fields(out, serial, alg, samples, elapsed, world, workload):
             pass
 
 
+def parity_leg(args):
+    """the CPU leg runs (--full without --no-cpu-baseline): the image after the first timed window is read for its parity figures"""
+    return args.full and not args.no_cpu_baseline
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(dirname, img):
+    """--dump-outputs: what the timed path hands a caller after its last step -- the accumulation image (pt_read_accum: H x W x RGBA float32, the
+    running mean of every frame rendered so far), gathered from every rank.  image.npy when it fits in DUMP_BYTES; beyond that a fixed, seeded sample of
+    pixels: image_sample.npy (RGBA per pixel) and image_sample_pixels.npy (their row-major pixel ids, float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    img = np.ascontiguousarray(img, np.float32)
+    if img.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(dirname, "image.npy"), img)
+        return
+    flat = img.reshape(-1, img.shape[-1])
+    n = (DUMP_BYTES - 4096) // (flat.shape[1] * 4 + 8)  # (room for the two .npy headers)
+    ids = np.sort(np.random.default_rng(0).permutation(flat.shape[0])[:n])
+    np.save(os.path.join(dirname, "image_sample.npy"), flat[ids])
+    np.save(os.path.join(dirname, "image_sample_pixels.npy"), ids.astype(np.float64))
+
+
 def build_workload(args):
     from vk_raytrace_amd import capi, workloads
     if args.from_gltf:
@@ -591,7 +624,8 @@ def single_process(args):
         if rep == 0:
             per_rank_ms = done
             stats = [r.stats() for r in rs]
-            img_first, _ = gather()
+            if parity_leg(args):
+                img_first, _ = gather()
     img, gather_ms = gather()
     RAY_KEYS = ("closestRays", "shadowRays", "shadedHits", "misses", "alphaTests", "neeLookups")
     total = dict(stats[0])
@@ -722,7 +756,8 @@ def multi_process(args, rank, local_rank, world):
                 slot[rank] = mine * 1e3 / args.steps
                 per_rank_ms = dist.all_reduce(slot, "sum")   # every rank's own time for the window (before the barrier): who is the slowest
             # frames 0 .. warmup+steps-1 of the WHOLE image: what the parity leg re-renders on the CPU (untimed: between two windows)
-            img_first, _ = gather()
+            if parity_leg(args):
+                img_first, _ = gather()
     img, gather_ms = gather()
 
     RAY_KEYS = ("closestRays", "shadowRays", "shadedHits", "misses", "alphaTests", "neeLookups")
@@ -740,6 +775,23 @@ def multi_process(args, rank, local_rank, world):
     return {"wl": wl, "W": W, "H": H, "windows": windows, "img_first": img_first, "img": img, "gather_ms": gather_ms, "stats": stats, "ranks_seen": ranks_seen, "t_setup": t_setup,
             "integral": integral, "cam": cam, "renderer": r, "st": st, "frame": frame, "per_rank_ms": per_rank_ms, "gather": how, "poisoned": poisoned, "shard": (shard_rank, shard_n),
             "cleanup": (lambda: (dist.barrier(), dist.close())) if dist is not None else (lambda: None)}
+
+
+def emit_line(out, job):
+    """the JSON line as the last thing on stdout, then the job's cleanup"""
+    try:  # RCCL writes a version banner through C stdio, which a pipe holds back until exit -- AFTER the line.  Out with it now: the line is the last thing on stdout.
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
+    print(json.dumps(out))
+    sys.stdout.flush()
+    job["cleanup"]()
+    try:
+        sys.stdout.flush()
+        os.dup2(os.open(os.devnull, os.O_WRONLY), 1)  # nothing a library prints at exit may follow the line
+    except Exception:
+        pass
 
 
 def main():
@@ -816,7 +868,13 @@ def main():
         "image_mean": float(np.mean(img[..., :3])) if img is not None else None,
     }
 
-    if world > 1 and not args.emulate_shard:
+    if args.dump_outputs:
+        if img is None:
+            print("bench.py: --dump-outputs: no image to write (the gather failed)", file=sys.stderr)
+        else:
+            dump_outputs(args.dump_outputs, img)
+
+    if args.full and world > 1 and not args.emulate_shard:
         try:
             out["scaling_prediction"] = scaling_prediction(args.workload, args.steps, world, out["ms_per_step"])
         except Exception as e:  # noqa: BLE001
@@ -837,13 +895,13 @@ def main():
     # texture filtering) is bound to the oracle's trace contract.  `port_value`: the oracle's own restatement on the same sample.
     # N > 1: the same leg on rank 0, against the GATHERED image of the first window -- the line of a multi-GPU run carries both halves of the metric too
     alg = None
-    if not args.no_cpu_baseline:
+    if parity_leg(args):
         out["cpu_baseline"], par, alg = cpu_leg(wl, cam, integral, W, H, frames_first, img_first, args.cpu_seconds)
         if par is not None:
             out["parity"] = par
             if world > 1:
                 par["note"] = f"image GATHERED from {world} ranks ({job.get('gather')}) after the first timed window vs CPU renders of the same frames on the sampled pixels"
-    elif os.path.exists(os.path.join(ROOT, "profiles", "alg_bytes_c3.json")):
+    elif args.full and os.path.exists(os.path.join(ROOT, "profiles", "alg_bytes_c3.json")):
         alg = json.load(open(os.path.join(ROOT, "profiles", "alg_bytes_c3.json")))
 
     if alg is not None:
@@ -863,6 +921,9 @@ def main():
         sys.stdout.flush()
         with_timeout(job["cleanup"], 10, "control-plane barrier")  # let the other ranks leave (the control plane is independent of the wedged collective)
         os._exit(4)  # (not sys.exit: the helper thread inside the collective would keep the interpreter alive)
+    if not args.full:
+        emit_line(out, job)
+        return
     peaks = r.measure_peaks()
     out["calibration"] = {"valu_G_wave_instr_per_s": peaks["valuWaveInstrPerSec"] / 1e9, "hbm_copy_GBps": peaks["hbmCopyBytesPerSec"] / 1e9,
                           "hbm_read_GBps": peaks["hbmReadBytesPerSec"] / 1e9, "compute_units": peaks["computeUnits"], "clock_MHz": peaks["clockMHz"],
@@ -938,19 +999,7 @@ def main():
         evidence_fields(out, serial, alg, samples, elapsed, world, args.workload + ("two" if args.accel == "two" else ""))  # (the PMC summaries are per workload AND structure)
     except Exception as e:  # the evidence fields are additions: a failure in their post-processing must never cost the line itself
         out["evidence_error"] = repr(e)
-    try:  # RCCL writes a version banner through C stdio, which a pipe holds back until exit -- AFTER the line.  Out with it now: the line is the last thing on stdout.
-        import ctypes
-        ctypes.CDLL(None).fflush(None)
-    except Exception:
-        pass
-    print(json.dumps(out))
-    sys.stdout.flush()
-    job["cleanup"]()
-    try:
-        sys.stdout.flush()
-        os.dup2(os.open(os.devnull, os.O_WRONLY), 1)  # nothing a library prints at exit may follow the line
-    except Exception:
-        pass
+    emit_line(out, job)
     if out.get("parity") and not (out["parity"]["l2"] <= out["parity"]["tolerance"]):
         print(f"bench.py: parity FAILED: per-pixel L2 {out['parity']['l2']} against {out['parity']['against']} exceeds {out['parity']['tolerance']}", file=sys.stderr)
         raise SystemExit(3)

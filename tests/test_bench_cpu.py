@@ -1,6 +1,8 @@
 """bench.py's host logic that needs no GPU: the CPU leg (cpu_baseline + the per-pixel L2 of the metric's second half) on a small instance of the
 bench workload.  The "GPU image" here is the oracle's own render of the same frames, so the parity figures must say "identical" -- and a perturbed
 image must be reported as a mismatch (shaders/pathtrace.comp:122-133 is the accumulation the comparison is taken on)."""
+import os
+
 import numpy as np
 
 import bench
@@ -140,9 +142,9 @@ def _run_fallback(extra=()):
 def test_failed_self_launch_falls_back_to_single_process():
     """`bench.py --gpus 2` without a launcher: the self-launched ranks fail -> the same job from ONE process (--single-process) instead of no line at all, and the
     line says so; `--no-fallback` turns the failure into the exit code.  The launch and the renderer are stubs here (no GPU): what is under test is main()'s flow
-    -- the fallback, the median window, the N > 1 fields incl. the prediction of tools/shard_table.py, the line being the last thing on stdout."""
+    -- the fallback, the median window, the N > 1 fields incl. the prediction of tools/shard_table.py (--full), the line being the last thing on stdout."""
     import json
-    p, calls = _run_fallback()
+    p, calls = _run_fallback(["--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     assert [c[0] for c in calls] == ["self_launch", "single_process", "cleanup"] and calls[0][1] == 2
     assert "falling back to --single-process" in p.stderr and "exit code 7" in p.stderr
@@ -153,5 +155,52 @@ def test_failed_self_launch_falls_back_to_single_process():
     sp = line["scaling_prediction"]
     assert sp["tabulated_steps"] == 20 and 0.0 < sp["efficiency_predicted"] <= 1.0 and sp["ms_per_step_measured"] == line["ms_per_step"]
     assert abs(sp["efficiency_vs_n1_prediction"] - sp["n1_ms_per_step_predicted"] / (2 * line["ms_per_step"])) < 1e-12
-    p, calls = _run_fallback(["--no-fallback"])
+    p, calls = _run_fallback(["--full", "--no-fallback"])
     assert p.returncode == 7 and [c[0] for c in calls] == ["self_launch"] and p.stdout.strip() == ""
+
+
+def test_plain_run_is_the_headline_only_and_dumps_its_image(tmp_path):
+    """Without --full main() prints the headline line and nothing the evidence legs add (no calibration pass: the stub renderer is never asked for
+    peaks, no prediction); --dump-outputs writes the image the timed path left after its last step."""
+    import json
+    p, calls = _run_fallback(["--dump-outputs", str(tmp_path / "out")])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert [c[0] for c in calls] == ["self_launch", "single_process", "cleanup"]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert abs(line["ms_per_step"] - 1.0) < 1e-9 and line["higher_is_better"] is True and line["dtype"] == "f32"
+    for k in ("calibration", "scaling_prediction", "cpu_baseline", "parity", "serialised", "roofline", "interactive", "alg_model"):
+        assert k not in line, k
+    img = np.load(tmp_path / "out" / "image.npy")
+    assert img.dtype == np.float32 and img.shape == (32, 64, 4) and np.all(img == 1.0)
+
+
+def test_repeats_default_to_one_window_and_five_with_full(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "7"])
+    a = bench.parse()
+    assert a.steps == 7 and a.repeats == 1 and not a.full and a.dump_outputs == ""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full"])
+    assert bench.parse().repeats == 5
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--repeats", "2"])
+    assert bench.parse().repeats == 2
+
+
+def test_dump_outputs_fits_the_budget_with_a_fixed_sample(tmp_path):
+    """a small image is written whole; one beyond 64 MB as the same seeded pixel sample every time, every file float32 / float64"""
+    small = np.arange(6 * 5 * 4, dtype=np.float32).reshape(6, 5, 4)
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    assert np.array_equal(np.load(tmp_path / "s" / "image.npy"), small)
+    H, W = 2160, 2048   # 70.8 MB of RGBA32F
+    big = np.random.default_rng(5).random((H, W, 4), dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["image_sample.npy", "image_sample_pixels.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    vals, ids = np.load(tmp_path / "a" / "image_sample.npy"), np.load(tmp_path / "a" / "image_sample_pixels.npy")
+    assert vals.dtype == np.float32 and ids.dtype == np.float64 and len(ids) == len(vals) > (H * W) // 3
+    assert np.all(np.diff(ids) > 0) and ids[-1] < H * W
+    assert np.array_equal(vals, big.reshape(-1, 4)[ids.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f

@@ -98,7 +98,7 @@ def test_bench_two_processes_share_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["PT_BENCH_SAME_DEVICE"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "2", "--width", "256", "--height", "160", "--tex-size", "32",
-           "--tris", "2000", "--no-profile", "--no-interactive", "--cpu-seconds", "2"]
+           "--tris", "2000", "--full", "--no-profile", "--no-interactive", "--cpu-seconds", "2"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = _last_json(p.stdout)
@@ -124,7 +124,7 @@ def test_bench_single_process_flavour():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--single-process", "--steps", "3", "--warmup", "1", "--repeats", "2", "--width", "256", "--height", "160",
-           "--tex-size", "32", "--tris", "2000", "--no-profile", "--no-interactive", "--cpu-seconds", "2"]
+           "--tex-size", "32", "--tris", "2000", "--full", "--no-profile", "--no-interactive", "--cpu-seconds", "2"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = _last_json(p.stdout)

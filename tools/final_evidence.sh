@@ -31,5 +31,5 @@ PY
 timeout 1200 python tools/shard_table.py --workload c3 --steps 20 128 256 > $O/${R}_shard_table_c3.json 2> $O/shard_c3.err; cp $O/${R}_shard_table_c3.json profiles/ 2>/dev/null
 timeout 1200 python tools/shard_table.py --workload c4 --steps 20 128 > $O/${R}_shard_table_c4.json 2> $O/shard_c4.err; cp $O/${R}_shard_table_c4.json profiles/ 2>/dev/null
 bash tools/gpu_run.sh $T bench20 bench256 prof20 line:c2:64 line:c4:20 line:c5:32 line:c5:32:two
-PT_BENCH_SAME_DEVICE=1 timeout 900 python bench.py --gpus 2 --steps 20 --warmup 5 --no-profile --no-interactive > $O/${R}_two_ranks_one_gpu_bench_20.json 2> $O/two_ranks.err; echo "two ranks on one device: rc $?" | tee -a $O/log.txt
+PT_BENCH_SAME_DEVICE=1 timeout 900 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-profile --no-interactive > $O/${R}_two_ranks_one_gpu_bench_20.json 2> $O/two_ranks.err; echo "two ranks on one device: rc $?" | tee -a $O/log.txt
 bash tools/gpu_run.sh $T tests smoke

@@ -32,24 +32,24 @@ for step in "$@"; do
   IFS=: read -r kind a b <<< "$step"
   echo "=== $step" | tee -a $O/log.txt
   case $kind in
-    cold20)  PT_TUNE=warm=0 timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-profile --no-interactive > $O/cold20.json 2> $O/cold20.err; val < $O/cold20.json | tee -a $O/log.txt ;;
-    bench20) timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_20.json 2> $O/bench_20.err; echo "rc $?" | tee -a $O/log.txt; val < $O/bench_20.json | tee -a $O/log.txt ;;
-    bench256) timeout 900 python bench.py --gpus 1 --steps 256 --warmup 8 > $O/bench_256.json 2> $O/bench_256.err; val < $O/bench_256.json | tee -a $O/log.txt ;;
+    cold20)  PT_TUNE=warm=0 timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-profile --no-interactive > $O/cold20.json 2> $O/cold20.err; val < $O/cold20.json | tee -a $O/log.txt ;;
+    bench20) timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_20.json 2> $O/bench_20.err; echo "rc $?" | tee -a $O/log.txt; val < $O/bench_20.json | tee -a $O/log.txt ;;
+    bench256) timeout 900 python bench.py --full --gpus 1 --steps 256 --warmup 8 > $O/bench_256.json 2> $O/bench_256.err; val < $O/bench_256.json | tee -a $O/log.txt ;;
     line)    # line:<workload>:<steps>[:two]  a full line (parity, cpu_baseline, roofline) of another BASELINE configuration
              IFS=: read -r ln_steps ln_accel <<< "$b"; ACC=flat; SUF=""; [ "$ln_accel" = "two" ] && ACC=two && SUF=_two
-             timeout 1500 python bench.py --gpus 1 --workload $a --accel $ACC --steps $ln_steps --warmup 5 > $O/bench_${a}_${ln_steps}$SUF.json 2> $O/bench_${a}_${ln_steps}$SUF.err; echo "rc $?" | tee -a $O/log.txt; val < $O/bench_${a}_${ln_steps}$SUF.json | tee -a $O/log.txt ;;
-    quick)   timeout 300 python bench.py --steps $a --warmup 8 --no-cpu-baseline --no-profile --no-interactive > $O/quick_$a.json 2> $O/quick_$a.err; val < $O/quick_$a.json | tee -a $O/log.txt ;;
-    prof20)  (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof20 -o p -- python $REPO/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-interactive > $O/bench_20_profiled.json 2> $O/prof20.err)
+             timeout 1500 python bench.py --full --gpus 1 --workload $a --accel $ACC --steps $ln_steps --warmup 5 > $O/bench_${a}_${ln_steps}$SUF.json 2> $O/bench_${a}_${ln_steps}$SUF.err; echo "rc $?" | tee -a $O/log.txt; val < $O/bench_${a}_${ln_steps}$SUF.json | tee -a $O/log.txt ;;
+    quick)   timeout 300 python bench.py --full --steps $a --warmup 8 --no-cpu-baseline --no-profile --no-interactive > $O/quick_$a.json 2> $O/quick_$a.err; val < $O/quick_$a.json | tee -a $O/log.txt ;;
+    prof20)  (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof20 -o p -- python $REPO/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-interactive > $O/bench_20_profiled.json 2> $O/prof20.err)
              find $O/prof20 -name '*kernel_stats.csv' -exec cp {} $O/kernel_stats_bench20.csv \; ; rm -rf $O/prof20; head -12 $O/kernel_stats_bench20.csv | cut -c1-150 | tee -a $O/log.txt ;;
     tune)    for round in 1 2; do IFS=';' read -ra TS <<< "$b"; for t in "${TS[@]}"; do tt=$t; [ "$t" = "-" ] && tt=""
                echo -n "steps $a PT_TUNE=$tt : " | tee -a $O/log.txt
-               PT_TUNE=$tt timeout 300 python bench.py --steps $a --warmup 8 --no-cpu-baseline --no-profile --no-interactive 2>/dev/null | val | tee -a $O/log.txt; done; done ;;
+               PT_TUNE=$tt timeout 300 python bench.py --full --steps $a --warmup 8 --no-cpu-baseline --no-profile --no-interactive 2>/dev/null | val | tee -a $O/log.txt; done; done ;;
     libs)    for round in 1 2; do IFS=',' read -ra VS <<< "$b"; for v in "${VS[@]}"; do L=""; [ "$v" != default ] && L="$REPO/vk_raytrace_amd/variants/libptmi_$v.so"
                echo -n "steps $a lib $v : " | tee -a $O/log.txt
-               PT_LIB=$L timeout 300 python bench.py --steps $a --warmup 8 --no-cpu-baseline --no-profile --no-interactive 2>/dev/null | val | tee -a $O/log.txt; done; done ;;
+               PT_LIB=$L timeout 300 python bench.py --full --steps $a --warmup 8 --no-cpu-baseline --no-profile --no-interactive 2>/dev/null | val | tee -a $O/log.txt; done; done ;;
     libs5)   for round in 1 2; do IFS=',' read -ra VS <<< "$b"; for v in "${VS[@]}"; do L=""; [ "$v" != default ] && L="$REPO/vk_raytrace_amd/variants/libptmi_$v.so"
                echo -n "c5 two-level steps $a lib $v : " | tee -a $O/log.txt
-               PT_LIB=$L timeout 300 python bench.py --workload c5 --accel two --steps $a --warmup 8 --no-cpu-baseline --no-profile --no-interactive 2>/dev/null | val | tee -a $O/log.txt; done; done ;;
+               PT_LIB=$L timeout 300 python bench.py --full --workload c5 --accel two --steps $a --warmup 8 --no-cpu-baseline --no-profile --no-interactive 2>/dev/null | val | tee -a $O/log.txt; done; done ;;
     tests)   if [ -n "$a" ]; then timeout 1500 python -m pytest tests -m gpu -q -x -k "$a" > $O/gputest.txt 2>&1; else timeout 1500 python -m pytest tests -m gpu -q > $O/gputest.txt 2>&1; fi; tail -5 $O/gputest.txt | tee -a $O/log.txt ;;
     smoke)   timeout 300 python __graft_entry__.py smoke 2>&1 | tail -1 | tee -a $O/log.txt ;;
     pmc)     PMC_FRAMES=${a:-96} timeout 1500 bash tools/pmc_passes.sh $TAG > $O/pmc.txt 2>&1; for k in traffic valu cache; do [ -s gpurun_out/pmc_$TAG/$k.json ] && cp gpurun_out/pmc_$TAG/$k.json $O/$k.json; done; tail -4 $O/pmc.txt | tee -a $O/log.txt ;;
@@ -60,14 +60,14 @@ for step in "$@"; do
              for k in traffic valu binders; do [ -s gpurun_out/pmc_${TAG}_$PSUF/$k.json ] && cp gpurun_out/pmc_${TAG}_$PSUF/$k.json $O/${k}_$PSUF.json; done; tail -6 $O/pmc_$PSUF.txt | tee -a $O/log.txt ;;
     binders) PMC_FRAMES=${a:-64} PMC_TUNE=${b:-inflight=1,warm=0} timeout 1500 bash tools/pmc_binders.sh $TAG > $O/binders.txt 2>&1; cp gpurun_out/pmc_$TAG/binders.json $O/binders.json 2>/dev/null; tail -14 $O/binders.txt | tee -a $O/log.txt ;;
     shards)  for n in 1 2 4 8; do worst=0; for ((r = 0; r < n; r++)); do
-               timeout 300 python bench.py --workload $a --emulate-shard $r/$n --steps $b --warmup 5 --no-cpu-baseline --no-profile --no-interactive > $O/shard_${a}_${r}of${n}_$b.json 2>/dev/null
+               timeout 300 python bench.py --full --workload $a --emulate-shard $r/$n --steps $b --warmup 5 --no-cpu-baseline --no-profile --no-interactive > $O/shard_${a}_${r}of${n}_$b.json 2>/dev/null
                ms=$(python -c "import json; print(json.loads(open('$O/shard_${a}_${r}of${n}_$b.json').readline())['ms_per_step'])" 2>/dev/null || echo 0)
                worst=$(python -c "print(max($worst, $ms))"); done
                echo "$a steps $b N=$n: slowest rank $worst ms/frame" | tee -a $O/log.txt; done ;;
     shardtune) IFS=: read -r st_steps st_rn st_tunes <<< "$b"
              for round in 1 2; do IFS=';' read -ra TS <<< "$st_tunes"; for t in "${TS[@]}"; do tt=$t; [ "$t" = "-" ] && tt=""
                echo -n "$a shard $st_rn steps $st_steps PT_TUNE=$tt : " | tee -a $O/log.txt
-               PT_TUNE=$tt timeout 300 python bench.py --workload $a --emulate-shard $st_rn --steps $st_steps --warmup 5 --no-cpu-baseline --no-profile --no-interactive 2>/dev/null | python -c 'import sys,json; d=json.loads(sys.stdin.readline()); print(round(d["ms_per_step"],4), "ms/frame  windows:", [round(x) for x in d["repeats"]])' | tee -a $O/log.txt; done; done ;;
+               PT_TUNE=$tt timeout 300 python bench.py --full --workload $a --emulate-shard $st_rn --steps $st_steps --warmup 5 --no-cpu-baseline --no-profile --no-interactive 2>/dev/null | python -c 'import sys,json; d=json.loads(sys.stdin.readline()); print(round(d["ms_per_step"],4), "ms/frame  windows:", [round(x) for x in d["repeats"]])' | tee -a $O/log.txt; done; done ;;
     valumix) /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 tools/valu_mix.hip -o /tmp/valu_mix 2>/dev/null && timeout 300 /tmp/valu_mix | tee $O/valu_mix.txt | tee -a $O/log.txt ;;
     sh)      timeout 900 bash -c "${step#sh:}" 2>&1 | tail -20 | tee -a $O/log.txt ;;
     *)       echo "unknown step $step" | tee -a $O/log.txt ;;
