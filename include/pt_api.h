@@ -12,6 +12,11 @@
  *  - host arrays passed to pt_set_* are copied before the call returns.
  *  - pt_render_frame is asynchronous on the context's HIP stream; pt_read_accum, pt_tonemap,
  *    pt_get_stats and pt_synchronize wait for it.
+ *  - Traversal-stack overflow: a ray whose walk needs more than 64 stack entries drops a subtree, so the image misses geometry.  Once
+ *    such an overflow has been counted, every call that hands out results returns PT_ERR_STATE ("BVH traversal stack overflowed ...")
+ *    instead of PT_OK: pt_synchronize, pt_read_accum, pt_tonemap, pt_tonemap_zoom, pt_tonemap_end, pt_pick, pt_local_shard,
+ *    pt_gather_shards and pt_get_stats, and pt_tonemap_begin once the overflow is known (it then enqueues nothing).  The state stays
+ *    until pt_reset_stats or the next pt_build_accel (a new scene) clears it; images begun before the clear no longer report it.
  *  - there is no CPU fallback: without a gfx950 device pt_create fails with PT_ERR_NO_DEVICE.
  */
 #ifndef PT_API_H
@@ -137,7 +142,7 @@ int pt_render_frame(pt_context* ctx, const pt_RtxState* state);
 int pt_synchronize(pt_context* ctx);
 
 /* Reads the linear RGBA32F accumulation image, row-major width*height*4 floats (alpha == 1).
- * With nranks > 1 only locally owned pixels are valid unless pt_scatter_shards was called. */
+ * With nranks > 1 only locally owned pixels are valid unless pt_scatter_shards was called; the others read as zero. */
 int pt_read_accum(pt_context* ctx, float* rgba32f_out);
 
 /* Checkpoint restore (no reference counterpart; SURVEY.md section 5 "Checkpoint / resume": the progressive state of the reference is the
@@ -165,15 +170,17 @@ int pt_tonemap_zoom(pt_context* ctx, const pt_Tonemapper* tm, int disp_width, in
  * accumulate step waits until the pass has read the accumulation image).  pt_tonemap_end blocks until the OLDEST image begun is in host memory
  * and copies it to rgba8_out (the size given to its pt_tonemap_begin).  At most PT_DISPLAY_RING (8) images may be pending
  * (PT_ERR_STATE beyond, and for pt_tonemap_end with none pending); pt_tonemap_pending returns how many are.  The images are bit-identical to
- * what pt_tonemap_zoom returns at the same point of the frame sequence.  A traversal-stack overflow is reported by the next synchronising
- * call (pt_synchronize, pt_tonemap, pt_read_accum), not by pt_tonemap_end. */
+ * what pt_tonemap_zoom returns at the same point of the frame sequence.  A traversal-stack overflow in the frames an image shows is reported
+ * by its pt_tonemap_end (the image is still copied out and leaves the ring); after that pt_tonemap_begin refuses with PT_ERR_STATE, enqueuing
+ * nothing, until pt_reset_stats or pt_build_accel clears the overflow (see the top of this file). */
 #define PT_DISPLAY_RING 8
 int pt_tonemap_begin(pt_context* ctx, const pt_Tonemapper* tm, int disp_width, int disp_height);
 int pt_tonemap_end(pt_context* ctx, uint8_t* rgba8_out);
 int pt_tonemap_pending(pt_context* ctx);
 
 /* Device-side view of the local shard for the RCCL gather: pointer to [maxTilesPerRank][PT_TILE*PT_TILE][4]
- * floats (owned tiles first, in increasing global tile id; padding zero). */
+ * floats (owned tiles first, in increasing global tile id; padding zero).  Waits for the frames rendered since the last synchronising
+ * call and returns PT_ERR_STATE if they overflowed the traversal stack. */
 int pt_local_shard(pt_context* ctx, void** device_ptr, size_t* bytes, int* num_local_tiles, int* max_tiles_per_rank);
 
 /* Rank 0 after the gather: gathered_dev holds nranks consecutive shards as returned by
@@ -190,7 +197,8 @@ int pt_scatter_shards(pt_context* ctx, const void* gathered_dev, int nranks);
  *                         pt_gather_finish(ctx[0]).
  * The communicator's rank / size must equal pt_set_shard's.  Without librccl.so every call of this group returns PT_ERR_UNAVAILABLE
  * (single-GPU hosts never need the library; libptmi.so is built without the RCCL headers).  Only the root allocates the gather buffer;
- * pt_gather_finish on a context that did not enqueue a gather as root returns PT_ERR_STATE. */
+ * pt_gather_finish on a context that did not enqueue a gather as root returns PT_ERR_STATE.  A rank whose frames overflowed the traversal
+ * stack still takes part in the collective (leaving it would stall the peers) and then returns PT_ERR_STATE from pt_gather_shards. */
 typedef struct pt_comm pt_comm;
 #define PT_COMM_ID_BYTES 128
 int pt_comm_get_unique_id(unsigned char id_out[PT_COMM_ID_BYTES]);
@@ -242,7 +250,8 @@ int pt_sampler_from_gltf(int has_sampler, int gltf_mag, int gltf_min, int gltf_w
 /* replaces the ray picker of SampleExample::screenPicking [src/sample_example.cpp:468-511 -> nvvk::RayPickerKHR]: shoots one ray through
  * the normalised window position (pick_x, pick_y in [0,1], origin top-left like the reference's cursor position) with the given inverse view
  * and inverse projection matrices (column-major, as in pt_SceneCamera) and returns the nearest triangle -- every triangle counts, without
- * face culling or alpha test, like the picker's flag-less traceRayEXT.  Synchronous. */
+ * face culling or alpha test, like the picker's flag-less traceRayEXT.  Synchronous: waits for every frame in flight, then reports a
+ * traversal-stack overflow of those frames or of its own ray with PT_ERR_STATE. */
 int pt_pick(pt_context* ctx, float pick_x, float pick_y, const float view_inverse[16], const float proj_inverse[16], pt_PickResult* out);
 
 /* Measures, on this device, the two ceilings the measurement contract prices kernels against (no reference counterpart): VALU issue

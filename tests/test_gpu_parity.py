@@ -508,6 +508,8 @@ from tests.common import Config, render_hip
 from vk_raytrace_amd import synth
 if %r == "feature":
     cfg = Config(synth.feature_box(tex_size=32), synth.procedural_sky(128, 64), 160, 96, depth=6, max_samples=%d)
+elif %r == "spill":
+    cfg = Config(synth.deep_chain(synth.DEEP_SPILL_LEVELS), synth.procedural_sky(128, 64), 64, 48, depth=5, max_samples=%d)
 else:
     cfg = Config(synth.sponza_like(target_tris=30000, tex_size=64), synth.procedural_sky(128, 64), 192, 108, depth=6, max_samples=%d)
 frames = %d
@@ -541,7 +543,7 @@ else:
         r.setPushContants(st)
         r.run()
     np.save(sys.argv[1], r.read_accum())
-""" % (ROOT, scene.replace("camswitch", "feature").replace("perframe-", ""), max_samples, max_samples, frames, "perframe" if scene.startswith("perframe-") else scene, scene)
+""" % (ROOT, scene.replace("camswitch", "feature").replace("perframe-", ""), max_samples, scene, max_samples, max_samples, frames, "perframe" if scene.startswith("perframe-") else scene, scene)
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "acc.npy")
         env = dict(os.environ)
@@ -564,7 +566,9 @@ def test_launch_policy_never_changes_results():
                  "fuse=2,tail=0,batch=4", "accel=two,fuse=2,tail=0,batch=2", "fuse=2,tail=0,packetClosest=0,batch=5", "texGroups=0,texTile=0,fuse=2,tail=0,batch=2",
                  "batch=4,inflight=3,packetClosest=2", "batch=32,inflight=3,build=sah", "batch=3,inflight=1,build=lbvh", "batch=2,build=ploc", "build=sahdev", "stateGB=1",
                  "regen=0,batch=2,inflight=2", "accel=two,packetTwo=0", "accel=two,regen=0", "warm=0,texTile=0,shadeTris=0", "cnodes=0,shadeTris=0,batch=2,inflight=2,tail=0", "accel=two,cnodes=0,shadeTris=0",
-                 "accel=two,mergeSingles=0,tail=0,batch=2", "accel=two,batch=4,inflight=2,tail=100", "accel=two,build=lbvh,batch=3", "accel=two,build=sah,blasWorkers=1"]:
+                 "accel=two,mergeSingles=0,tail=0,batch=2", "accel=two,batch=4,inflight=2,tail=100", "accel=two,build=lbvh,batch=3", "accel=two,build=sah,blasWorkers=1",
+                 # each knob that picks a traversal / shading code path, alone
+                 "cnodes=0", "accel=two", "build=ploc", "build=sah", "fuse=0,tail=0", "regen=0", "shadeTris=0", "texGroups=0", "texTile=0"]:
         got = _render_in_subprocess(tune)
         assert np.array_equal(got, ref), tune
 

@@ -293,14 +293,22 @@ class TracedScene(Traced):
         self.keep = keep
         self.n = self.L.th_num_tris(self.h)
 
-    def settle(self, kind, two, exact, org, dirs, seeds, tmax=None, variant=0):
+    def settle(self, kind, two, exact, org, dirs, seeds, tmax=None, variant=0, sp_hist=False):
+        """sp_hist: also return the histogram of the deepest traversal-stack level each trace-machine walk (exact = 2) used (bin 64: 64 or
+        more) and the number of overflows (pushes beyond STACK_LDS + STACK_SPILL = 64 entries) instead of asserting that there are none"""
         org, dirs = np.ascontiguousarray(org, np.float32), np.ascontiguousarray(dirs, np.float32)
         seeds = np.ascontiguousarray(seeds, np.uint32)
         n = len(org)
         tm = None if tmax is None else np.ascontiguousarray(tmax, np.float32)
         w, tuv, sd, dr = np.zeros(n, np.uint32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        hist = np.zeros(65, np.uint64)
+        self.L.th_take_sp_hist.argtypes = [C.c_void_p]
+        self.L.th_take_sp_hist(hist.ctypes.data)
         over = self.L.th_settle(self.h, kind, two, exact, variant, n, org.ctypes.data, dirs.ctypes.data, tm.ctypes.data if tm is not None else None, seeds.ctypes.data,
                                 w.ctypes.data, tuv.ctypes.data, sd.ctypes.data, dr.ctypes.data)
+        self.L.th_take_sp_hist(hist.ctypes.data)
+        if sp_hist:
+            return w, tuv, sd, dr, hist, over
         assert over == 0
         return w, tuv, sd, dr
 
@@ -473,3 +481,65 @@ def test_host_build_renders_the_c3_stand_in_like_the_oracle():
     assert np.isfinite(ref).all() and ref[..., :3].max() > 0
     for two in (0, 1):
         assert _bits_equal(host_render(cfg, 4, two), ref), two
+
+
+# ---- deep structures: the premise of tests/test_gpu_edges.py ----------------------------------------------------------------------------------
+def _deep_rays(cfg):
+    """camera rays through the pixel centres of cfg (pinhole)"""
+    from vk_raytrace_amd.scene import Camera
+    cam: Camera = cfg.scene.camera
+    t = np.tan(np.radians(cam.fov) / 2)
+    ys, xs = np.mgrid[0:cfg.height, 0:cfg.width]
+    d = np.stack([(2 * (xs + 0.5) / cfg.width - 1) * t * cfg.width / cfg.height, (1 - 2 * (ys + 0.5) / cfg.height) * t, np.ones(xs.shape)], -1).reshape(-1, 3)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    o = np.broadcast_to(np.asarray(cam.eye, np.float64), d.shape)
+    return o, d
+
+
+@pytest.mark.parametrize("two,merge", [(0, True), (1, True), (1, False)])
+def test_deep_chain_reaches_the_spill_array_and_the_overflow(two, merge):
+    """synth.deep_chain at DEEP_SPILL_LEVELS: camera, bounce and shadow walks of the default builder's structure (device binned SAH, host
+    emulation) reach stack levels 25..64 -- beyond the LDS part (STACK_LDS = 24 entries), within the private spill array -- and none overflows.
+    At DEEP_OVERFLOW_LEVELS walks need more than 64 entries.  If a builder change flattens these trees this test fails, instead of the GPU
+    tests passing without reaching the spill path."""
+    from tests.common import Config
+    rng = np.random.default_rng(17)
+    env = synth.procedural_sky(64, 32)
+    harness().th_set_merge_singles(1 if merge else 0)
+    try:
+        tr = TracedScene(synth.deep_chain(synth.DEEP_SPILL_LEVELS))
+        deep = TracedScene(synth.deep_chain(synth.DEEP_OVERFLOW_LEVELS))
+    finally:
+        harness().th_set_merge_singles(1)
+    cfg = Config(synth.deep_chain(synth.DEEP_SPILL_LEVELS), env, 64, 48)
+    o, d = _deep_rays(cfg)
+    seeds = np.arange(len(o), dtype=np.uint32)
+    w, tuv, _, _, hist, over = tr.settle(0, two, 2, o, d, seeds, sp_hist=True)
+    assert over == 0
+    assert hist[64] == 0 and hist[25:64].sum() > 0.4 * hist.sum(), hist       # camera rays: most walks spill
+    hit = w != NONE
+    assert hit.mean() > 0.5
+    # bounce rays from where they hit, transmitted onwards (+z: the thin-walled slivers' main lobe), and shadow rays along the same
+    # directions (towards the environment's +z hemisphere, unbounded and bounded)
+    p = (o + d * tuv[:, :1])[hit]
+    k = len(p)
+    b = rng.normal(0, 1, (k, 3)); b[:, 2] = np.abs(b[:, 2]) + 1.0
+    b /= np.linalg.norm(b, axis=1, keepdims=True)
+    start = p + b * (1e-4 * np.abs(p).max(1, keepdims=True))
+    for kind, tmax in ((0, None), (1, np.full(k, 1e30, np.float32)), (1, rng.uniform(1e5, 1e7, k).astype(np.float32))):
+        _, _, _, _, hist, over = tr.settle(kind, two, 2, start, b, seeds[:k], tmax, sp_hist=True)
+        assert over == 0, kind
+        assert hist[64] == 0 and hist[25:64].sum() > 0.02 * hist.sum(), (kind, hist)   # bounce and shadow walks spill too
+    _, _, _, _, hist, over = deep.settle(0, two, 2, o, d, seeds, sp_hist=True)
+    assert over > 0 and hist[64] > 0.1 * hist.sum(), (over, hist)         # a share of the camera walks needs more than 64 entries
+    tr.close(); deep.close()
+
+
+def test_host_build_renders_the_spill_scene_like_the_oracle():
+    """the same deep scene through the product's shading source on the host (lock-step walks of k_tail, spill array included) == oracle"""
+    from tests.common import Config, render_oracle
+    cfg = Config(synth.deep_chain(synth.DEEP_SPILL_LEVELS), synth.procedural_sky(128, 64), 48, 32, depth=5, max_samples=2)
+    ref = render_oracle(cfg, 2)
+    assert np.isfinite(ref).all() and ref[..., :3].max() > 0
+    for two in (0, 1):
+        assert _bits_equal(host_render(cfg, 2, two), ref), two

@@ -317,6 +317,13 @@ def test_two_level_forest_build_runs_and_small_meshes(env_small):
     rng = np.random.default_rng(77)
     sc = Scene("forest")
     mats = [sc.add_material(pbrBaseColorFactor=(0.3 + 0.1 * k, 0.8 - 0.1 * k, 0.5, 1), doubleSided=1, pbrRoughnessFactor=0.6) for k in range(3)]
+    # some meshes alpha-tested (MASK, textured: the any-hit pass walks the forest's BLASes) and some blended (BLEND: stochastic alpha)
+    cut = np.zeros((16, 16, 4), np.uint8)
+    cut[..., :3] = rng.integers(60, 255, (16, 16, 3))
+    cut[..., 3] = np.where(rng.random((16, 16)) < 0.45, 0, 255)
+    mats.append(sc.add_material(pbrBaseColorTexture=sc.add_texture(cut), alphaMode=hd.ALPHA_MASK, alphaCutoff=0.5, doubleSided=1, pbrRoughnessFactor=0.7))
+    mats.append(sc.add_material(pbrBaseColorFactor=(0.9, 0.4, 0.2, 0.55), alphaMode=hd.ALPHA_BLEND, doubleSided=1, pbrRoughnessFactor=0.5))
+    mesh_mat = [0, 3, 1, 2, 4, 3, 0, 4, 1, 3]   # MASK on the meshes of 2, 12 and 90 triangles, BLEND on those of 300 and 1
 
     def soup(n_tris, spread):
         """n_tris random triangles around the origin"""
@@ -328,7 +335,7 @@ def test_two_level_forest_build_runs_and_small_meshes(env_small):
 
     sizes = [40, 2, 13, 1, 300, 12, 1, 1, 7, 90]   # runs: [40, 2, 13] | 1 | [300, 12] | 1 | 1 | [7, 90]
     for i, n in enumerate(sizes):
-        pm = sc.add_prim_mesh(*soup(n, 0.8), mats[i % 3])
+        pm = sc.add_prim_mesh(*soup(n, 0.8), mats[mesh_mat[i]])
         sc.add_node(pm, translate(-3.0 + 0.7 * i, 0.4 * ((i % 3) - 1), 0.0))
         sc.add_node(pm, translate(-3.0 + 0.7 * i, -0.6 + 0.3 * (i % 2), -1.0) @ rotate_y(0.4 * i) @ scale(0.8, 1.1, 0.9))
     sc.camera = Camera(eye=(0.2, 0.3, 6.5), center=(0, 0, 0), fov=50)

@@ -59,6 +59,7 @@ struct pt_context {
   std::vector<float>    hPrimBound;     // per prim-mesh: max |coordinate| of its vertices (object space); bounds the rounding of the ray transform
   double   msBuildTlas = 0;
   bool     renderedSinceCheck = false;
+  unsigned overflowSeen = 0;           // traversal-stack overflows counted so far (check_traversal); cleared with the counters
   bool     anyHit = true;               // RtxPipeline::useAnyHit (src/rtx_pipeline.cpp:269-276); false: every triangle is opaque
   std::vector<InstanceRec> hInstances;  // as built by pt_set_scene (flags without the useAnyHit override)  // frames were launched since the traversal-stack overflow counter was last looked at
   bool     haveScene = false, haveAccel = false, haveEnv = false, haveCamera = false;
@@ -119,6 +120,7 @@ struct pt_context {
     uint8_t*   host  = nullptr;
     size_t     bytes = 0, used = 0;
     hipEvent_t done = nullptr, read = nullptr;
+    unsigned*  overflow = nullptr;  // pinned: the overflow counter as the display pass saw it (pt_tonemap_end reports it)
   };
   DisplaySlot display[PT_DISPLAY_RING];
   uint64_t    displayHead = 0, displayTail = 0;  // oldest image not collected yet / next one to fill
@@ -249,18 +251,34 @@ hipError_t sync_all(pt_context* c)
 }
 // After a synchronisation: a traversal that ran out of stack (STACK_LDS + STACK_SPILL entries) dropped a subtree, so the image is wrong --
 // every call that hands results to the caller reports it instead of returning PT_OK with missing geometry.
+// The rule (include/pt_api.h, "Traversal-stack overflow"): pt_synchronize, pt_read_accum, pt_tonemap / pt_tonemap_zoom, pt_tonemap_end
+// (from the counter the display pass copied), pt_pick, pt_local_shard, pt_gather_shards and pt_get_stats return PT_ERR_STATE with this
+// message once an overflow has been counted, and so does pt_tonemap_begin once one is known; they keep doing so until the counter is
+// cleared -- by pt_reset_stats, or by pt_build_accel, since a new structure makes the old overflows meaningless.
+// Callers have synchronised (sync_all): the copies of the counter that pending display images carry have landed and are cleared with it.
+static void clear_overflow(pt_context* c)
+{
+  c->overflowSeen       = 0;
+  c->renderedSinceCheck = false;
+  for(auto& ds : c->display)
+    if(ds.overflow)
+      *ds.overflow = 0;
+}
+static int report_overflow(pt_context* c)
+{
+  return c->fail(PT_ERR_STATE, "BVH traversal stack overflowed %u times (the image is invalid: the acceleration structure is deeper than the traversal stack)",
+                 c->overflowSeen);
+}
 int check_traversal(pt_context* c)
 {
-  if(!c->renderedSinceCheck)
-    return PT_OK;
-  unsigned int n = 0;
-  HIP_TRY(c, hipMemcpy(&n, (const char*)c->dCounters.p + offsetof(Counters, stackOverflow), sizeof(n), hipMemcpyDeviceToHost));
-  c->renderedSinceCheck = false;
-  if(n)
+  if(c->renderedSinceCheck)
   {
-    return c->fail(PT_ERR_STATE, "BVH traversal stack overflowed %u times (the image is invalid: the acceleration structure is deeper than the traversal stack)", n);
+    unsigned int n = 0;
+    HIP_TRY(c, hipMemcpy(&n, (const char*)c->dCounters.p + offsetof(Counters, stackOverflow), sizeof(n), hipMemcpyDeviceToHost));
+    c->renderedSinceCheck = false;
+    c->overflowSeen       = n;
   }
-  return PT_OK;
+  return c->overflowSeen ? report_overflow(c) : PT_OK;
 }
 
 // the instance records as the kernels see them: with useAnyHit(false) every instance carries FORCE_OPAQUE, which is what a hit group
@@ -892,6 +910,8 @@ int pt_destroy(pt_context* c)
   {
     if(ds.host)
       (void)hipHostFree(ds.host);
+    if(ds.overflow)
+      (void)hipHostFree(ds.overflow);
     if(ds.done)
       (void)hipEventDestroy(ds.done);
     if(ds.read)
@@ -1307,6 +1327,9 @@ int pt_build_accel(pt_context* c)
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_all(c));
   c->haveAccel = false;
+  // overflows of the previous structure say nothing about the new one (check_traversal)
+  HIP_TRY(c, hipMemset((char*)c->dCounters.p + offsetof(Counters, stackOverflow), 0, sizeof(unsigned int)));
+  clear_overflow(c);
   if(c->accelMode == PT_ACCEL_TWO_LEVEL)
     return build_two_level(c);
   int rc;
@@ -2040,6 +2063,8 @@ int pt_write_accum(pt_context* c, const float* in)
   HIP_TRY(c, hipMemcpyAsync(c->dRowMajor.p, in, sizeof(float4) * size_t(c->width) * c->height, hipMemcpyHostToDevice, c->stream));
   pt_launch_retile(c->stream, (const float4*)c->dRowMajor.p, (const uint32_t*)c->dSlotTile.p, c->numLocalTiles, c->tilesX, c->width, c->height, (float4*)c->dFrame.p);
   HIP_TRY(c, hipGetLastError());
+  // the staging image keeps only what the untile writes back: pixels of other ranks read back as zero, as after rendering
+  HIP_TRY(c, hipMemsetAsync(c->dRowMajor.p, 0, sizeof(float4) * size_t(c->width) * c->height, c->stream));
   HIP_TRY(c, sync_all(c));
   c->haveFull = false;
   return PT_OK;
@@ -2059,8 +2084,9 @@ int pt_pick(pt_context* c, float pick_x, float pick_y, const float* view_inverse
   pt_launch_pick(c->stream, c->scene, pick_x, pick_y, view_inverse, proj_inverse, (pt_PickResult*)c->dPick.p, (Counters*)c->dCounters.p);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(out, c->dPick.p, sizeof(pt_PickResult), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return PT_OK;
+  HIP_TRY(c, sync_all(c));
+  c->renderedSinceCheck = true;  // the pick's own walk counts into the same counter
+  return check_traversal(c);
 }
 
 // ---- on-box calibration of the two rooflines bench.py prices against (no reference counterpart) ------------------------------------------
@@ -2273,6 +2299,8 @@ int pt_tonemap_begin(pt_context* c, const pt_Tonemapper* tm, int dispW, int disp
     return c->fail(PT_ERR_STATE, "pt_tonemap_begin: %d images are waiting for pt_tonemap_end", PT_DISPLAY_RING);
   if(dispW <= 0 || dispH <= 0 || dispW > 32768 || dispH > 32768)
     return c->fail(PT_ERR_INVALID, "pt_tonemap_begin: viewport %dx%d", dispW, dispH);
+  if(c->overflowSeen)  // known already: nothing is enqueued (without a synchronisation pt_tonemap_end is the call that finds out)
+    return report_overflow(c);
   HIP_TRY(c, hipSetDevice(c->device));
   pt_context::DisplaySlot& ds    = c->display[c->displayTail % PT_DISPLAY_RING];
   const size_t             bytes = 4 * size_t(dispW) * dispH;
@@ -2289,9 +2317,13 @@ int pt_tonemap_begin(pt_context* c, const pt_Tonemapper* tm, int dispW, int disp
     HIP_TRY(c, hipEventCreateWithFlags(&ds.done, hipEventDisableTiming));
   if(!ds.read)
     HIP_TRY(c, hipEventCreateWithFlags(&ds.read, hipEventDisableTiming));
+  if(!ds.overflow)
+    HIP_TRY(c, hipHostMalloc((void**)&ds.overflow, sizeof(unsigned), hipHostMallocDefault));
   int rc = enqueue_tonemap(c, tm, dispW, dispH, ds.host, ds.read);
   if(rc != PT_OK)
     return rc;
+  // behind the frames the pass reads (untile_to_rowmajor waits for them): the overflow counter, without a synchronisation here
+  HIP_TRY(c, hipMemcpyAsync(ds.overflow, (const char*)c->dCounters.p + offsetof(Counters, stackOverflow), sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipEventRecord(ds.done, c->stream));
   ds.used = bytes;
   c->displayTail++;
@@ -2313,7 +2345,9 @@ int pt_tonemap_end(pt_context* c, uint8_t* out)
   HIP_TRY(c, hipEventSynchronize(ds.done));
   std::memcpy(out, ds.host, ds.used);
   c->displayHead++;
-  return PT_OK;
+  if(*ds.overflow > c->overflowSeen)
+    c->overflowSeen = *ds.overflow;
+  return c->overflowSeen ? report_overflow(c) : PT_OK;
 }
 
 int pt_local_shard(pt_context* c, void** device_ptr, size_t* bytes, int* num_local_tiles, int* max_tiles_per_rank)
@@ -2323,6 +2357,13 @@ int pt_local_shard(pt_context* c, void** device_ptr, size_t* bytes, int* num_loc
     return c->fail(PT_ERR_STATE, "pt_local_shard before pt_resize");
   int rc = flush_pending(c);
   if(rc != PT_OK)
+    return rc;
+  if(c->renderedSinceCheck)  // the shard leaves the library here: the frames it holds must not have lost geometry
+  {
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_all(c));
+  }
+  if((rc = check_traversal(c)) != PT_OK)
     return rc;
   if(device_ptr) *device_ptr = c->dFrame.p;
   if(bytes) *bytes = sizeof(float4) * size_t(c->maxTilesPerRank) * 1024u;
@@ -2360,7 +2401,10 @@ int pt_scatter_shards(pt_context* c, const void* gathered_dev, int nranks)
 }
 
 // internal hooks of pt_comm.cpp (hidden: not part of the ABI)
-__attribute__((visibility("hidden"))) int pt_comm_internal_shard(pt_context* c, void** shard, size_t* bytes, int* rank, int* nranks, int root, void** gatherBuf, hipStream_t* stream, int* device)
+// traversal: check_traversal of the shard (PT_ERR_STATE after an overflow).  pt_gather_shards still takes part in the collective -- a rank
+// that left it would stall its peers -- and returns this code afterwards.
+__attribute__((visibility("hidden"))) int pt_comm_internal_shard(pt_context* c, void** shard, size_t* bytes, int* rank, int* nranks, int root, void** gatherBuf, hipStream_t* stream, int* device,
+                                                                  int* traversal)
 {
   CTX_CHECK(c);
   if(c->width == 0)
@@ -2369,6 +2413,7 @@ __attribute__((visibility("hidden"))) int pt_comm_internal_shard(pt_context* c, 
     return c->fail(PT_ERR_INVALID, "pt_gather_shards: root %d of %d ranks", root, c->nranks);
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_all(c));  // the shard is complete; the gather is enqueued on the context's stream
+  *traversal = check_traversal(c);
   *shard  = c->dFrame.p;
   *bytes  = sizeof(float4) * size_t(c->maxTilesPerRank) * 1024u;
   *rank   = c->rank;
@@ -2424,8 +2469,10 @@ int pt_get_stats(pt_context* c, pt_Stats* out)
   pt_timers_collect(&c->timers);
   Counters k{};
   HIP_TRY(c, hipMemcpy(&k, c->dCounters.p, sizeof(k), hipMemcpyDeviceToHost));
+  c->renderedSinceCheck = false;
+  c->overflowSeen       = k.stackOverflow;
   if(k.stackOverflow)
-    return c->fail(PT_ERR_STATE, "BVH traversal stack overflowed %u times (results are invalid)", k.stackOverflow);
+    return report_overflow(c);
   pt_Stats s = c->stats;
   s.closestRays = k.closestRays; s.shadowRays = k.shadowRays; s.shadedHits = k.shadedHits; s.misses = k.misses; s.alphaTests = k.alphaTests;
   s.neeLookups = k.neeLookups; s.nodesVisited = k.nodesVisited; s.trisTested = k.trisTested;
@@ -2470,6 +2517,7 @@ int pt_reset_stats(pt_context* c)
   c->timers.launchesFused   = 0;
   c->stats                  = pt_Stats{};
   HIP_TRY(c, hipMemset(c->dCounters.p, 0, sizeof(Counters)));
+  clear_overflow(c);
   return PT_OK;
 }
 

@@ -16,7 +16,8 @@
 #include <string>
 #include "../../include/pt_api.h"
 
-extern "C" int  pt_comm_internal_shard(pt_context* ctx, void** shard, size_t* bytes, int* rank, int* nranks, int root, void** gatherBuf, hipStream_t* stream, int* device);
+extern "C" int  pt_comm_internal_shard(pt_context* ctx, void** shard, size_t* bytes, int* rank, int* nranks, int root, void** gatherBuf, hipStream_t* stream, int* device,
+                                        int* traversal);
 extern "C" void pt_comm_internal_fail(pt_context* ctx, int code, const char* msg);
 
 namespace {
@@ -235,10 +236,10 @@ int pt_gather_shards(pt_context* ctx, pt_comm* comm, int root)
   void*       shard = nullptr;
   void*       gbuf  = nullptr;
   size_t      bytes = 0;
-  int         rank = 0, nranks = 1, device = 0;
+  int         rank = 0, nranks = 1, device = 0, traversal = PT_OK;
   hipStream_t stream = nullptr;
   // validates root against pt_set_shard's nranks and allocates the gather buffer on the root only
-  int         rc     = pt_comm_internal_shard(ctx, &shard, &bytes, &rank, &nranks, root, &gbuf, &stream, &device);
+  int         rc     = pt_comm_internal_shard(ctx, &shard, &bytes, &rank, &nranks, root, &gbuf, &stream, &device, &traversal);
   if(rc != PT_OK)
     return rc;
   rcclComm_t c  = reinterpret_cast<rcclComm_t>(comm);
@@ -293,6 +294,6 @@ int pt_gather_shards(pt_context* ctx, pt_comm* comm, int root)
     return nccl_fail(ctx, firstWhat, firstRc);
   if(r != 0)
     return nccl_fail(ctx, "ncclGroupEnd", r);
-  return PT_OK;
+  return traversal;  // PT_ERR_STATE: this rank's shard lost geometry to a traversal-stack overflow (the message is pt_last_error's)
 }
 }

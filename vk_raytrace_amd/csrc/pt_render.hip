@@ -1230,7 +1230,8 @@ void pt_launch_pick(hipStream_t stream, const DeviceScene& scene, float px, floa
 void pt_launch_untile(hipStream_t stream, const float4* frameTiles, const uint32_t* slotTile, uint32_t numLocalTiles, int tilesX, int width, int height, float4* outRowMajor)
 {
   uint32_t n = numLocalTiles * 1024u;
-  k_untile<<<(n + 255) / 256, 256, 0, stream>>>(frameTiles, slotTile, n, tilesX, width, height, outRowMajor);
+  if(n)  // a rank that owns no tile (more ranks than tiles): nothing to place, and a zero-block grid is a launch error
+    k_untile<<<(n + 255) / 256, 256, 0, stream>>>(frameTiles, slotTile, n, tilesX, width, height, outRowMajor);
 }
 
 void pt_launch_retile(hipStream_t stream, const float4* rowMajor, const uint32_t* slotTile, uint32_t numLocalTiles, int tilesX, int width, int height, float4* frameTiles)

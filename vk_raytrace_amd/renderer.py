@@ -194,8 +194,11 @@ class HipRenderer(Renderer):
             raise capi.PtError(capi.PT_ERR_STATE, "tonemap_end: the display ring and its Python shadow disagree (context re-created?)")
         w, h = self._display_sizes[0]
         out = np.empty((h, w, 4), np.uint8)
-        self._check(self._lib.pt_tonemap_end(self._ctx, out.ctypes.data))
-        self._display_sizes.pop(0)
+        pending = self.tonemap_pending()
+        rc = self._lib.pt_tonemap_end(self._ctx, out.ctypes.data)
+        if self.tonemap_pending() < pending:  # collected, also when it reports an error (a traversal-stack overflow): the two stay in step
+            self._display_sizes.pop(0)
+        self._check(rc)
         return out
 
     def measure_peaks(self):

@@ -593,6 +593,71 @@ def bistro_like(target_tris=3_800_000, tex_size=512, seed=SEED_BASE + 5, distinc
     return sc
 
 
+# deep_chain sizes (ratio 1.2) measured by tests/test_trace_host.py: walks reach stack levels 25..64 (the spill array) / go past 64 (overflow)
+DEEP_SPILL_LEVELS, DEEP_OVERFLOW_LEVELS = 80, 190
+
+
+def deep_chain(levels, ratio=1.2, seed=SEED_BASE + 7):
+    """Geometry that drives the traversal stack deep (tests/test_trace_host.py measures how deep, tests/test_gpu_edges.py renders it).
+
+    `levels` thin triangles ("slivers") cross the z axis at z = ratio**i, each `ratio` times larger than the one before it and turned by the
+    golden angle, so every sliver's box contains the axis.  The set is self-similar: the binned-SAH builder makes the same decision at every
+    scale -- peel off the few largest slivers as a sibling subtree, recurse into the rest -- and the tree becomes a chain whose near end holds
+    the smallest slivers.  A ray that starts at the small end and travels along +z passes through every box; at each level of the chain it
+    descends into the near subtree and pushes the far siblings, so the stack grows with the number of chain levels (about 0.45 entries per
+    sliver at ratio 1.2).  Most slivers are thin-walled transmissive (bounce rays keep travelling along +z); every 5th is an ALPHA_MASK card
+    with a checker texture and every 7th ALPHA_BLEND, so the alpha passes and the exact fallbacks walk the same stack.  The camera sits at the
+    apex looking along +z; the environment shows between the slivers."""
+    rng = np.random.default_rng(seed)
+    sc = Scene(f"deep_chain{levels}")
+    chk = np.zeros((8, 8, 4), np.uint8)
+    chk[..., :3] = (tex_albedo(rng, 8, (0.9, 0.8, 0.6), pattern="checker")[..., :3])
+    chk[..., 3] = np.where((np.arange(8)[:, None] + np.arange(8)[None, :]) % 2 == 0, 255, 0)
+    t_chk = sc.add_texture(chk, magFilter=hd.FILTER_NEAREST)
+    m_thin = sc.add_material(pbrBaseColorFactor=(0.9, 0.85, 0.8, 1), pbrMetallicFactor=0.0, pbrRoughnessFactor=0.3, transmissionFactor=0.85,
+                             thicknessFactor=0.0, doubleSided=1)
+    m_mask = sc.add_material(pbrBaseColorTexture=t_chk, alphaMode=hd.ALPHA_MASK, alphaCutoff=0.5, doubleSided=1, pbrMetallicFactor=0.0,
+                             pbrRoughnessFactor=0.7)
+    m_blend = sc.add_material(pbrBaseColorFactor=(0.3, 0.7, 0.9, 0.5), alphaMode=hd.ALPHA_BLEND, doubleSided=1, pbrMetallicFactor=0.0,
+                              pbrRoughnessFactor=0.6)
+    golden = np.pi * (3.0 - np.sqrt(5.0))
+    for i in range(levels):
+        z, s, w = ratio ** i, 0.5 * ratio ** i, 0.03 * ratio ** i
+        a = golden * i
+        ca, sa = np.cos(a), np.sin(a)
+        loc = np.array([[-s, -w], [s, -w], [0.0, 2.0 * w]])                  # centroid on the axis
+        xy = loc @ np.array([[ca, sa], [-sa, ca]])
+        pos = np.concatenate([xy, np.full((3, 1), z)], 1)
+        mat = m_mask if i % 5 == 4 else m_blend if i % 7 == 6 else m_thin
+        uv = (loc - loc.min(0)) / (2.0 * w) * 0.5                              # checker cells of about one sliver width
+        _add(sc, (pos.astype(np.float32), np.tile([[0.0, 0.0, -1.0]], (3, 1)).astype(np.float32), uv.astype(np.float32),
+                  np.arange(3, dtype=np.uint32), np.tile([[ca, sa, 0.0, 1.0]], (3, 1)).astype(np.float32)), mat)
+    sc.camera = Camera(eye=(0.0, 0.0, 0.0), center=(0.0, 0.0, 1.0), up=(0, 1, 0), fov=40.0)
+    return sc
+
+
+def bright_room(opening=0.6):
+    """A closed 4 x 3 x 4 room of white glossy metal (a bounce keeps almost all of the throughput, so after the first bounce Russian roulette
+    continues a path with the capped probability 0.95 and some paths last hundreds of bounces), one emissive panel, and a square opening of side
+    `opening` in the ceiling through which the environment lights the room; the camera is inside."""
+    sc = Scene("bright_room")
+    m_wall = sc.add_material(pbrBaseColorFactor=(1.0, 1.0, 1.0, 1), pbrMetallicFactor=1.0, pbrRoughnessFactor=0.05)
+    m_tint = sc.add_material(pbrBaseColorFactor=(1.0, 0.99, 0.97, 1), pbrMetallicFactor=1.0, pbrRoughnessFactor=0.15)
+    m_emit = sc.add_material(pbrBaseColorFactor=(0.1, 0.1, 0.1, 1), emissiveFactor=(4.0, 3.5, 3.0), pbrMetallicFactor=0.0)
+    _add(sc, grid(4, 4, (-2, 0, 2), (4, 0, 0), (0, 0, -4)), m_tint)           # floor, normal +y
+    _add(sc, grid(4, 3, (-2, 0, -2), (4, 0, 0), (0, 3, 0)), m_wall)           # back, normal +z
+    _add(sc, grid(4, 3, (2, 0, 2), (-4, 0, 0), (0, 3, 0)), m_wall)            # front, normal -z
+    _add(sc, grid(4, 3, (-2, 0, 2), (0, 0, -4), (0, 3, 0)), m_wall)           # left, normal +x
+    _add(sc, grid(4, 3, (2, 0, -2), (0, 0, 4), (0, 3, 0)), m_wall)            # right, normal -x
+    h = opening / 2.0                                                          # ceiling (normal -y) as four panels around the opening
+    for (x0, z0, dx, dz) in ((-2, -2, 4, 2 - h), (-2, h, 4, 2 - h), (-2, -h, 2 - h, 2 * h), (h, -h, 2 - h, 2 * h)):
+        _add(sc, grid(2, 2, (x0, 3, z0), (dx, 0, 0), (0, 0, dz)), m_wall)
+    _add(sc, grid(1, 1, (-1.6, 0.5, -1.99), (0.8, 0, 0), (0, 0.6, 0)), m_emit)  # panel on the back wall, normal +z
+    _add(sc, box((0.6, 0.9, 0.6)), m_tint, translate(0.6, 0.45, -0.5) @ rotate_y(0.4))
+    sc.camera = Camera(eye=(0.0, 1.5, 1.8), center=(0.0, 1.2, -1.0), up=(0, 1, 0), fov=60.0)
+    return sc
+
+
 def fuzz_scene(seed):
     """Random geometry chosen to stress the traversal: axis-aligned boxes on an integer lattice (rays parallel to faces, origins
     on box planes), slivers, tiny and huge triangles, coincident triangles (ties in t), mirrored / scaled instances, a mix of
