@@ -565,4 +565,62 @@ void orc_trace_closest(orc_ctx* c, uint32_t n, const float* org, const float* di
   }
 }
 
+// Environment_sample on a hand-made alias table: xi[3] width height pad[3] EnvAccel[width * height] -> to_light[3] pdf (uv: unused here, the
+// restatement does not expose it; the environment image is white, its lookup is the sampler's business)
+void orc_env_sample(const float* r, float* out, float* uv)
+{
+  Scene sc;
+  sc.envW = (int)r[3]; sc.envH = (int)r[4];
+  const size_t n = size_t(sc.envW) * sc.envH;
+  sc.envAccel.resize(n);
+  std::memcpy(sc.envAccel.data(), r + 8, n * sizeof(pt_EnvAccel));
+  sc.env.assign(n * 4, 1.0f);
+  pt_RtxState st{};
+  Tracer      tr(sc, st, 0);
+  vec3        l(0);
+  float       pdf = 0.0f;
+  tr.Environment_sample(vec3(r[0], r[1], r[2]), l, pdf);
+  out[0] = l.x; out[1] = l.y; out[2] = l.z; out[3] = pdf;
+}
+// EnvSample with Sun & Sky in use (env_sampling.glsl:111-125): pt_SunAndSky[24] seed -> lightDir[3] pdf, seed afterwards
+void orc_sun_disk_sample(const float* r, float* out)
+{
+  Scene sc;
+  std::memcpy(&sc.sunsky, r, sizeof(pt_SunAndSky));
+  sc.sunsky.in_use = 1;
+  pt_RtxState st{};
+  Tracer      tr(sc, st, 0);
+  std::memcpy(&tr.prd.seed, r + sizeof(pt_SunAndSky) / 4, 4);
+  vec3       radiance(0);
+  const vec4 l = tr.EnvSample(radiance);
+  out[0] = l.x; out[1] = l.y; out[2] = l.z; out[3] = l.w;
+  std::memcpy(out + 4, &tr.prd.seed, 4);
+}
+// the tonemap curves one at a time (tonemapping.glsl:29-65): rows rgb[3] exposure -> rgb[3].  fn: 0 linearTosRGB  1 sRGBToLinear  2 toneMapUncharted
+// 3 toneMapHejlRichard  4 toneMapACES  5 toneMap(color, exposure) (post.frag defines TONEMAP_UNCHARTED).  -1: not restated here (the display pass uses 0-2 only)
+int orc_tonemap_curve(int fn, uint64_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  if(fn < 0 || fn > 2)
+    return -1;
+  for(uint64_t i = 0; i < n; ++i)
+  {
+    const float* p = in + i * (uint64_t)in_stride;
+    const vec3   c(p[0], p[1], p[2]);
+    const vec3   r = fn == 0 ? linearTosRGB(c) : fn == 1 ? sRGBToLinear(c) : toneMapUncharted(c);
+    float*       o = out + i * (uint64_t)out_stride;
+    o[0] = r.x; o[1] = r.y; o[2] = r.z;
+  }
+  return 0;
+}
+#define PROBE_MUL_POINT(m, p) mul_point(m, p)
+#define PROBE_MUL_ROWVEC(p, m) mul_rowvec(p, m)
+#define PROBE_MUL_DIR(m, p) mul_dir(m, p)
+#define PROBE_MAT3_MUL(a, b, c, v) mul_mat3(a, b, c, v)
+#define PROBE_FN(x) orc_##x
+#define PROBE_MIX gmix
+#define PROBE_SMOOTHSTEP gsmoothstep
+#define PROBE_STEP gstep
+#define PROBE_CLAMP gclamp
+#include "probe_rows.h"  // orc_shading_probe: the probes above over arrays of states
+
 }  // extern "C"

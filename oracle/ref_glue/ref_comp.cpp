@@ -229,4 +229,53 @@ void ref_bsdf_sample(int pbrMode, const float* m, const float* N, const float* T
   L[0] = l.x; L[1] = l.y; L[2] = l.z; f[0] = r.x; f[1] = r.y; f[2] = r.z; *pdf = p;
 }
 
+// Environment_sample (env_sampling.glsl:38-99) on a hand-made alias table: xi[3] width height pad[3] EnvAccel[width * height] -> to_light[3] pdf.
+// The environment lookup at its end is the driver's: the hook installed here hands the shader's (u, v) back, so that they can be read too (uv, if given).
+static thread_local float s_envUv[2];
+static void env_uv_hook(void*, float u, float v, float* rgb) { s_envUv[0] = u; s_envUv[1] = v; rgb[0] = rgb[1] = rgb[2] = 1.0f; }
+void ref_env_sample(const float* r, float* out, float* uv)
+{
+  const RefHooks   keepHooks = g_hooks;
+  const sampler2D  keepTex   = environmentTexture;
+  const EnvAccel*  keepData  = envSamplingData;
+  g_hooks.sample_env      = env_uv_hook;
+  environmentTexture.kind = 1; environmentTexture.w = (int)r[3]; environmentTexture.h = (int)r[4];
+  envSamplingData         = reinterpret_cast<const EnvAccel*>(r + 8);
+  vec3  l(0);
+  float pdf = 0.0f;
+  Environment_sample(environmentTexture, vec3(r[0], r[1], r[2]), l, pdf);
+  out[0] = l.x; out[1] = l.y; out[2] = l.z; out[3] = pdf;
+  if(uv) { uv[0] = s_envUv[0]; uv[1] = s_envUv[1]; }
+  g_hooks = keepHooks; environmentTexture = keepTex; envSamplingData = keepData;
+}
+void ref_env_sample_uv(uint64_t n, const float* in, int in_stride, float* out4, float* uv2)
+{
+  for(uint64_t i = 0; i < n; ++i)
+    ref_env_sample(in + i * (uint64_t)in_stride, out4 + 4 * i, uv2 + 2 * i);
+}
+// EnvSample with Sun & Sky in use (env_sampling.glsl:111-125): pt_SunAndSky[24] seed -> lightDir[3] pdf, seed afterwards
+void ref_sun_disk_sample(const float* r, float* out)
+{
+  const SunAndSky keep = _sunAndSky;
+  std::memcpy(&_sunAndSky, r, sizeof(SunAndSky));
+  _sunAndSky.in_use = 1;
+  std::memcpy(&prd.seed, r + sizeof(SunAndSky) / 4, 4);
+  vec3       radiance(0);
+  const vec4 l = EnvSample(radiance);
+  out[0] = l.x; out[1] = l.y; out[2] = l.z; out[3] = l.w;
+  std::memcpy(out + 4, &prd.seed, 4);
+  _sunAndSky = keep;
+}
+#define PROBE_MUL_POINT(m, p) ((m) * vec4(p, 1.0f))
+#define PROBE_MUL_ROWVEC(p, m) vec3((p) * (m))
+#define PROBE_MUL_DIR(m, p) vec3(mat4(m) * vec4(p, 0.0f))
+#define PROBE_MAT3_MUL(a, b, c, v) (mat3(a, b, c) * (v))
+#define PROBE_FN(x) ref_##x
+#define PROBE_MIX mix
+#define PROBE_SMOOTHSTEP smoothstep
+#define PROBE_STEP step
+#define PROBE_CLAMP clamp
+#define PROBE_HAS_SCALAR_BUILTINS 1
+#include "../probe_rows.h"  // ref_shading_probe: the probes above over arrays of states
+
 }  // extern "C"

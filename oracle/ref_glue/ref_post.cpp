@@ -88,6 +88,22 @@ int ref_mip_chain(const float* rgba, int W, int H, int level, float* out, int* o
 
 // RenderOutput::genMipmap + RenderOutput::run on an accumulation image: out receives the fragment shader's fragColor (RGBA32F) per
 // pixel of a W x H viewport (the reference's swapchain then stores it as UNORM8).
+// the tonemap curves one at a time (tonemapping.glsl:29-105): rows rgb[3] exposure -> rgb[3].  fn: 0 linearTosRGB  1 sRGBToLinear  2 toneMapUncharted
+// 3 toneMapHejlRichard  4 toneMapACES  5 toneMap(color, exposure) as post.frag compiles it (TONEMAP_UNCHARTED)
+int ref_tonemap_curve(int fn, uint64_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  if(fn < 0 || fn > 5)
+    return -1;
+  for(uint64_t i = 0; i < n; ++i)
+  {
+    const float* p = in + i * (uint64_t)in_stride;
+    const vec3   c(p[0], p[1], p[2]);
+    const vec3   r = fn == 0 ? linearTosRGB(c) : fn == 1 ? sRGBToLinear(c) : fn == 2 ? toneMapUncharted(c) : fn == 3 ? toneMapHejlRichard(c) : fn == 4 ? toneMapACES(c) : toneMap(c, p[3]);
+    float*       o = out + i * (uint64_t)out_stride;
+    o[0] = r.x; o[1] = r.y; o[2] = r.z;
+  }
+  return 0;
+}
 int ref_tonemap(const pt_Tonemapper* t, const float* rgba, int W, int H, float* out)
 {
   MipChain mc;

@@ -183,6 +183,7 @@ static inline bool th_tri_test_certified(const TriRec& tr, uint32_t flags, f3 o,
 #include "pt_shade.h"  // pt_settle.h (pt_trace.h + the per-ray settle functions k_tail runs) + the shading steps of a path (generate_ray, shade_path, ...)
 #include "pt_machine.h"  // the resumable per-lane traversal of the persistent kernels (k_closest_p / k_shadow_p)
 #include "pt_cnode.h"    // WideNode -> CompactNode (what pt_accel.hip k_compact_nodes runs per node)
+#include "pt_probe.h"    // shading_probe: one call of a shading function per state (what pt_capi.hip k_shading_probe runs per lane)
 #include "../../include/pt_types.h"
 
 extern "C" int pt_debug_sahdev_topology(uint32_t n, const float* tri9, uint32_t* vals, uint32_t* childL, uint32_t* childR, uint32_t* parI, uint32_t* parL);
@@ -1337,6 +1338,20 @@ uint32_t th_render_shard(void* p, int two, const pt_RtxState* stIn, int variant,
       std::memcpy(out + (size_t(py) * W + px) * 4, &frame[slot], 16);
   }
   return total.stackOverflow;
+}
+
+// ---- the shading functions one at a time (pt_probe.h): BSDF evaluation / sampling, sun & sky, environment uv, tangent frame, punctual-light
+// attenuation, the GLSL built-ins of pt_math.h -- n states, one row each.  The device runs the same function per lane (pt_debug_shading_probe).
+int th_shading_probe(int fn, uint64_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  int inWords = 0, outWords = 0;
+  probe_row_words(fn, inWords, outWords);
+  if(inWords == 0 || in_stride < inWords || out_stride < outWords)
+    return -1;
+#pragma omp parallel for schedule(static)
+  for(long long i = 0; i < (long long)n; ++i)
+    shading_probe(fn, in + size_t(i) * in_stride, out + size_t(i) * out_stride);
+  return 0;
 }
 
 }  // extern "C"

@@ -78,6 +78,9 @@ def lib():
         L.ref_env_accel.argtypes = [P, C.c_int, C.c_int, P, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.ref_mip_chain.argtypes = [P, C.c_int, C.c_int, C.c_int, P, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.ref_tonemap.argtypes = [C.POINTER(hd.Tonemapper), P, C.c_int, C.c_int, P]
+        for fn in (L.ref_shading_probe, L.ref_glsl_builtin, L.ref_tonemap_curve):  # (fn, n, in, in_stride, out, out_stride): oracle/probe_rows.h
+            fn.restype, fn.argtypes = C.c_int, [C.c_int, C.c_uint64, P, C.c_int, P, C.c_int]
+        L.ref_env_sample_uv.argtypes = [C.c_uint64, P, C.c_int, P, P]
         _lib = L
     return _lib
 

@@ -41,7 +41,7 @@ def harness():
     capi.lib()  # libptmi.so must exist: the harness links its test hooks (device-builder emulation, two_level_pad)
     global OUT
     OUT = os.path.join(ROOT, "tests", "cpp", "_build", "libtracehost%s.so" % ("_" + FLAVOUR if FLAVOUR else ""))
-    deps = [SRC] + [os.path.join(ROOT, "vk_raytrace_amd", "csrc", f) for f in ("pt_trace.h", "pt_machine.h", "pt_settle.h", "pt_shade.h", "pt_surface.h", "pt_device.h", "pt_math.h", "pt_cnode.h")] + [capi.LIB_PATH]
+    deps = [SRC] + [os.path.join(ROOT, "vk_raytrace_amd", "csrc", f) for f in ("pt_trace.h", "pt_machine.h", "pt_settle.h", "pt_shade.h", "pt_surface.h", "pt_device.h", "pt_math.h", "pt_cnode.h", "pt_bsdf.h", "pt_sky.h", "pt_probe.h")] + [capi.LIB_PATH]
     if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
         os.makedirs(os.path.dirname(OUT), exist_ok=True)
         lib_dir = os.path.dirname(capi.LIB_PATH)
@@ -59,6 +59,8 @@ def harness():
     L.th_world_tri.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.th_candidates.restype = C.c_uint32
     L.th_candidates.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.th_shading_probe.restype = C.c_int
+    L.th_shading_probe.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int]  # csrc/pt_probe.h: (fn, n, in, in_stride, out, out_stride)
     return L
 
 

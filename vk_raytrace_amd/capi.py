@@ -80,6 +80,11 @@ API = [
     ("pt_gltf_free", None, [_P]),
 ]
 
+# test entry points that are exported but deliberately not part of include/pt_api.h
+DEBUG_API = [
+    ("pt_debug_shading_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h: (ctx, fn, n, in, in_stride, out, out_stride)
+]
+
 _lib = None
 
 
@@ -105,7 +110,7 @@ def lib():
         # library, and the RCCL it opens the same way (csrc/pt_comm.cpp), always share one runtime; a process that uses libptmi must simply not
         # initialise torch.cuda (bench.py's ranks use torch.distributed over gloo for the control plane only).
         L = C.CDLL(LIB_PATH, mode=os.RTLD_LOCAL | os.RTLD_DEEPBIND)
-        for name, res, args in API:
+        for name, res, args in API + DEBUG_API:
             fn = getattr(L, name)  # AttributeError if the ABI and the header ever disagree
             fn.restype = res
             fn.argtypes = args

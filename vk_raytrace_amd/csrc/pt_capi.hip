@@ -17,6 +17,7 @@
 #include <vector>
 #include "../../include/pt_api.h"
 #include "pt_internal.h"
+#include "pt_probe.h"
 
 namespace {
 std::string g_createError;
@@ -2220,6 +2221,47 @@ int pt_fpmath_eval(pt_context* c, int fn, uint64_t n, const float* a, const floa
 }
 
 }  // extern "C"
+// The shading functions one at a time on the device (pt_probe.h: the functions shade_path calls, no formula of its own): one state per lane, row i of
+// `in` -> row i of `out`.  tests/test_float_kat.py holds the result bit for bit to the host build of the same function (tests/cpp/trace_host.cpp).
+__global__ void k_shading_probe(int fn, uint32_t n, const float* __restrict__ in, int inStride, float* __restrict__ out, int outStride, int inWords, int outWords)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  float row[PROBE_BSDF_IN], res[8];
+  for(int k = 0; k < PROBE_BSDF_IN; ++k)
+    row[k] = k < inWords ? in[size_t(i) * inStride + k] : 0.0f;
+  for(int k = 0; k < 8; ++k)
+    res[k] = 0.0f;
+  shading_probe(fn, row, res);
+  for(int k = 0; k < outWords; ++k)
+    out[size_t(i) * outStride + k] = res[k];
+}
+extern "C" __attribute__((visibility("default"))) int pt_debug_shading_probe(pt_context* c, int fn, uint32_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  CTX_CHECK(c);
+  int inWords = 0, outWords = 0;
+  probe_row_words(fn, inWords, outWords);
+  if(inWords == 0 || inWords > PROBE_BSDF_IN || outWords > 8 || !in || !out || in_stride < inWords || out_stride < outWords || n > (1u << 24))
+    return c->fail(PT_ERR_INVALID, "pt_debug_shading_probe: bad arguments");
+  if(n == 0)
+    return PT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  float *dIn = nullptr, *dOut = nullptr;
+  auto   done = [&](int r) {
+    (void)hipFree(dIn); (void)hipFree(dOut);
+    return r;
+  };
+  const size_t inBytes = size_t(n) * in_stride * 4, outBytes = size_t(n) * out_stride * 4;
+  if(hipMalloc(&dIn, inBytes) != hipSuccess || hipMalloc(&dOut, outBytes) != hipSuccess)
+    return done(c->fail(PT_ERR_OOM, "pt_debug_shading_probe: out of device memory"));
+  if(hipMemcpy(dIn, in, inBytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dOut, out, outBytes, hipMemcpyHostToDevice) != hipSuccess)
+    return done(c->fail(PT_ERR_HIP, "pt_debug_shading_probe: upload failed"));
+  k_shading_probe<<<dim3((n + 63) / 64), dim3(64), 0, c->stream>>>(fn, n, dIn, in_stride, dOut, out_stride, inWords, outWords);
+  if(hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return done(c->fail(PT_ERR_HIP, "pt_debug_shading_probe: kernel failed"));
+  return done(PT_OK);
+}
 // The display pass enqueued on the context's stream, ending with the copy of the RGBA8 image to `out` (host memory; the caller synchronises).
 // readDone: recorded once the accumulation image has been read, and made the event the next frame's accumulate step waits for -- frames
 // rendered after this call may then overlap the rest of the pass.

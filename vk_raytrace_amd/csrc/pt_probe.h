@@ -1,0 +1,178 @@
+// Per-function probe of the shading source (test infrastructure, not part of include/pt_api.h): one state in, one result out, through the very
+// functions shade_path calls -- bsdf_eval / bsdf_sample (disney_*, gltf_*), sun_and_sky, spherical_uv, make_frame, range / spot attenuation and the
+// GLSL built-ins of pt_math.h (mirror, bend, lerp, smooth).  No formula lives here.  pt_capi.hip wraps it in a kernel (k_shading_probe, one state
+// per lane); tests/cpp/trace_host.cpp compiles the same function for the host (th_shading_probe).  tests/test_float_kat.py holds both to an
+// independent float64 model and to each other, bit for bit.
+//
+// Row layouts (32-bit words; integers travel as bit patterns):
+//   PROBE_EVAL_DISNEY / PROBE_EVAL_GLTF      in  m[22] N[3] T[3] B[3] eta thin V[3] L[3] seed   (PROBE_BSDF_IN = 40; m = albedo3 specular anisotropy metallic roughness subsurface specularTint sheen sheenTint3 clearcoat clearcoatRoughness transmission ior ax ay f0_3)
+//                                            out f[3] pdf
+//   PROBE_SAMPLE_DISNEY / PROBE_SAMPLE_GLTF  in  the same row (L unused)                        out L[3] f[3] pdf seed
+//   PROBE_SUN_AND_SKY                        in  pt_SunAndSky[24] dir[3]                        out rgb[3]
+//   PROBE_SPHERICAL_UV                       in  dir[3]                                         out uv[2]
+//   PROBE_FRAME                              in  N[3]                                           out T[3] B[3]
+//   PROBE_RANGE_ATTENUATION                  in  range distance                                 out 1
+//   PROBE_SPOT_ATTENUATION                   in  pointToLight[3] spotDir[3] outerCos innerCos   out 1
+//   PROBE_MIRROR                             in  I[3] N[3]                                      out 3
+//   PROBE_BEND                               in  I[3] N[3] eta                                  out 3
+//   PROBE_LERP                               in  a[3] b[3] t                                    out 3
+//   PROBE_SMOOTH                             in  e0 e1 x                                        out 1
+//   PROBE_ENV_SAMPLE                         in  xi[3] width height pad[3] pt_EnvAccel[width * height <= 8]   out toLight[3] pdf   (env_importance_sample; the radiance it returns is the sampler's business)
+//   PROBE_CROSS                              in  a[3] b[3]                                      out 3   (cross3)
+//   PROBE_UNIT                               in  a[3]                                           out 3   (unit = GLSL normalize)
+//   PROBE_MAT4_VEC4                          in  m[16] column-major, v[4]                       out 4   (mat4_mul = mat4 * vec4)
+//   PROBE_VEC4_MAT4                          no such function in the product (number kept in step with oracle/probe_rows.h)
+//   PROBE_XFORM_POINT / _ROWVEC / _DIR       in  m[12] = 4 columns of vec3 (a GLSL mat4x3), p[3] out 3   (M * vec4(p, 1), vec3(p * M), mat4(M) * vec4(p, 0) on the Affine rows)
+//   PROBE_BASIS_MUL                          in  c0[3] c1[3] c2[3] v[3]                         out 3   (mat3(c0, c1, c2) * v)
+#pragma once
+#include "pt_shade.h"
+
+enum {
+  PROBE_EVAL_DISNEY = 0, PROBE_EVAL_GLTF, PROBE_SAMPLE_DISNEY, PROBE_SAMPLE_GLTF, PROBE_SUN_AND_SKY, PROBE_SPHERICAL_UV, PROBE_FRAME, PROBE_RANGE_ATTENUATION,
+  PROBE_SPOT_ATTENUATION, PROBE_MIRROR, PROBE_BEND, PROBE_LERP, PROBE_SMOOTH, PROBE_ENV_SAMPLE, PROBE_CROSS, PROBE_UNIT, PROBE_MAT4_VEC4, PROBE_VEC4_MAT4,
+  PROBE_XFORM_POINT, PROBE_XFORM_ROWVEC, PROBE_XFORM_DIR, PROBE_BASIS_MUL, PROBE_COUNT
+};
+enum { PROBE_BSDF_IN = 40, PROBE_ENV_TEXELS = 8, PROBE_SKY_WORDS = int(sizeof(pt_SunAndSky) / 4) };
+
+// words a row of function fn must hold (0: no such function)
+__host__ __device__ inline void probe_row_words(int fn, int& in, int& out)
+{
+  switch(fn)
+  {
+    case PROBE_EVAL_DISNEY: case PROBE_EVAL_GLTF: in = PROBE_BSDF_IN; out = 4; break;
+    case PROBE_SAMPLE_DISNEY: case PROBE_SAMPLE_GLTF: in = PROBE_BSDF_IN; out = 8; break;
+    case PROBE_SUN_AND_SKY: in = PROBE_SKY_WORDS + 3; out = 3; break;
+    case PROBE_SPHERICAL_UV: in = 3; out = 2; break;
+    case PROBE_FRAME: in = 3; out = 6; break;
+    case PROBE_RANGE_ATTENUATION: in = 2; out = 1; break;
+    case PROBE_SPOT_ATTENUATION: in = 8; out = 1; break;
+    case PROBE_MIRROR: in = 6; out = 3; break;
+    case PROBE_BEND: case PROBE_LERP: in = 7; out = 3; break;
+    case PROBE_SMOOTH: in = 3; out = 1; break;
+    case PROBE_ENV_SAMPLE: in = 8 + 4 * PROBE_ENV_TEXELS; out = 4; break;
+    case PROBE_CROSS: in = 6; out = 3; break;
+    case PROBE_UNIT: in = 3; out = 3; break;
+    case PROBE_MAT4_VEC4: in = 20; out = 4; break;
+    case PROBE_XFORM_POINT: case PROBE_XFORM_ROWVEC: case PROBE_XFORM_DIR: in = 15; out = 3; break;
+    case PROBE_BASIS_MUL: in = 12; out = 3; break;
+    default: in = 0; out = 0; break;
+  }
+}
+
+PT_DEV f3 probe_f3(const float* p) { return f3{p[0], p[1], p[2]}; }
+PT_DEV void probe_put(float* o, f3 v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
+
+PT_DEV void probe_surface(Surface& s, const float* r)
+{
+  const float* m = r;
+  s.position = splat3(0.0f); s.normal = probe_f3(r + 22); s.ffnormal = s.normal; s.tangent = probe_f3(r + 25); s.bitangent = probe_f3(r + 28); s.uv = f2{0.0f, 0.0f};
+  s.albedo = probe_f3(m); s.specular = m[3]; s.emission = splat3(0.0f); s.anisotropy = m[4]; s.metallic = m[5]; s.roughness = m[6];
+  s.subsurface = m[7]; s.specularTint = m[8]; s.sheen = m[9]; s.sheenTint = probe_f3(m + 10); s.clearcoat = m[13];
+  s.clearcoatRoughness = m[14]; s.transmission = m[15]; s.ior = m[16]; s.attenuationColor = splat3(1.0f); s.attenuationDistance = 1.0f;
+  s.ax = m[17]; s.ay = m[18]; s.f0 = probe_f3(m + 19); s.alpha = 1.0f; s.unlit = false;
+  s.eta = r[31]; s.thinwalled = r[32] != 0.0f;
+}
+
+PT_DEV void shading_probe(int fn, const float* in, float* out)
+{
+  switch(fn)
+  {
+    case PROBE_EVAL_DISNEY:
+    case PROBE_EVAL_GLTF:
+    {
+      Surface s;
+      probe_surface(s, in);
+      float pdf = 0.0f;
+      probe_put(out, bsdf_eval(fn - PROBE_EVAL_DISNEY, s, probe_f3(in + 33), s.ffnormal, probe_f3(in + 36), pdf));
+      out[3] = pdf;
+      break;
+    }
+    case PROBE_SAMPLE_DISNEY:
+    case PROBE_SAMPLE_GLTF:
+    {
+      Surface s;
+      probe_surface(s, in);
+      float    pdf  = 0.0f;
+      uint32_t seed = __float_as_uint(in[39]);
+      f3       L    = splat3(0.0f);
+      const f3 f    = bsdf_sample(fn - PROBE_SAMPLE_DISNEY, s, probe_f3(in + 33), s.ffnormal, L, pdf, seed);
+      probe_put(out, L);
+      probe_put(out + 3, f);
+      out[6] = pdf;
+      out[7] = __uint_as_float(seed);
+      break;
+    }
+    case PROBE_SUN_AND_SKY:
+    {
+      pt_SunAndSky ss;
+      float        w[PROBE_SKY_WORDS];
+      for(int k = 0; k < PROBE_SKY_WORDS; ++k)
+        w[k] = in[k];
+      memcpy(&ss, w, sizeof(ss));
+      probe_put(out, sun_and_sky(ss, probe_f3(in + PROBE_SKY_WORDS)));
+      break;
+    }
+    case PROBE_SPHERICAL_UV:
+    {
+      const f2 uv = spherical_uv(probe_f3(in));
+      out[0] = uv.x; out[1] = uv.y;
+      break;
+    }
+    case PROBE_FRAME:
+    {
+      f3 T, B;
+      make_frame(probe_f3(in), T, B);
+      probe_put(out, T);
+      probe_put(out + 3, B);
+      break;
+    }
+    case PROBE_RANGE_ATTENUATION: out[0] = range_attenuation(in[0], in[1]); break;
+    case PROBE_SPOT_ATTENUATION: out[0] = spot_attenuation(probe_f3(in), probe_f3(in + 3), in[6], in[7]); break;
+    case PROBE_MIRROR: probe_put(out, mirror(probe_f3(in), probe_f3(in + 3))); break;
+    case PROBE_BEND: probe_put(out, bend(probe_f3(in), probe_f3(in + 3), in[6])); break;
+    case PROBE_LERP: probe_put(out, lerp(probe_f3(in), probe_f3(in + 3), in[6])); break;
+    case PROBE_SMOOTH: out[0] = smooth(in[0], in[1], in[2]); break;
+    case PROBE_ENV_SAMPLE:
+    {
+      const int w = int(in[3]), h = int(in[4]);
+      if(w < 1 || h < 1 || w * h > PROBE_ENV_TEXELS)
+        break;
+      pt_EnvAccel acc[PROBE_ENV_TEXELS];
+      float4      texels[PROBE_ENV_TEXELS];
+      for(int k = 0; k < PROBE_ENV_TEXELS; ++k)
+      {
+        acc[k].alias = __float_as_uint(in[8 + 4 * k]); acc[k].q = in[9 + 4 * k]; acc[k].pdf = in[10 + 4 * k]; acc[k].aliasPdf = in[11 + 4 * k];
+        texels[k] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+      }
+      DeviceScene S;
+      memset(&S, 0, sizeof(S));
+      S.env = texels; S.envAccel = acc; S.envW = w; S.envH = h;
+      f3    toLight = splat3(0.0f);
+      float pdf     = 0.0f;
+      (void)env_importance_sample(S, probe_f3(in), toLight, pdf);
+      probe_put(out, toLight);
+      out[3] = pdf;
+      break;
+    }
+    case PROBE_CROSS: probe_put(out, cross3(probe_f3(in), probe_f3(in + 3))); break;
+    case PROBE_UNIT: probe_put(out, unit(probe_f3(in))); break;
+    case PROBE_MAT4_VEC4:
+    {
+      const f4 r = mat4_mul(in, f4{in[16], in[17], in[18], in[19]});
+      out[0] = r.x; out[1] = r.y; out[2] = r.z; out[3] = r.w;
+      break;
+    }
+    case PROBE_XFORM_POINT:
+    case PROBE_XFORM_ROWVEC:
+    case PROBE_XFORM_DIR:
+    {
+      Affine m;  // row r of the column-major matrix, as the scene records store it
+      m.r0 = make_float4(in[0], in[3], in[6], in[9]); m.r1 = make_float4(in[1], in[4], in[7], in[10]); m.r2 = make_float4(in[2], in[5], in[8], in[11]);
+      const f3 p = probe_f3(in + 12);
+      probe_put(out, fn == PROBE_XFORM_POINT ? xform_point(m, p) : fn == PROBE_XFORM_ROWVEC ? xform_rowvec(p, m) : xform_dir(m, p));
+      break;
+    }
+    case PROBE_BASIS_MUL: probe_put(out, basis_mul(probe_f3(in), probe_f3(in + 3), probe_f3(in + 6), probe_f3(in + 9))); break;
+    default: break;
+  }
+}
