@@ -443,6 +443,8 @@ void orc_sample_texture(orc_ctx* c, int id, float u, float v, float* out)
   vec4 t = c->scene.sample_texture(id, vec2(u, v), nullptr);
   out[0] = t.x; out[1] = t.y; out[2] = t.z; out[3] = t.w;
 }
+// the address modes on their own (tests/test_texture_model.py holds them to an independent model on every integer that matters)
+int orc_wrap_coord(int i, int n, int mode) { return Scene::wrap_coord(i, n, mode); }
 
 // ---- the "driver" side of oracle/_ref (oracle/ref_glue/ref_driver.h RefHooks): the reference's shader code compiled from its own
 // sources calls back here for what the Vulkan driver would supply -- triangle candidates in the order of the trace contract

@@ -1354,4 +1354,37 @@ int th_shading_probe(int fn, uint64_t n, const float* in, int in_stride, float* 
   return 0;
 }
 
+// ---- the software texture path one call at a time (pt_probe.h texture_probe) on a scene made by th_create_scene: the product's own records, material
+// lines, opacity maps and pool (pt_debug_scene_records), the environment of th_set_env.  The device runs the same function per lane (pt_debug_texture_probe).
+int th_texture_probe(void* p, int kind, uint64_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  Scene* s = static_cast<Scene*>(p);
+  if(!s || kind < 0 || kind >= TEXP_COUNT || in_stride < TEXP_IN || out_stride < TEXP_OUT)
+    return -1;
+  const TexProbeLimits lim{uint32_t(s->texRecs.size()), uint32_t(s->alphaMats.size() < s->matLines.size() / PT_MAT_LINE_QUADS ? s->alphaMats.size() : s->matLines.size() / PT_MAT_LINE_QUADS),
+                           uint32_t(s->texels.size())};
+#pragma omp parallel for schedule(static)
+  for(long long i = 0; i < (long long)n; ++i)
+    texture_probe(s->dsFlat, lim, kind, in + size_t(i) * in_stride, out + size_t(i) * out_stride);
+  return 0;
+}
+// the scene's texture records (TexRec, 32 B each), material lines (PT_MAT_LINE_QUADS x 16 B per material), alpha view (AlphaMat, 80 B each), opacity maps
+// and texel pool as th_create_scene fetched them; null outputs: the counts only (records, materials, map words, pool texels)
+void th_texture_records(void* p, unsigned long long* counts4, void* texRecsOut, void* matLinesOut, void* alphaMatsOut, uint32_t* alphaMapsOut, uint32_t* texelsOut)
+{
+  Scene* s = static_cast<Scene*>(p);
+  counts4[0] = s->texRecs.size(); counts4[1] = s->matLines.size() / PT_MAT_LINE_QUADS; counts4[2] = s->alphaMaps.size(); counts4[3] = s->texels.size();
+  if(texRecsOut) std::memcpy(texRecsOut, s->texRecs.data(), sizeof(TexRec) * s->texRecs.size());
+  if(matLinesOut) std::memcpy(matLinesOut, s->matLines.data(), sizeof(uint4) * s->matLines.size());
+  if(alphaMatsOut) std::memcpy(alphaMatsOut, s->alphaMats.data(), sizeof(AlphaMat) * s->alphaMats.size());
+  if(alphaMapsOut) std::memcpy(alphaMapsOut, s->alphaMaps.data(), 4 * s->alphaMaps.size());
+  if(texelsOut) std::memcpy(texelsOut, s->texels.data(), 4 * s->texels.size());
+}
+// ALPHA_FAST_TAP cleared in every alpha record: opacity_eval then takes the general path (sample_rgba8_rec, wrap_index) and finds no map to ask
+void th_clear_fast_tap(void* p)
+{
+  for(AlphaMat& a : static_cast<Scene*>(p)->alphaMats)
+    a.texWrap &= ~ALPHA_FAST_TAP;
+}
+
 }  // extern "C"

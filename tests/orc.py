@@ -64,6 +64,8 @@ def lib():
         L.orc_sampler_from_gltf.argtypes = [C.c_int] * 5 + [C.POINTER(hd.TextureDesc)]
         L.orc_sun_and_sky.argtypes = [C.POINTER(hd.SunAndSky), C.c_void_p, C.c_void_p]
         L.orc_sample_texture.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p]
+        L.orc_hook_sample_env.restype, L.orc_hook_sample_env.argtypes = None, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]   # (ctx, u, v, rgb): sample_env as the reference's hook
+        L.orc_wrap_coord.restype, L.orc_wrap_coord.argtypes = C.c_int, [C.c_int, C.c_int, C.c_int]   # (i, n, mode)
         L.orc_trace_closest.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 7
         for fn in (L.orc_shading_probe, L.orc_glsl_builtin, L.orc_tonemap_curve):  # (fn, n, in, in_stride, out, out_stride): oracle/probe_rows.h
             fn.restype, fn.argtypes = C.c_int, [C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int]

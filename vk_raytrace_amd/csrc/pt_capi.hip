@@ -2262,6 +2262,54 @@ extern "C" __attribute__((visibility("default"))) int pt_debug_shading_probe(pt_
     return done(c->fail(PT_ERR_HIP, "pt_debug_shading_probe: kernel failed"));
   return done(PT_OK);
 }
+// The software texture path one call at a time on the device (pt_probe.h texture_probe), on the scene the context holds: one row per lane.  tests/test_texture_model.py
+// holds the result bit for bit to the host build of the same function (tests/cpp/trace_host.cpp th_texture_probe); this is where the device's own index
+// arithmetic (tex_index's 24-bit multiply) is seen.  Not part of the ABI.
+__global__ void k_texture_probe(DeviceScene S, TexProbeLimits lim, int kind, uint32_t n, const float* __restrict__ in, int inStride, float* __restrict__ out, int outStride)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  float row[TEXP_IN], res[TEXP_OUT];
+  for(int k = 0; k < TEXP_IN; ++k)
+    row[k] = in[size_t(i) * inStride + k];
+  for(int k = 0; k < TEXP_OUT; ++k)
+    res[k] = out[size_t(i) * outStride + k];
+  texture_probe(S, lim, kind, row, res);
+  for(int k = 0; k < TEXP_OUT; ++k)
+    out[size_t(i) * outStride + k] = res[k];
+}
+extern "C" __attribute__((visibility("default"))) int pt_debug_texture_probe(pt_context* c, int kind, uint32_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  CTX_CHECK(c);
+  if(kind < 0 || kind >= TEXP_COUNT || !in || !out || in_stride < TEXP_IN || out_stride < TEXP_OUT || n > (1u << 24))
+    return c->fail(PT_ERR_INVALID, "pt_debug_texture_probe: bad arguments");
+  if(!c->haveScene)
+    return c->fail(PT_ERR_STATE, "pt_debug_texture_probe before pt_set_scene");
+  if(kind == TEXP_ENV && !c->haveEnv)
+    return c->fail(PT_ERR_STATE, "pt_debug_texture_probe: no environment");
+  if(n == 0)
+    return PT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_all(c));
+  // what the device arrays are known to hold (an allocation is at least as large as its last upload)
+  const size_t         mats = std::min(c->dMatLines.bytes / (sizeof(uint4) * PT_MAT_LINE_QUADS), std::min(c->dAlphaMats.bytes / sizeof(AlphaMat), c->dMaterials.bytes / sizeof(pt_GltfShadeMaterial)));
+  const TexProbeLimits lim{uint32_t(c->dTexRecs.bytes / sizeof(TexRec)), uint32_t(mats), uint32_t(std::min<size_t>(c->dTexels.bytes / 4, 0xffffffffu))};
+  float *dIn = nullptr, *dOut = nullptr;
+  auto   done = [&](int r) {
+    (void)hipFree(dIn); (void)hipFree(dOut);
+    return r;
+  };
+  const size_t inBytes = size_t(n) * in_stride * 4, outBytes = size_t(n) * out_stride * 4;
+  if(hipMalloc(&dIn, inBytes) != hipSuccess || hipMalloc(&dOut, outBytes) != hipSuccess)
+    return done(c->fail(PT_ERR_OOM, "pt_debug_texture_probe: out of device memory"));
+  if(hipMemcpy(dIn, in, inBytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dOut, out, outBytes, hipMemcpyHostToDevice) != hipSuccess)
+    return done(c->fail(PT_ERR_HIP, "pt_debug_texture_probe: upload failed"));
+  k_texture_probe<<<dim3((n + 63) / 64), dim3(64), 0, c->stream>>>(c->scene, lim, kind, n, dIn, in_stride, dOut, out_stride);
+  if(hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return done(c->fail(PT_ERR_HIP, "pt_debug_texture_probe: kernel failed"));
+  return done(PT_OK);
+}
 // The display pass enqueued on the context's stream, ending with the copy of the RGBA8 image to `out` (host memory; the caller synchronises).
 // readDone: recorded once the accumulation image has been read, and made the event the next frame's accumulate step waits for -- frames
 // rendered after this call may then overlap the rest of the pass.

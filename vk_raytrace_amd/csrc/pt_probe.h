@@ -176,3 +176,111 @@ PT_DEV void shading_probe(int fn, const float* in, float* out)
     default: break;
   }
 }
+
+// ---- the software texture path one call at a time (tests/test_texture_model.py): the functions of pt_surface.h / pt_device.h on the records and the pool of
+// a scene that is loaded -- tex_tap / tex_filter as resolve_material uses them, sample_rgba8_rec, opacity_eval with and without the opacity map, sample_env,
+// wrap_index, tex_index.  No formula lives here either.  Rows of TEXP_IN words in, TEXP_OUT words out (integers travel as bit patterns):
+//   TEXP_TAP          in  id slot u v       out i[4] a b     slot -1: the plain record texRecs[id]; 0..3: that descriptor of material id's line.  NO loads.
+//   TEXP_SAMPLE_REC   in  id - u v          out rgba         sample_rgba8_rec on texRecs[id]
+//   TEXP_SAMPLE_DESC  in  material slot u v out rgba         tex_desc_unpack, tex_tap, four loads, tex_filter: the lines of resolve_material
+//   TEXP_OPACITY      in  uv0[2] uv1[2] uv2[2] material bu bv   out opacity_eval<false>, opacity_eval<true>
+//   TEXP_ENV          in  u v               out rgb          sample_env
+//   TEXP_WRAP         in  i n mode pot      out wrap_index
+//   TEXP_INDEX        in  w ix iy tiled     out tex_index
+//   TEXP_DESC         in  id slot           out offset w h mag wrapS wrapT pot tiled of tex_desc_unpack(tex_desc_pack(r)), r the record TEXP_TAP would use
+// The kinds that load leave a row alone (its output stays as the caller filled it) unless every texel index of its tap is below `poolTexels` and its
+// coordinates are inside the domain of the numerical contract (|u W|, |v H| < 2^30): a probe must not be able to read outside the pool.
+enum { TEXP_TAP = 0, TEXP_SAMPLE_REC, TEXP_SAMPLE_DESC, TEXP_OPACITY, TEXP_ENV, TEXP_WRAP, TEXP_INDEX, TEXP_DESC, TEXP_COUNT };
+enum { TEXP_IN = 12, TEXP_OUT = 8 };
+struct TexProbeLimits {
+  uint32_t numTexRecs, numMaterials, poolTexels;  // what the scene's arrays hold
+};
+
+PT_DEV bool texp_in_domain(const TexRec& tr, f2 uv) { return fabsf(uv.x * float(tr.w)) < 1073741824.0f && fabsf(uv.y * float(tr.h)) < 1073741824.0f; }
+PT_DEV bool texp_record(const DeviceScene& S, const TexProbeLimits& lim, int id, int slot, TexRec& tr)
+{
+  if(id < 0 || slot < -1 || slot > 3)
+    return false;
+  if(slot < 0)
+  {
+    if(uint32_t(id) >= lim.numTexRecs)
+      return false;
+    tr = S.texRecs[id];
+    return true;
+  }
+  if(uint32_t(id) >= lim.numMaterials)
+    return false;
+  tr = tex_desc_unpack(S.matLines[size_t(id) * PT_MAT_LINE_QUADS + 3 + slot]);
+  return true;
+}
+
+PT_DEV void texture_probe(const DeviceScene& S, const TexProbeLimits& lim, int kind, const float* in, float* out)
+{
+  const int i0 = __float_as_int(in[0]), i1 = __float_as_int(in[1]);
+  const f2  uv = f2{in[2], in[3]};
+  switch(kind)
+  {
+    case TEXP_TAP:
+    case TEXP_SAMPLE_REC:
+    case TEXP_SAMPLE_DESC:
+    {
+      TexRec tr;
+      if(!texp_record(S, lim, i0, kind == TEXP_SAMPLE_REC ? -1 : i1, tr))
+        break;
+      const TexTap t = tex_tap(tr, uv);
+      if(kind == TEXP_TAP)
+      {
+        for(int k = 0; k < 4; ++k)
+          out[k] = __uint_as_float(t.i[k]);
+        out[4] = t.a; out[5] = t.b;
+        break;
+      }
+      if(!texp_in_domain(tr, uv) || t.i[0] >= lim.poolTexels || t.i[1] >= lim.poolTexels || t.i[2] >= lim.poolTexels || t.i[3] >= lim.poolTexels)
+        break;
+      const f4 c = kind == TEXP_SAMPLE_REC ? sample_rgba8_rec(S.texels, tr, uv) : tex_filter(t, S.texels[t.i[0]], S.texels[t.i[1]], S.texels[t.i[2]], S.texels[t.i[3]]);
+      out[0] = c.x; out[1] = c.y; out[2] = c.z; out[3] = c.w;
+      break;
+    }
+    case TEXP_OPACITY:
+    {
+      const uint32_t m = __float_as_uint(in[6]);
+      if(m >= lim.numMaterials)
+        break;
+      bool ok = true;  // |coordinates| <= 4 and |uvTransform| <= 16 keep the transformed coordinate far inside the domain for every image size
+      for(int k = 0; k < 9; ++k)
+        ok = ok && (k == 6 || fabsf(in[k]) <= 4.0f);
+      for(int k = 0; k < 8; ++k)
+        ok = ok && fabsf(S.alphaMats[m].m[k]) <= 16.0f;
+      if(!ok)
+        break;
+      AlphaRec ar;
+      ar.uv0[0] = in[0]; ar.uv0[1] = in[1]; ar.uv1[0] = in[2]; ar.uv1[1] = in[3]; ar.uv2[0] = in[4]; ar.uv2[1] = in[5];
+      ar.material = m; ar._pad = 0u;
+      out[0] = opacity_eval<false>(S, ar, in[7], in[8]);
+      out[1] = opacity_eval<true>(S, ar, in[7], in[8]);
+      break;
+    }
+    case TEXP_ENV:
+    {
+      const f2 e = f2{in[0], in[1]};
+      if(S.env == nullptr || S.envW < 1 || S.envH < 1 || !(fabsf(e.x * float(S.envW)) < 1073741824.0f && fabsf(e.y * float(S.envH)) < 1073741824.0f))
+        break;
+      probe_put(out, sample_env(S, e));
+      break;
+    }
+    case TEXP_WRAP: out[0] = __int_as_float(wrap_index(i0, i1, __float_as_int(in[2]), __float_as_int(in[3]) != 0)); break;
+    case TEXP_INDEX: out[0] = __uint_as_float(tex_index(i0, i1, __float_as_int(in[2]), __float_as_int(in[3]) != 0)); break;
+    case TEXP_DESC:
+    {
+      TexRec tr;
+      if(!texp_record(S, lim, i0, i1, tr))
+        break;
+      const TexRec   r    = tex_desc_unpack(tex_desc_pack(tr));
+      const uint32_t w[8] = {r.offset, uint32_t(r.w), uint32_t(r.h), uint32_t(r.mag), uint32_t(r.wrapS), uint32_t(r.wrapT), uint32_t(r.pot), uint32_t(r.tiled)};
+      for(int k = 0; k < 8; ++k)
+        out[k] = __uint_as_float(w[k]);
+      break;
+    }
+    default: break;
+  }
+}

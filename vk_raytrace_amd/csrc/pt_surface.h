@@ -33,6 +33,12 @@ PT_DEV int wrap_index(int i, int n, int mode, bool pot)
   return m < 0 ? m + n : m;
 }
 
+// Floored float texel coordinate -> int.  Beyond +-2^30, and for NaN, the conversion -- and the `x0 + 1` of a bilinear tap after it -- is undefined in C++; the device's
+// conversion saturates at INT_MAX, and with the successor's overflow "impossible" the compiler folds the + 1 through the clamp of CLAMP_TO_EDGE: the tap of an
+// infinite coordinate came out as texel index 2^31 (tests/test_texture_model.py, the rows outside the domain).  So clamp first (NaN -> -2^30): every index stays inside
+// the image for every float.  Inside the domain of the numerical contract (|x| < 2^30) the value is untouched.
+PT_DEV int texel_coord(float f) { return (int)fminf(fmaxf(f, -1073741824.0f), 1073741824.0f); }
+
 PT_DEV uint32_t tex_layers(const TexRec& tr) { return ((uint32_t(tr.tiled) >> 8) & 3u) + 1u; }
 PT_DEV uint32_t tex_layer(const TexRec& tr) { return (uint32_t(tr.tiled) >> 10) & 3u; }
 PT_DEV f4 texel_bytes(const uint32_t* pool, const TexRec& tr, int ix, int iy)
@@ -48,12 +54,12 @@ PT_DEV f4 sample_rgba8_rec(const uint32_t* texels, const TexRec& tr, f2 uv)
   const float  s255 = 1.0f / 255.0f;
   float        x = uv.x * float(tr.w), y = uv.y * float(tr.h);
   if(tr.mag == PT_FILTER_NEAREST)
-    return texel_bytes(texels, tr, (int)floorf(x), (int)floorf(y)) * s255;
+    return texel_bytes(texels, tr, texel_coord(floorf(x)), texel_coord(floorf(y))) * s255;
   x -= 0.5f;
   y -= 0.5f;
   float fx = floorf(x), fy = floorf(y);
   float a = x - fx, b = y - fy;
-  int   x0 = (int)fx, y0 = (int)fy;
+  int   x0 = texel_coord(fx), y0 = texel_coord(fy);
   f4    top = texel_bytes(texels, tr, x0, y0) * (1.0f - a) + texel_bytes(texels, tr, x0 + 1, y0) * a;
   f4    bot = texel_bytes(texels, tr, x0, y0 + 1) * (1.0f - a) + texel_bytes(texels, tr, x0 + 1, y0 + 1) * a;
   return (top * (1.0f - b) + bot * b) * s255;
@@ -81,7 +87,7 @@ PT_DEV TexTap tex_tap(const TexRec& tr, f2 uv)
   if(t.nearest)
   {
     t.a = t.b = 0.0f;
-    t.i[0] = t.i[1] = t.i[2] = t.i[3] = base + tex_index(tr.w, wrap_index((int)floorf(x), tr.w, tr.wrapS, ps), wrap_index((int)floorf(y), tr.h, tr.wrapT, pt), tiled) * K;
+    t.i[0] = t.i[1] = t.i[2] = t.i[3] = base + tex_index(tr.w, wrap_index(texel_coord(floorf(x)), tr.w, tr.wrapS, ps), wrap_index(texel_coord(floorf(y)), tr.h, tr.wrapT, pt), tiled) * K;
     return t;
   }
   x -= 0.5f;
@@ -89,7 +95,7 @@ PT_DEV TexTap tex_tap(const TexRec& tr, f2 uv)
   const float fx = floorf(x), fy = floorf(y);
   t.a = x - fx;
   t.b = y - fy;
-  const int x0 = (int)fx, y0 = (int)fy;
+  const int x0 = texel_coord(fx), y0 = texel_coord(fy);
   const int wx0 = wrap_index(x0, tr.w, tr.wrapS, ps), wx1 = wrap_index(x0 + 1, tr.w, tr.wrapS, ps), wy0 = wrap_index(y0, tr.h, tr.wrapT, pt), wy1 = wrap_index(y0 + 1, tr.h, tr.wrapT, pt);
   t.i[0] = base + tex_index(tr.w, wx0, wy0, tiled) * K;
   t.i[1] = base + tex_index(tr.w, wx1, wy0, tiled) * K;
@@ -114,7 +120,7 @@ PT_DEV f3 sample_env(const DeviceScene& S, f2 uv)
   float x = uv.x * float(S.envW) - 0.5f, y = uv.y * float(S.envH) - 0.5f;
   float fx = floorf(x), fy = floorf(y);
   float a = x - fx, b = y - fy;
-  int   x0 = (int)fx, y0 = (int)fy;
+  int   x0 = texel_coord(fx), y0 = texel_coord(fy);
   const bool wpot = (S.envW & (S.envW - 1)) == 0;
   int   xa = wrap_index(x0, S.envW, PT_WRAP_REPEAT, wpot), xb = wrap_index(x0 + 1, S.envW, PT_WRAP_REPEAT, wpot);
   int   ya = wrap_index(y0, S.envH, PT_WRAP_CLAMP_TO_EDGE, false), yb = wrap_index(y0 + 1, S.envH, PT_WRAP_CLAMP_TO_EDGE, false);
