@@ -625,4 +625,66 @@ int orc_tonemap_curve(int fn, uint64_t n, const float* in, int in_stride, float*
 #define PROBE_CLAMP gclamp
 #include "probe_rows.h"  // orc_shading_probe: the probes above over arrays of states
 
+// A hit turned into the State every BSDF call reads: GetShadeState + the lines of PathTrace between it and the debug modes + GetMaterialsAndTextures, on the
+// scene the context holds.  Row layout of vk_raytrace_amd/csrc/pt_probe.h surface_probe (kind 0, SURF_STATE; the `path` word is the product's business and
+// ignored, the line-path word is left alone): in instance primitive bu bv rayDir[3] path, out 17 words after GetShadeState, 50 after the resolve, the material
+// index.  Rows whose instance or primitive the scene does not have are left as the caller filled them.  Kind 1 (the product's shading lines): 1, no such data.
+int orc_surface_probe(orc_ctx* c, int kind, uint64_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  if(kind == 1)
+    return 1;
+  if(kind != 0 || in_stride < 8 || out_stride < 69)
+    return -1;
+  const Scene& sc = c->scene;
+  pt_RtxState  st{};
+  Tracer       tr(sc, st, c->variant);
+  auto put3 = [](float* o, vec3 v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; };
+  auto bits = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
+  for(uint64_t i = 0; i < n; ++i)
+  {
+    const float* r = in + i * (uint64_t)in_stride;
+    float*       o = out + i * (uint64_t)out_stride;
+    uint32_t     inst, prim;
+    std::memcpy(&inst, r, 4);
+    std::memcpy(&prim, r + 1, 4);
+    if(inst >= sc.nodes.size() || prim >= sc.primMeshes[sc.nodes[inst].primMesh].indexCount / 3)
+      continue;
+    PtPayload& prd          = tr.prd;
+    prd.instanceID          = (int)inst;
+    prd.instanceCustomIndex = sc.nodes[inst].primMesh;
+    prd.primitiveID         = (int)prim;
+    prd.baryCoord           = vec2(r[2], r[3]);
+    prd.objectToWorld       = sc.objectToWorld[inst];
+    prd.worldToObject       = sc.worldToObject[inst];
+    const Ray ray{vec3(0), vec3(r[4], r[5], r[6])};
+
+    ShadeState sstate = tr.GetShadeState(prd);
+    put3(o, sstate.position); put3(o + 3, sstate.normal); put3(o + 6, sstate.tangent_u); put3(o + 9, sstate.tangent_v);
+    o[12] = sstate.text_coords.x; o[13] = sstate.text_coords.y; put3(o + 14, sstate.color);
+    State state;  // pathtrace.glsl:228-245, as PathTrace has them
+    state.position       = sstate.position;
+    state.normal         = sstate.normal;
+    state.tangent        = sstate.tangent_u;
+    state.bitangent      = sstate.tangent_v;
+    state.texCoord       = sstate.text_coords;
+    state.matID          = sstate.matIndex;
+    state.isEmitter      = false;
+    state.specularBounce = false;
+    state.isSubsurface   = false;
+    state.ffnormal       = dot(state.normal, ray.direction) <= 0.0f ? state.normal : -state.normal;
+    tr.GetMaterialsAndTextures(state, ray);
+    state.mat.albedo *= sstate.color;
+
+    float*          q = o + 17;
+    const Material& a = state.mat;
+    put3(q, state.position); put3(q + 3, state.normal); put3(q + 6, state.ffnormal); put3(q + 9, state.tangent); put3(q + 12, state.bitangent);
+    q[15] = state.texCoord.x; q[16] = state.texCoord.y; put3(q + 17, a.albedo); put3(q + 20, a.emission); put3(q + 23, a.f0);
+    q[26] = a.metallic; q[27] = a.roughness; q[28] = a.ax; q[29] = a.ay; q[30] = a.anisotropy; q[31] = a.clearcoat; q[32] = a.clearcoatRoughness;
+    q[33] = a.transmission; q[34] = a.ior; q[35] = state.eta; put3(q + 36, a.attenuationColor); q[39] = a.attenuationDistance; q[40] = a.alpha;
+    q[41] = a.sheen; put3(q + 42, a.sheenTint); q[45] = a.specular; q[46] = a.specularTint; q[47] = a.subsurface;
+    q[48] = bits(a.unlit ? 1u : 0u); q[49] = bits(a.thinwalled ? 1u : 0u); q[50] = bits((uint32_t)state.matID);
+  }
+  return 0;
+}
+
 }  // extern "C"

@@ -32,6 +32,7 @@ using namespace glslc;
 using namespace glslc::refcomp;
 
 extern "C" {
+void ref_surface_bind(const pt_SceneDesc* d);  // (below, with ref_surface_probe)
 
 // Descriptor sets 0, 2, 3 (shaders/layouts.glsl:37-50).  Every pointer is borrowed; the caller keeps the arrays alive.
 int ref_bind(const pt_SceneDesc* d, const pt_EnvAccel* envAccel, int envW, int envH, const RefHooks* hooks)
@@ -61,6 +62,7 @@ int ref_bind(const pt_SceneDesc* d, const pt_EnvAccel* envAccel, int envW, int e
   environmentTexture.w    = envW;
   environmentTexture.h    = envH;
   envSamplingData         = reinterpret_cast<const EnvAccel*>(envAccel);
+  ref_surface_bind(d);
   return 0;
 }
 int ref_set_camera(const pt_SceneCamera* c)
@@ -265,6 +267,84 @@ void ref_sun_disk_sample(const float* r, float* out)
   out[0] = l.x; out[1] = l.y; out[2] = l.z; out[3] = l.w;
   std::memcpy(out + 4, &prd.seed, 4);
   _sunAndSky = keep;
+}
+// A hit turned into the State every BSDF call reads, by the reference's own GetShadeState (shade_state.glsl:63-145) and GetMaterialsAndTextures
+// (gltf_material.glsl:104-193) on the bound scene, with the lines of PathTrace between them (pathtrace.glsl:234-248) and the payload's matrices taken through
+// the instance hook.  Row layout of the product's surface probe (kind 0; see oracle/pt_oracle.cpp orc_surface_probe).  numNodes / numPrimMeshes bound the rows.
+static uint32_t s_numNodes = 0;
+static std::vector<uint32_t> s_primTris;
+static std::vector<int>      s_nodeMesh;
+void ref_surface_bind(const pt_SceneDesc* d)
+{
+  s_numNodes = d->numNodes;
+  s_primTris.resize(d->numPrimMeshes);
+  for(uint32_t i = 0; i < d->numPrimMeshes; ++i)
+    s_primTris[i] = d->primMeshes[i].indexCount / 3;
+  s_nodeMesh.resize(d->numNodes);
+  for(uint32_t i = 0; i < d->numNodes; ++i)
+    s_nodeMesh[i] = d->nodes[i].primMesh;
+}
+int ref_surface_probe(int kind, uint64_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  if(kind == 1)
+    return 1;
+  if(kind != 0 || in_stride < 8 || out_stride < 69)
+    return -1;
+  auto put3 = [](float* o, vec3 v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; };
+  auto bits = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
+  for(uint64_t i = 0; i < n; ++i)
+  {
+    const float* r = in + i * (uint64_t)in_stride;
+    float*       o = out + i * (uint64_t)out_stride;
+    uint32_t     inst, prim;
+    std::memcpy(&inst, r, 4);
+    std::memcpy(&prim, r + 1, 4);
+    if(inst >= s_numNodes || s_nodeMesh[inst] < 0 || uint32_t(s_nodeMesh[inst]) >= s_primTris.size() || prim >= s_primTris[s_nodeMesh[inst]])
+      continue;
+    float a[12], b[12];
+    g_hooks.instance(g_hooks.user, (int)inst, a, b);
+    PtPayload hstate;
+    hstate.seed = 0; hstate.hitT = 1.0f;
+    hstate.primitiveID         = (int)prim;
+    hstate.instanceID          = (int)inst;
+    hstate.instanceCustomIndex = s_nodeMesh[inst];
+    hstate.baryCoord           = vec2(r[2], r[3]);
+    for(int k = 0; k < 4; ++k)
+    {
+      hstate.objectToWorld.c[k] = vec3(a[3 * k], a[3 * k + 1], a[3 * k + 2]);
+      hstate.worldToObject.c[k] = vec3(b[3 * k], b[3 * k + 1], b[3 * k + 2]);
+    }
+    Ray ray;
+    ray.origin    = vec3(0);
+    ray.direction = vec3(r[4], r[5], r[6]);
+
+    ShadeState sstate = GetShadeState(hstate);
+    put3(o, sstate.position); put3(o + 3, sstate.normal); put3(o + 6, sstate.tangent_u[0]); put3(o + 9, sstate.tangent_v[0]);
+    o[12] = sstate.text_coords[0].x; o[13] = sstate.text_coords[0].y; put3(o + 14, sstate.color);
+    State state;
+    state.position       = sstate.position;
+    state.normal         = sstate.normal;
+    state.tangent        = sstate.tangent_u[0];
+    state.bitangent      = sstate.tangent_v[0];
+    state.texCoord       = sstate.text_coords[0];
+    state.matID          = sstate.matIndex;
+    state.isEmitter      = false;
+    state.specularBounce = false;
+    state.isSubsurface   = false;
+    state.ffnormal       = dot(state.normal, ray.direction) <= 0.0f ? state.normal : -state.normal;
+    GetMaterialsAndTextures(state, ray);
+    state.mat.albedo *= sstate.color;
+
+    float*          q = o + 17;
+    const Material& m = state.mat;
+    put3(q, state.position); put3(q + 3, state.normal); put3(q + 6, state.ffnormal); put3(q + 9, state.tangent); put3(q + 12, state.bitangent);
+    q[15] = state.texCoord.x; q[16] = state.texCoord.y; put3(q + 17, m.albedo); put3(q + 20, m.emission); put3(q + 23, m.f0);
+    q[26] = m.metallic; q[27] = m.roughness; q[28] = m.ax; q[29] = m.ay; q[30] = m.anisotropy; q[31] = m.clearcoat; q[32] = m.clearcoatRoughness;
+    q[33] = m.transmission; q[34] = m.ior; q[35] = state.eta; put3(q + 36, m.attenuationColor); q[39] = m.attenuationDistance; q[40] = m.alpha;
+    q[41] = m.sheen; put3(q + 42, m.sheenTint); q[45] = m.specular; q[46] = m.specularTint; q[47] = m.subsurface;
+    q[48] = bits(m.unlit ? 1u : 0u); q[49] = bits(m.thinwalled ? 1u : 0u); q[50] = bits((uint32_t)state.matID);
+  }
+  return 0;
 }
 #define PROBE_MUL_POINT(m, p) ((m) * vec4(p, 1.0f))
 #define PROBE_MUL_ROWVEC(p, m) vec3((p) * (m))

@@ -1368,6 +1368,24 @@ int th_texture_probe(void* p, int kind, uint64_t n, const float* in, int in_stri
     texture_probe(s->dsFlat, lim, kind, in + size_t(i) * in_stride, out + size_t(i) * out_stride);
   return 0;
 }
+// ---- a hit turned into a Surface (pt_probe.h surface_probe) on a scene made by th_create_scene: its instance records, packed vertices, indices, materials,
+// material lines and pool.  The device runs the same function per lane (pt_debug_surface_probe).  Returns SURF_NO_DATA (1) for SURF_SLOT: the host build keeps
+// no per-slot shading lines.
+int th_surface_probe(void* p, int kind, uint64_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  Scene* s = static_cast<Scene*>(p);
+  if(!s || kind < 0 || kind >= SURF_COUNT || in_stride < SURF_IN || out_stride < SURF_OUT)
+    return -1;
+  if(kind == SURF_SLOT && s->dsFlat.shadeTris == nullptr)
+    return SURF_NO_DATA;
+  const size_t          mats = s->materials.size() < s->matLines.size() / PT_MAT_LINE_QUADS ? s->materials.size() : s->matLines.size() / PT_MAT_LINE_QUADS;
+  const SurfProbeLimits lim{uint32_t(s->inst.size()), uint32_t(s->indices.size()), uint32_t(s->vertices.size() / 2), uint32_t(mats), uint32_t(s->texRecs.size()),
+                            uint32_t(s->texels.size()), 0u};
+#pragma omp parallel for schedule(static)
+  for(long long i = 0; i < (long long)n; ++i)
+    (void)surface_probe(s->dsFlat, lim, kind, in + size_t(i) * in_stride, out + size_t(i) * out_stride);
+  return 0;
+}
 // the scene's texture records (TexRec, 32 B each), material lines (PT_MAT_LINE_QUADS x 16 B per material), alpha view (AlphaMat, 80 B each), opacity maps
 // and texel pool as th_create_scene fetched them; null outputs: the counts only (records, materials, map words, pool texels)
 void th_texture_records(void* p, unsigned long long* counts4, void* texRecsOut, void* matLinesOut, void* alphaMatsOut, uint32_t* alphaMapsOut, uint32_t* texelsOut)

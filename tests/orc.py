@@ -69,6 +69,8 @@ def lib():
         L.orc_trace_closest.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 7
         for fn in (L.orc_shading_probe, L.orc_glsl_builtin, L.orc_tonemap_curve):  # (fn, n, in, in_stride, out, out_stride): oracle/probe_rows.h
             fn.restype, fn.argtypes = C.c_int, [C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        # (ctx, kind, n, in, in_stride, out, out_stride): a hit turned into a State on the context's scene, rows of csrc/pt_probe.h surface_probe; 1: no such data
+        L.orc_surface_probe.restype, L.orc_surface_probe.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     return _lib
 
 
@@ -181,6 +183,11 @@ class Oracle:
 
     def reset_stats(self):
         self.L.orc_reset_stats(self.ctx)
+
+    def surface_probe(self, kind, rows, out):
+        """rows (n, >= 8) float32 -> out (n, >= 69) float32 in place (oracle/pt_oracle.cpp orc_surface_probe); returns the call's code"""
+        assert rows.dtype == np.float32 and out.dtype == np.float32 and rows.flags.c_contiguous and out.flags.c_contiguous
+        return self.L.orc_surface_probe(self.ctx, int(kind), len(rows), rows.ctypes.data, rows.shape[1], out.ctypes.data, out.shape[1])
 
     def trace_closest(self, org, dirs, seeds=None):
         n = len(org)

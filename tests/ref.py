@@ -81,6 +81,8 @@ def lib():
         for fn in (L.ref_shading_probe, L.ref_glsl_builtin, L.ref_tonemap_curve):  # (fn, n, in, in_stride, out, out_stride): oracle/probe_rows.h
             fn.restype, fn.argtypes = C.c_int, [C.c_int, C.c_uint64, P, C.c_int, P, C.c_int]
         L.ref_env_sample_uv.argtypes = [C.c_uint64, P, C.c_int, P, P]
+        # (kind, n, in, in_stride, out, out_stride): the reference's GetShadeState + GetMaterialsAndTextures on the bound scene, rows of csrc/pt_probe.h surface_probe
+        L.ref_surface_probe.restype, L.ref_surface_probe.argtypes = C.c_int, [C.c_int, C.c_uint64, P, C.c_int, P, C.c_int]
         _lib = L
     return _lib
 
@@ -132,6 +134,11 @@ class Reference:
                                                                                     0 if ids is None else len(ids), threads)
         return accum
 
+
+    def surface_probe(self, kind, rows, out):
+        """rows (n, >= 8) float32 -> out (n, >= 69) float32 in place (oracle/ref_glue/ref_comp.cpp ref_surface_probe); returns the call's code"""
+        assert not self.rtx and rows.dtype == np.float32 and out.dtype == np.float32 and rows.flags.c_contiguous and out.flags.c_contiguous
+        return self.L.ref_surface_probe(int(kind), len(rows), rows.ctypes.data, rows.shape[1], out.ctypes.data, out.shape[1])
 
     def render_frames(self, state, first_frame, nframes, accum, pixel_ids, threads=0):
         """pathtrace.comp for `nframes` consecutive frames of the listed pixels inside one OpenMP team (bench.py's cpu_baseline leg)."""

@@ -2310,6 +2310,57 @@ extern "C" __attribute__((visibility("default"))) int pt_debug_texture_probe(pt_
     return done(c->fail(PT_ERR_HIP, "pt_debug_texture_probe: kernel failed"));
   return done(PT_OK);
 }
+// A hit turned into a Surface on the device (pt_probe.h surface_probe), on the scene the context holds: one row per lane.  tests/test_surface_model.py holds the
+// result bit for bit to the host build of the same function (tests/cpp/trace_host.cpp th_surface_probe) and reads the per-slot shading lines through it.
+// Returns SURF_NO_DATA (1, no error) for SURF_SLOT when the scene has no shading lines.  Not part of the ABI.
+__global__ void k_surface_probe(DeviceScene S, SurfProbeLimits lim, int kind, uint32_t n, const float* __restrict__ in, int inStride, float* __restrict__ out, int outStride)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  float row[SURF_IN], res[SURF_OUT];
+  for(int k = 0; k < SURF_IN; ++k)
+    row[k] = in[size_t(i) * inStride + k];
+  for(int k = 0; k < SURF_OUT; ++k)
+    res[k] = out[size_t(i) * outStride + k];
+  (void)surface_probe(S, lim, kind, row, res);
+  for(int k = 0; k < SURF_OUT; ++k)
+    out[size_t(i) * outStride + k] = res[k];
+}
+extern "C" __attribute__((visibility("default"))) int pt_debug_surface_probe(pt_context* c, int kind, uint32_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  CTX_CHECK(c);
+  if(kind < 0 || kind >= SURF_COUNT || !in || !out || in_stride < SURF_IN || out_stride < SURF_OUT || n > (1u << 24))
+    return c->fail(PT_ERR_INVALID, "pt_debug_surface_probe: bad arguments");
+  if(!c->haveScene)
+    return c->fail(PT_ERR_STATE, "pt_debug_surface_probe before pt_set_scene");
+  if(n == 0)
+    return PT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_all(c));
+  if(kind == SURF_SLOT && c->scene.shadeTris == nullptr)
+    return SURF_NO_DATA;
+  // what the device arrays are known to hold (an allocation is at least as large as its last upload)
+  const size_t mats = std::min(c->dMatLines.bytes / (sizeof(uint4) * PT_MAT_LINE_QUADS), c->dMaterials.bytes / sizeof(pt_GltfShadeMaterial));
+  const size_t slots = c->scene.shadeTris ? std::min<size_t>(c->numTris, c->dShadeTris.bytes / (sizeof(float4) * PT_SHADE_REC_QUADS)) : 0;
+  const SurfProbeLimits lim{uint32_t(std::min<size_t>(c->numInstances, c->dInstances.bytes / sizeof(InstanceRec))), uint32_t(std::min<size_t>(c->dIndices.bytes / 4, 0xffffffffu)),
+                            uint32_t(std::min<size_t>(c->dVertices.bytes / 32, 0xffffffffu)), uint32_t(mats), uint32_t(c->dTexRecs.bytes / sizeof(TexRec)),
+                            uint32_t(std::min<size_t>(c->dTexels.bytes / 4, 0xffffffffu)), uint32_t(slots)};
+  float *dIn = nullptr, *dOut = nullptr;
+  auto   done = [&](int r) {
+    (void)hipFree(dIn); (void)hipFree(dOut);
+    return r;
+  };
+  const size_t inBytes = size_t(n) * in_stride * 4, outBytes = size_t(n) * out_stride * 4;
+  if(hipMalloc(&dIn, inBytes) != hipSuccess || hipMalloc(&dOut, outBytes) != hipSuccess)
+    return done(c->fail(PT_ERR_OOM, "pt_debug_surface_probe: out of device memory"));
+  if(hipMemcpy(dIn, in, inBytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dOut, out, outBytes, hipMemcpyHostToDevice) != hipSuccess)
+    return done(c->fail(PT_ERR_HIP, "pt_debug_surface_probe: upload failed"));
+  k_surface_probe<<<dim3((n + 63) / 64), dim3(64), 0, c->stream>>>(c->scene, lim, kind, n, dIn, in_stride, dOut, out_stride);
+  if(hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return done(c->fail(PT_ERR_HIP, "pt_debug_surface_probe: kernel failed"));
+  return done(PT_OK);
+}
 // The display pass enqueued on the context's stream, ending with the copy of the RGBA8 image to `out` (host memory; the caller synchronises).
 // readDone: recorded once the accumulation image has been read, and made the event the next frame's accumulate step waits for -- frames
 // rendered after this call may then overlap the rest of the pass.

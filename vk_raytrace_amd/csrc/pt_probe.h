@@ -2,7 +2,8 @@
 // functions shade_path calls -- bsdf_eval / bsdf_sample (disney_*, gltf_*), sun_and_sky, spherical_uv, make_frame, range / spot attenuation and the
 // GLSL built-ins of pt_math.h (mirror, bend, lerp, smooth).  No formula lives here.  pt_capi.hip wraps it in a kernel (k_shading_probe, one state
 // per lane); tests/cpp/trace_host.cpp compiles the same function for the host (th_shading_probe).  tests/test_float_kat.py holds both to an
-// independent float64 model and to each other, bit for bit.
+// independent float64 model and to each other, bit for bit.  Below it: texture_probe (the software texture path one call at a time, tests/test_texture_model.py)
+// and surface_probe (a hit turned into the Surface: fetch_triangle, surface_at_hit, resolve_material_at, and the per-slot shading lines; tests/test_surface_model.py).
 //
 // Row layouts (32-bit words; integers travel as bit patterns):
 //   PROBE_EVAL_DISNEY / PROBE_EVAL_GLTF      in  m[22] N[3] T[3] B[3] eta thin V[3] L[3] seed   (PROBE_BSDF_IN = 40; m = albedo3 specular anisotropy metallic roughness subsurface specularTint sheen sheenTint3 clearcoat clearcoatRoughness transmission ior ax ay f0_3)
@@ -283,4 +284,122 @@ PT_DEV void texture_probe(const DeviceScene& S, const TexProbeLimits& lim, int k
     }
     default: break;
   }
+}
+
+// ---- a hit turned into the Surface every BSDF call reads (tests/test_surface_model.py): fetch_triangle, surface_at_hit, the ffnormal line, resolve_material_at
+// and the vertex-colour line, on the instances / vertices / materials / pool of a scene that is loaded.  No formula lives here; pt_shade.h is left alone
+// (factoring its lines 257-267 into a function of their own is not worth a different pt_render.o), so the three glue lines between the calls are REPEATED
+// below, word for word.  Rows of SURF_IN words in, SURF_OUT words out (integers travel as bit patterns):
+//   SURF_STATE  in  instance primitive bu bv rayDir[3] path     path 0: what shade_path does (resolve_material_at); 1: the full material record, always
+//               out after surface_at_hit  position[3] normal[3] tangent[3] bitangent[3] uv[2] vcolor[3]                                  (words 0-16)
+//                   after the resolve     position[3] normal[3] ffnormal[3] tangent[3] bitangent[3] uv[2] albedo[3] (x vcolor) emission[3] f0[3] metallic
+//                                         roughness ax ay anisotropy clearcoat clearcoatRoughness transmission ior eta attenuationColor[3]
+//                                         attenuationDistance alpha sheen sheenTint[3] specular specularTint subsurface unlit thinwalled   (words 17-66)
+//                   material index used, 1 when the material came from its 128-byte line alone (MAT_SIMPLE)                              (words 67-68)
+//   SURF_SLOT   in  slot                                        out the six float4 of the slot's shading line (words 0-23), then instance primitive material 0
+//               surface_probe returns SURF_NO_DATA (and touches nothing) when the scene has no shading lines
+// A row is left alone (its output stays as the caller filled it) unless its instance, primitive, vertex indices, material, slot and every texture the material
+// names lie inside what the scene's arrays hold: a probe must not be able to read outside them.  A texture is inside when its whole image is (every tap of
+// tex_tap / sample_rgba8_rec lands in the image for every float coordinate, texel_coord), so no coordinate has to be known before the resolve runs.
+enum { SURF_STATE = 0, SURF_SLOT, SURF_COUNT };
+enum { SURF_IN = 8, SURF_OUT = 72, SURF_FRAME_WORDS = 17, SURF_WORDS = 69, SURF_OK = 0, SURF_NO_DATA = 1 };
+struct SurfProbeLimits {
+  uint32_t numInstances, numIndices, numVertices, numMaterials, numTexRecs, poolTexels, numSlots;  // what the scene's arrays hold
+};
+
+PT_DEV bool surfp_texture_inside(const TexRec& tr, const SurfProbeLimits& lim)
+{
+  if(tr.w < 1 || tr.h < 1 || tr.w > 65535 || tr.h > 65535)
+    return false;
+  return uint64_t(tr.offset) + uint64_t(tr.w) * uint64_t(tr.h) * tex_layers(tr) <= uint64_t(lim.poolTexels);
+}
+PT_DEV bool surfp_material_inside(const DeviceScene& S, const SurfProbeLimits& lim, int m)
+{
+  if(m < 0 || uint32_t(m) >= lim.numMaterials)
+    return false;
+  const uint4*   line  = S.matLines + size_t(m) * PT_MAT_LINE_QUADS;
+  const uint32_t flags = line[2].w;
+  const uint32_t has[4] = {MAT_HAS_NORMAL, MAT_HAS_EMISSIVE, MAT_HAS_MR, MAT_HAS_BASE};
+  const pt_GltfShadeMaterial& r = S.materials[m];
+  const int      ids[4] = {r.normalTexture, r.emissiveTexture, r.pbrMetallicRoughnessTexture, r.pbrBaseColorTexture};
+  for(int k = 0; k < 4; ++k)
+  {
+    if(((flags & has[k]) != 0) != (ids[k] > -1))  // line and record name the same textures
+      return false;
+    if((flags & has[k]) && !surfp_texture_inside(tex_desc_unpack(line[3 + k]), lim))
+      return false;
+  }
+  const int more[3] = {r.transmissionTexture, r.clearcoatTexture, r.clearcoatRoughnessTexture};
+  for(int k = 0; k < 3; ++k)
+    if(more[k] > -1 && (uint32_t(more[k]) >= lim.numTexRecs || !surfp_texture_inside(S.texRecs[more[k]], lim)))
+      return false;
+  return true;
+}
+PT_DEV void surfp_put2(float* o, f2 v) { o[0] = v.x; o[1] = v.y; }
+
+PT_DEV int surface_probe(const DeviceScene& S, const SurfProbeLimits& lim, int kind, const float* in, float* out)
+{
+  if(kind == SURF_SLOT)
+  {
+    if(S.shadeTris == nullptr)
+      return SURF_NO_DATA;
+    const uint32_t slot = __float_as_uint(in[0]);
+    if(slot >= lim.numSlots)
+      return SURF_OK;
+    const VertexTriple v = fetch_triangle_slot(S, slot);
+    const float4       q[7] = {v.a0, v.b0, v.a1, v.b1, v.a2, v.b2, S.shadeTris[size_t(slot) * PT_SHADE_REC_QUADS + 6]};
+    for(int k = 0; k < 7; ++k)
+    {
+      out[4 * k] = q[k].x; out[4 * k + 1] = q[k].y; out[4 * k + 2] = q[k].z; out[4 * k + 3] = q[k].w;
+    }
+    return SURF_OK;
+  }
+  if(kind != SURF_STATE)
+    return SURF_OK;
+  const uint32_t hitInst = __float_as_uint(in[0]), hitPrim = __float_as_uint(in[1]), path = __float_as_uint(in[7]);
+  if(hitInst >= lim.numInstances || path > 1u)
+    return SURF_OK;
+  const InstanceRec& I = S.instances[hitInst];
+  if(hitPrim >= I.triCount || uint64_t(I.firstIndex) + 3ull * hitPrim + 3ull > uint64_t(lim.numIndices))
+    return SURF_OK;
+  for(int k = 0; k < 3; ++k)
+    if(uint64_t(I.vertexOffset) + uint64_t(S.indices[I.firstIndex + 3 * size_t(hitPrim) + k]) >= uint64_t(lim.numVertices))
+      return SURF_OK;
+  const int matIndex = I.materialIndex;
+  const int useMat   = matIndex < 0 ? 0 : matIndex;
+  if(!surfp_material_inside(S, lim, useMat))
+    return SURF_OK;
+  const f3 rdir = probe_f3(in + 4);
+
+  Surface            sf;
+  f3                 vcolor;
+  const VertexTriple vt = fetch_triangle(S, I, hitPrim);
+  surface_at_hit(S, I, vt, in[2], in[3], sf, vcolor);
+  probe_put(out, sf.position); probe_put(out + 3, sf.normal); probe_put(out + 6, sf.tangent); probe_put(out + 9, sf.bitangent);
+  surfp_put2(out + 12, sf.uv); probe_put(out + 14, vcolor);
+  // pt_shade.h:264-267, repeated
+  sf.ffnormal = dot3(sf.normal, rdir) <= 0.0f ? sf.normal : -sf.normal;
+  bool line   = false;
+  if(path == 0u)
+  {
+    line = (S.matLines[size_t(useMat) * PT_MAT_LINE_QUADS + 2].w & MAT_SIMPLE) != 0;
+    resolve_material_at(S, matIndex < 0 ? 0 : matIndex, rdir, sf);
+  }
+  else
+  {
+    const uint4* l     = S.matLines + size_t(useMat) * PT_MAT_LINE_QUADS;
+    const uint4  md[4] = {l[3], l[4], l[5], l[6]};
+    resolve_material(S, S.materials[useMat], md, rdir, sf);
+  }
+  sf.albedo *= vcolor;
+
+  float* o = out + SURF_FRAME_WORDS;
+  probe_put(o, sf.position); probe_put(o + 3, sf.normal); probe_put(o + 6, sf.ffnormal); probe_put(o + 9, sf.tangent); probe_put(o + 12, sf.bitangent);
+  surfp_put2(o + 15, sf.uv); probe_put(o + 17, sf.albedo); probe_put(o + 20, sf.emission); probe_put(o + 23, sf.f0);
+  o[26] = sf.metallic; o[27] = sf.roughness; o[28] = sf.ax; o[29] = sf.ay; o[30] = sf.anisotropy; o[31] = sf.clearcoat; o[32] = sf.clearcoatRoughness;
+  o[33] = sf.transmission; o[34] = sf.ior; o[35] = sf.eta; probe_put(o + 36, sf.attenuationColor); o[39] = sf.attenuationDistance; o[40] = sf.alpha;
+  o[41] = sf.sheen; probe_put(o + 42, sf.sheenTint); o[45] = sf.specular; o[46] = sf.specularTint; o[47] = sf.subsurface;
+  o[48] = __uint_as_float(sf.unlit ? 1u : 0u); o[49] = __uint_as_float(sf.thinwalled ? 1u : 0u);
+  o[50] = __uint_as_float(uint32_t(useMat)); o[51] = __uint_as_float(line ? 1u : 0u);
+  return SURF_OK;
 }
