@@ -4,7 +4,7 @@
 // inline C++ apart from a handful of intrinsics, so it is compiled here for the host (g++, -ffp-contract=off like the device build) and run
 // against a brute-force loop over every world triangle with the same tri_test.  What the GPU parity tests can only show through images is
 // checked ray by ray without a GPU: the flat walk and the two-level walk (TLAS + object-space BLASes, per-instance box padding from
-// pt_capi.hip's two_level_pad) must report exactly the candidates brute force reports -- every candidate along the ray, in key order.
+// pt_scene_records.cpp's two_level_pad) must report exactly the candidates brute force reports -- every candidate along the ray, in key order.
 //
 // The acceleration structures are assembled on the host in the product's formats (TriRec, WideNode, TlasLeaf).  Topology comes from the
 // product's device builder run through its host emulation (pt_debug_sahdev_topology in libptmi.so); boxes, the 4-wide collapse, the vertex
@@ -183,7 +183,7 @@ static inline bool th_tri_test_certified(const TriRec& tr, uint32_t flags, f3 o,
 #include "pt_shade.h"  // pt_settle.h (pt_trace.h + the per-ray settle functions k_tail runs) + the shading steps of a path (generate_ray, shade_path, ...)
 #include "pt_machine.h"  // the resumable per-lane traversal of the persistent kernels (k_closest_p / k_shadow_p)
 #include "pt_cnode.h"    // WideNode -> CompactNode (what pt_accel.hip k_compact_nodes runs per node)
-#include "pt_probe.h"    // shading_probe: one call of a shading function per state (what pt_capi.hip k_shading_probe runs per lane)
+#include "pt_probe.h"    // shading_probe: one call of a shading function per state (what pt_debug.hip k_shading_probe runs per lane)
 #include "../../include/pt_types.h"
 
 extern "C" int pt_debug_sahdev_topology(uint32_t n, const float* tri9, uint32_t* vals, uint32_t* childL, uint32_t* childR, uint32_t* parI, uint32_t* parL);
@@ -376,7 +376,7 @@ struct Scene {
   Bvh                      tlas;
   std::vector<TlasLeaf>    tlasLeaves;
   std::vector<AlphaRec>    flatAlpha;
-  std::vector<uint32_t>    instBlock;  // DeviceScene::instBlock (pt_capi.hip build_tlas)
+  std::vector<uint32_t>    instBlock;  // DeviceScene::instBlock (pt_capi_accel.hip build_tlas)
   std::vector<CompactNode> blasCNodes, tlasCNodes;  // ... and the two-level structure's
   std::vector<CompactNode> flatCNodes;  // PT_TUNE cnodes=1: the flat structure's nodes in the compact form (read by lane_inner only)
   AlphaMat                 alphaMat;
@@ -457,7 +457,7 @@ static void build_structures(Scene* s, const std::vector<float>& padC0, const st
   s->flatAlpha.assign(std::max<size_t>(1, s->flat.tris.size()), AlphaRec{});
   for(size_t i = 0; i < s->flat.tris.size(); ++i)
     s->flatAlpha[i] = alpha_record(*s, s->inst[__float_as_uint(s->flat.tris[i].e1n.w)], __float_as_uint(s->flat.tris[i].e2p.w));
-  // ---- two-level: the prim-meshes instantiated once share one world-space structure at slot 0 / node 0 (pt_capi.hip build_merged /
+  // ---- two-level: the prim-meshes instantiated once share one world-space structure at slot 0 / node 0 (pt_capi_accel.hip build_merged /
   // pt_accel.hip pt_merged_build) ...
   std::vector<char> isMerged(numInst, 0);
   bool              haveMerged = false;
@@ -496,7 +496,7 @@ static void build_structures(Scene* s, const std::vector<float>& padC0, const st
         s->blasWide.push_back(w);  // slot base and node base are 0: the references are already global
     }
   }
-  // ... and one object-space BLAS per other prim-mesh that is instantiated (pt_capi.hip build_two_level / pt_accel.hip pt_blas_build)
+  // ... and one object-space BLAS per other prim-mesh that is instantiated (pt_capi_accel.hip build_two_level / pt_accel.hip pt_blas_build)
   std::vector<int64_t> nodeBaseOf(numPrimMeshes, -1);
   for(uint32_t i = 0; i < numInst; ++i)
   {
@@ -750,7 +750,7 @@ void* th_create(const float* vertices8, uint32_t numVerts, const uint32_t* indic
 }
 
 // a full scene description (materials, textures): instance records, flags, alpha view, opacity maps and texel pool are the PRODUCT's
-// (pt_capi.hip build_scene_records through pt_debug_scene_records), so the any-hit evaluation reads exactly what the GPU reads
+// (pt_scene_records.cpp build_scene_records through pt_debug_scene_records), so the any-hit evaluation reads exactly what the GPU reads
 void* th_create_scene(const pt_SceneDesc* d, char* err, size_t errLen)
 {
   unsigned long long counts[5] = {0, 0, 0, 0, 0};

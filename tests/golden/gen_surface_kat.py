@@ -12,7 +12,7 @@ numpy only, written from the shader text
     common.glsl:80-92                  CreateCoordinateSystem
 and evaluated twice, in float64 (the fixture's answer) and in float32 (decides, with the float64 one, which rows are KEPT).  Texture values come from the
 numpy sampler model of gen_tex_kat.py (its address modes and its blend), not from any leg.  The inverse world matrix is computed in float64 from the
-float32 matrix and rounded to float32, as pt_capi.hip set_instance_transform and orc_scene.h build_world both do; it is an INPUT of both evaluations.
+float32 matrix and rounded to float32, as pt_scene_records.cpp set_instance_transform and orc_scene.h build_world both do; it is an INPUT of both evaluations.
 
 The scene is the smallest that reaches every line: five pieces of geometry of four triangles each (every vertex its own normal, tangent, handedness bit,
 uv with the LSB of v set, colour; two triangles of a piece wound against their normals), the fourth holding the named edge cases, the fifth texture coordinates of

@@ -42,7 +42,7 @@ against it; x = worst error / bound):
 and on the product's side, host build only:
   tex_index, tile row and tile column swapped (pt_device.h)        SAMPLE_REC, SAMPLE_DESC, tap footprint, storage orders, extreme sizes (65528 x 4 is no
                                                                     bijection), opacity (the map changed the class of an opacity)
-  opacity apron removed (pt_capi.hip build_opacity_maps, k = 0..3) opacity: the five blocks with one texel of 0 in their apron are classified ONE
+  opacity apron removed (pt_scene_records.cpp build_opacity_maps, k = 0..3) opacity: the five blocks with one texel of 0 in their apron are classified ONE
 """
 import ctypes as C
 

@@ -278,7 +278,7 @@ def test_degenerate_inputs():
 # ---- stochastic alpha: the product's two-pass settle functions against the contract's key-ordered loop -------------------------------------
 class TracedScene(Traced):
     """a full scene description (materials, textures): instance flags, alpha view, opacity maps and texel pool come from the product's own
-    host code (pt_capi.hip build_scene_records)"""
+    host code (pt_scene_records.cpp build_scene_records)"""
 
     def __init__(self, scene: Scene):
         self.L = harness()

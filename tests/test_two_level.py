@@ -1,7 +1,7 @@
 """Two-level acceleration structure (PT_ACCEL_TWO_LEVEL: one object-space BLAS per prim-mesh + a TLAS over the instances; reference:
 src/accelstruct.cpp:110-162) and instance updates (pt_update_instances: TLAS refit).
 
-CPU part: the object-space box padding of the walk (pt_capi.hip two_level_pad / pt_trace.h enter_instance) is held to a float32 emulation
+CPU part: the object-space box padding of the walk (pt_scene_records.cpp two_level_pad / pt_trace.h enter_instance) is held to a float32 emulation
 of the ray transform -- the padded box must contain the transformed ray's point for every hit the world-space triangle test can report.
 GPU part: frames, AOVs, counters and picks of the two-level mode are bit-identical to the oracle (the trace contract is BVH independent),
 before and after instance updates, under every launch policy.
@@ -393,7 +393,7 @@ def test_two_level_ray_picker(env_small):
 
 # ---- launch policy (host logic) -------------------------------------------------------------------------------------------------------------
 def test_tail_depth_follows_the_observed_queue_sizes():
-    """flush_pending's decision where the fused tail kernel takes over (pt_capi.hip tail_from_depth), on plain numbers: the first bounce
+    """flush_pending's decision where the fused tail kernel takes over (pt_scene_records.cpp tail_from_depth), on plain numbers: the first bounce
     whose expected queue is <= the threshold; observed alive fractions first, the last observed shrink factor beyond them, 0.3 per bounce
     before any feedback; never when the threshold is 0.  (Performance policy only: tests/test_gpu_parity.py holds every threshold to
     bit-identical images.)"""

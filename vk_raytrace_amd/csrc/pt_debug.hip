@@ -1,0 +1,268 @@
+// Device code that is not the product: the on-box calibration of the two rooflines (pt_measure_peaks), the fp32 transcendental contract evaluated
+// on the device (pt_fpmath_eval) and the probe kernels that run single functions of the render path row by row for the tests (pt_probe.h).
+#include <algorithm>
+#include "pt_context.h"
+#include "pt_probe.h"
+
+extern "C" {
+
+// ---- on-box calibration of the two rooflines bench.py prices against (no reference counterpart) ------------------------------------------
+// VALU issue: every lane runs 8 independent v_fmac_f32 chains (the form with the highest measured issue rate, tools/valu_peak.hip; inline asm: the
+// compiler can neither pack two of them into v_pk_fma_f32 nor drop them), 8 waves per SIMD on every CU; the result is wave-instructions per second over the whole chip.
+__global__ void __launch_bounds__(256) k_calib_valu(int iters, float* out)
+{
+  float a0 = threadIdx.x, a1 = a0 + 1.f, a2 = a0 + 2.f, a3 = a0 + 3.f, a4 = a0 + 4.f, a5 = a0 + 5.f, a6 = a0 + 6.f, a7 = a0 + 7.f;
+  const float m = 0.999f, c = 0.001f;
+  for(int i = 0; i < iters; ++i)
+  {
+    asm volatile("v_fmac_f32 %0, %8, %9\n v_fmac_f32 %1, %8, %9\n v_fmac_f32 %2, %8, %9\n v_fmac_f32 %3, %8, %9\n"
+                 "v_fmac_f32 %4, %8, %9\n v_fmac_f32 %5, %8, %9\n v_fmac_f32 %6, %8, %9\n v_fmac_f32 %7, %8, %9\n"
+                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)
+                 : "v"(m), "v"(c));
+  }
+  float s = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
+  if(s == 12345.678f)
+    out[0] = s;
+}
+// HBM streaming: float4 copy (read + write) and float4 read-only reduction over buffers far larger than the 256 MB Infinity Cache
+__global__ void __launch_bounds__(256) k_calib_copy(const float4* __restrict__ src, float4* __restrict__ dst, size_t n)
+{
+  for(size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x)
+    dst[i] = src[i];
+}
+__global__ void __launch_bounds__(256) k_calib_read(const float4* __restrict__ src, size_t n, float* out)
+{
+  float acc = 0.f;
+  for(size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x)
+  {
+    float4 v = src[i];
+    acc += (v.x + v.y) + (v.z + v.w);
+  }
+  if(acc == 12345.678f)
+    out[0] = acc;
+}
+int pt_measure_peaks(pt_context* c, pt_Peaks* out)
+{
+  CTX_CHECK(c);
+  if(!out)
+    return c->fail(PT_ERR_INVALID, "pt_measure_peaks: null");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_all(c));
+  hipDeviceProp_t prop;
+  HIP_TRY(c, hipGetDeviceProperties(&prop, c->device));
+  const int    cus = prop.multiProcessorCount;
+  const size_t n   = size_t(1) << 26;  // 2^26 float4 = 1 GiB per buffer
+  float4 *     a = nullptr, *b = nullptr;
+  float*       sink = nullptr;
+  hipEvent_t   e0 = nullptr, e1 = nullptr;
+  auto         done = [&](int rc) {
+    (void)hipFree(a); (void)hipFree(b); (void)hipFree(sink);
+    if(e0) (void)hipEventDestroy(e0);
+    if(e1) (void)hipEventDestroy(e1);
+    return rc;
+  };
+  if(hipMalloc(&a, n * 16) != hipSuccess || hipMalloc(&b, n * 16) != hipSuccess || hipMalloc(&sink, 64) != hipSuccess)
+    return done(c->fail(PT_ERR_OOM, "pt_measure_peaks: out of device memory"));
+  if(hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipMemsetAsync(a, 0, n * 16, c->stream) != hipSuccess)
+    return done(c->fail(PT_ERR_HIP, "pt_measure_peaks: setup failed"));
+  auto timed = [&](auto&& launch, int reps) -> double {
+    launch();  // warm-up
+    (void)hipEventRecord(e0, c->stream);
+    for(int i = 0; i < reps; ++i)
+      launch();
+    (void)hipEventRecord(e1, c->stream);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    return double(ms) * 1e-3 / reps;
+  };
+  const int      iters = 4096;
+  const unsigned blocks = unsigned(cus) * 8u;  // 8 blocks of 4 waves per CU = 8 waves per SIMD
+  double         t = timed([&] { k_calib_valu<<<blocks, 256, 0, c->stream>>>(iters, sink); }, 5);
+  out->valuWaveInstrPerSec = double(blocks) * 4.0 * double(iters) * 8.0 / t;
+  t = timed([&] { k_calib_copy<<<unsigned(cus) * 16u, 256, 0, c->stream>>>(a, b, n); }, 5);
+  out->hbmCopyBytesPerSec = 2.0 * double(n) * 16.0 / t;
+  t = timed([&] { k_calib_read<<<unsigned(cus) * 16u, 256, 0, c->stream>>>(a, n, sink); }, 5);
+  out->hbmReadBytesPerSec = double(n) * 16.0 / t;
+  out->computeUnits = cus;
+  out->clockMHz     = prop.clockRate / 1000;
+  if(hipGetLastError() != hipSuccess)
+    return done(c->fail(PT_ERR_HIP, "pt_measure_peaks: kernel failed"));
+  return done(PT_OK);
+}
+
+// The fp32 transcendental contract evaluated on the device (include/pt_fpmath.h); tests hold it bit for bit to the host evaluation.
+__global__ void k_fpmath(int fn, uint64_t n, const float* a, const float* b, float* out)
+{
+  uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  float x = a[i], y = b ? b[i] : 0.0f, r;
+  switch(fn)
+  {
+    case PT_FN_SIN: r = pt_sin(x); break;
+    case PT_FN_COS: r = pt_cos(x); break;
+    case PT_FN_TAN: r = pt_tan(x); break;
+    case PT_FN_ASIN: r = pt_asin(x); break;
+    case PT_FN_ACOS: r = pt_acos(x); break;
+    case PT_FN_ATAN2: r = pt_atan2(x, y); break;
+    case PT_FN_EXP: r = pt_exp(x); break;
+    case PT_FN_LOG: r = pt_log(x); break;
+    default: r = pt_pow(x, y); break;
+  }
+  out[i] = r;
+}
+int pt_fpmath_eval(pt_context* c, int fn, uint64_t n, const float* a, const float* b, float* out)
+{
+  CTX_CHECK(c);
+  if(fn < PT_FN_SIN || fn > PT_FN_POW || !a || !out || ((fn == PT_FN_ATAN2 || fn == PT_FN_POW) && !b))
+    return c->fail(PT_ERR_INVALID, "pt_fpmath_eval: bad arguments");
+  if(n == 0)
+    return PT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  float *dA = nullptr, *dB = nullptr, *dO = nullptr;
+  int    rc = PT_OK;
+  auto   done = [&](int r) {
+    (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dO);
+    return r;
+  };
+  if(hipMalloc(&dA, n * 4) != hipSuccess || hipMalloc(&dO, n * 4) != hipSuccess || (b && hipMalloc(&dB, n * 4) != hipSuccess))
+    return done(c->fail(PT_ERR_OOM, "pt_fpmath_eval: out of device memory"));
+  if(hipMemcpy(dA, a, n * 4, hipMemcpyHostToDevice) != hipSuccess || (b && hipMemcpy(dB, b, n * 4, hipMemcpyHostToDevice) != hipSuccess))
+    return done(c->fail(PT_ERR_HIP, "pt_fpmath_eval: upload failed"));
+  k_fpmath<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>(fn, n, dA, dB, dO);
+  if(hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, dO, n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return done(c->fail(PT_ERR_HIP, "pt_fpmath_eval: kernel failed"));
+  return done(rc);
+}
+
+}  // extern "C"
+
+// ---- row probes (test hooks, not part of the ABI): one function of the render path per lane, row i of `in` -> row i of `out` ------------------
+// The host side of a probe: `in` and `out` (n rows of in_stride / out_stride floats) go to the device -- `out` too, the kernels read it --,
+// launch(dIn, dOut) enqueues the kernel on the context's stream, and `out` comes back.  Errors carry the entry point's name.
+template <class Launch>
+static int run_rows(pt_context* c, const char* who, uint32_t n, const float* in, int in_stride, float* out, int out_stride, Launch&& launch)
+{
+  float *dIn = nullptr, *dOut = nullptr;
+  auto   done = [&](int r) {
+    (void)hipFree(dIn); (void)hipFree(dOut);
+    return r;
+  };
+  const size_t inBytes = size_t(n) * in_stride * 4, outBytes = size_t(n) * out_stride * 4;
+  if(hipMalloc(&dIn, inBytes) != hipSuccess || hipMalloc(&dOut, outBytes) != hipSuccess)
+    return done(c->fail(PT_ERR_OOM, "%s: out of device memory", who));
+  if(hipMemcpy(dIn, in, inBytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dOut, out, outBytes, hipMemcpyHostToDevice) != hipSuccess)
+    return done(c->fail(PT_ERR_HIP, "%s: upload failed", who));
+  launch(dIn, dOut);
+  if(hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return done(c->fail(PT_ERR_HIP, "%s: kernel failed", who));
+  return done(PT_OK);
+}
+// The shading functions one at a time on the device (pt_probe.h: the functions shade_path calls, no formula of its own): one state per lane, row i of
+// `in` -> row i of `out`.  tests/test_float_kat.py holds the result bit for bit to the host build of the same function (tests/cpp/trace_host.cpp).
+__global__ void k_shading_probe(int fn, uint32_t n, const float* __restrict__ in, int inStride, float* __restrict__ out, int outStride, int inWords, int outWords)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  float row[PROBE_BSDF_IN], res[8];
+  for(int k = 0; k < PROBE_BSDF_IN; ++k)
+    row[k] = k < inWords ? in[size_t(i) * inStride + k] : 0.0f;
+  for(int k = 0; k < 8; ++k)
+    res[k] = 0.0f;
+  shading_probe(fn, row, res);
+  for(int k = 0; k < outWords; ++k)
+    out[size_t(i) * outStride + k] = res[k];
+}
+extern "C" __attribute__((visibility("default"))) int pt_debug_shading_probe(pt_context* c, int fn, uint32_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  CTX_CHECK(c);
+  int inWords = 0, outWords = 0;
+  probe_row_words(fn, inWords, outWords);
+  if(inWords == 0 || inWords > PROBE_BSDF_IN || outWords > 8 || !in || !out || in_stride < inWords || out_stride < outWords || n > (1u << 24))
+    return c->fail(PT_ERR_INVALID, "pt_debug_shading_probe: bad arguments");
+  if(n == 0)
+    return PT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return run_rows(c, "pt_debug_shading_probe", n, in, in_stride, out, out_stride, [&](const float* dIn, float* dOut) {
+    k_shading_probe<<<dim3((n + 63) / 64), dim3(64), 0, c->stream>>>(fn, n, dIn, in_stride, dOut, out_stride, inWords, outWords);
+  });
+}
+// The software texture path one call at a time on the device (pt_probe.h texture_probe), on the scene the context holds: one row per lane.  tests/test_texture_model.py
+// holds the result bit for bit to the host build of the same function (tests/cpp/trace_host.cpp th_texture_probe); this is where the device's own index
+// arithmetic (tex_index's 24-bit multiply) is seen.  Not part of the ABI.
+__global__ void k_texture_probe(DeviceScene S, TexProbeLimits lim, int kind, uint32_t n, const float* __restrict__ in, int inStride, float* __restrict__ out, int outStride)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  float row[TEXP_IN], res[TEXP_OUT];
+  for(int k = 0; k < TEXP_IN; ++k)
+    row[k] = in[size_t(i) * inStride + k];
+  for(int k = 0; k < TEXP_OUT; ++k)
+    res[k] = out[size_t(i) * outStride + k];
+  texture_probe(S, lim, kind, row, res);
+  for(int k = 0; k < TEXP_OUT; ++k)
+    out[size_t(i) * outStride + k] = res[k];
+}
+extern "C" __attribute__((visibility("default"))) int pt_debug_texture_probe(pt_context* c, int kind, uint32_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  CTX_CHECK(c);
+  if(kind < 0 || kind >= TEXP_COUNT || !in || !out || in_stride < TEXP_IN || out_stride < TEXP_OUT || n > (1u << 24))
+    return c->fail(PT_ERR_INVALID, "pt_debug_texture_probe: bad arguments");
+  if(!c->haveScene)
+    return c->fail(PT_ERR_STATE, "pt_debug_texture_probe before pt_set_scene");
+  if(kind == TEXP_ENV && !c->haveEnv)
+    return c->fail(PT_ERR_STATE, "pt_debug_texture_probe: no environment");
+  if(n == 0)
+    return PT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_all(c));
+  // what the device arrays are known to hold (an allocation is at least as large as its last upload)
+  const size_t         mats = std::min(c->dMatLines.bytes / (sizeof(uint4) * PT_MAT_LINE_QUADS), std::min(c->dAlphaMats.bytes / sizeof(AlphaMat), c->dMaterials.bytes / sizeof(pt_GltfShadeMaterial)));
+  const TexProbeLimits lim{uint32_t(c->dTexRecs.bytes / sizeof(TexRec)), uint32_t(mats), uint32_t(std::min<size_t>(c->dTexels.bytes / 4, 0xffffffffu))};
+  return run_rows(c, "pt_debug_texture_probe", n, in, in_stride, out, out_stride, [&](const float* dIn, float* dOut) {
+    k_texture_probe<<<dim3((n + 63) / 64), dim3(64), 0, c->stream>>>(c->scene, lim, kind, n, dIn, in_stride, dOut, out_stride);
+  });
+}
+// A hit turned into a Surface on the device (pt_probe.h surface_probe), on the scene the context holds: one row per lane.  tests/test_surface_model.py holds the
+// result bit for bit to the host build of the same function (tests/cpp/trace_host.cpp th_surface_probe) and reads the per-slot shading lines through it.
+// Returns SURF_NO_DATA (1, no error) for SURF_SLOT when the scene has no shading lines.  Not part of the ABI.
+__global__ void k_surface_probe(DeviceScene S, SurfProbeLimits lim, int kind, uint32_t n, const float* __restrict__ in, int inStride, float* __restrict__ out, int outStride)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  float row[SURF_IN], res[SURF_OUT];
+  for(int k = 0; k < SURF_IN; ++k)
+    row[k] = in[size_t(i) * inStride + k];
+  for(int k = 0; k < SURF_OUT; ++k)
+    res[k] = out[size_t(i) * outStride + k];
+  (void)surface_probe(S, lim, kind, row, res);
+  for(int k = 0; k < SURF_OUT; ++k)
+    out[size_t(i) * outStride + k] = res[k];
+}
+extern "C" __attribute__((visibility("default"))) int pt_debug_surface_probe(pt_context* c, int kind, uint32_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  CTX_CHECK(c);
+  if(kind < 0 || kind >= SURF_COUNT || !in || !out || in_stride < SURF_IN || out_stride < SURF_OUT || n > (1u << 24))
+    return c->fail(PT_ERR_INVALID, "pt_debug_surface_probe: bad arguments");
+  if(!c->haveScene)
+    return c->fail(PT_ERR_STATE, "pt_debug_surface_probe before pt_set_scene");
+  if(n == 0)
+    return PT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_all(c));
+  if(kind == SURF_SLOT && c->scene.shadeTris == nullptr)
+    return SURF_NO_DATA;
+  // what the device arrays are known to hold (an allocation is at least as large as its last upload)
+  const size_t mats = std::min(c->dMatLines.bytes / (sizeof(uint4) * PT_MAT_LINE_QUADS), c->dMaterials.bytes / sizeof(pt_GltfShadeMaterial));
+  const size_t slots = c->scene.shadeTris ? std::min<size_t>(c->numTris, c->dShadeTris.bytes / (sizeof(float4) * PT_SHADE_REC_QUADS)) : 0;
+  const SurfProbeLimits lim{uint32_t(std::min<size_t>(c->numInstances, c->dInstances.bytes / sizeof(InstanceRec))), uint32_t(std::min<size_t>(c->dIndices.bytes / 4, 0xffffffffu)),
+                            uint32_t(std::min<size_t>(c->dVertices.bytes / 32, 0xffffffffu)), uint32_t(mats), uint32_t(c->dTexRecs.bytes / sizeof(TexRec)),
+                            uint32_t(std::min<size_t>(c->dTexels.bytes / 4, 0xffffffffu)), uint32_t(slots)};
+  return run_rows(c, "pt_debug_surface_probe", n, in, in_stride, out, out_stride, [&](const float* dIn, float* dOut) {
+    k_surface_probe<<<dim3((n + 63) / 64), dim3(64), 0, c->stream>>>(c->scene, lim, kind, n, dIn, in_stride, dOut, out_stride);
+  });
+}

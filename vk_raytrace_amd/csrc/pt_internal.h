@@ -161,7 +161,7 @@ struct RenderBuffersT {
 };
 typedef RenderBuffersT<PT_STATE_POLICY> RenderBuffers;
 void pt_sah_topology(uint32_t n, const struct TriRec* tris, uint32_t* vals, uint32_t* childL, uint32_t* childR, uint32_t* parI, uint32_t* parL);  // pt_sah.hip
-struct StageTimers;  // pt_capi.hip
+struct StageTimers;  // below; pt_capi.hip implements the pt_timers_* calls
 // waitBeforeAccum (may be null): accumDone event of the previous frame; recordAfterAccum: this frame's
 // A launch sequence as steps that each enqueue one stage on the sequence's stream (pt_render.hip plan_frame).  `accum`: the step that folds the
 // batch into the running mean -- it waits on the previous sequence's event, so sequences must issue their accum steps in order.

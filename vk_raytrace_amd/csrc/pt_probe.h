@@ -1,6 +1,6 @@
 // Per-function probe of the shading source (test infrastructure, not part of include/pt_api.h): one state in, one result out, through the very
 // functions shade_path calls -- bsdf_eval / bsdf_sample (disney_*, gltf_*), sun_and_sky, spherical_uv, make_frame, range / spot attenuation and the
-// GLSL built-ins of pt_math.h (mirror, bend, lerp, smooth).  No formula lives here.  pt_capi.hip wraps it in a kernel (k_shading_probe, one state
+// GLSL built-ins of pt_math.h (mirror, bend, lerp, smooth).  No formula lives here.  pt_debug.hip wraps it in a kernel (k_shading_probe, one state
 // per lane); tests/cpp/trace_host.cpp compiles the same function for the host (th_shading_probe).  tests/test_float_kat.py holds both to an
 // independent float64 model and to each other, bit for bit.  Below it: texture_probe (the software texture path one call at a time, tests/test_texture_model.py)
 // and surface_probe (a hit turned into the Surface: fetch_triangle, surface_at_hit, resolve_material_at, and the per-slot shading lines; tests/test_surface_model.py).

@@ -296,7 +296,7 @@ struct InstCtx {
 
 // Object-space ray constants of a ray entering the instance of TLAS leaf `tl`.  Transforming the ray rounds (o' and d' carry an absolute
 // error of a few 2^-24 x |worldToObject| x (|o| + |hit point|)); instead of tracking it per plane the BLAS boxes are grown by
-// eps = padC1 * max|o| + padC0 (host-computed bound with a 16x margin, pt_capi.hip: two_level_pad), folded into the per-ray constants:
+// eps = padC1 * max|o| + padC0 (host-computed bound with a 16x margin, pt_scene_records.cpp: two_level_pad), folded into the per-ray constants:
 // (plane -+ eps) * idir + n  =  plane * idir + (n -+ eps * |idir|).
 PT_DEV RayBox enter_instance(const DeviceScene& S, const TlasLeaf& tl, f3 o, f3 d)
 {
