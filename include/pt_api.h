@@ -178,6 +178,11 @@ int pt_tonemap_begin(pt_context* ctx, const pt_Tonemapper* tm, int disp_width, i
 int pt_tonemap_end(pt_context* ctx, uint8_t* rgba8_out);
 int pt_tonemap_pending(pt_context* ctx);
 
+/* Test access to the image the display pass samples: builds the offscreen image of a disp_width x disp_height viewport and its full mip chain exactly
+ * as pt_tonemap_zoom does with auto-exposure on, and copies level `level` (RGBA32F, row-major) to rgba32f_out, its extent to *width / *height (each may
+ * be NULL).  Returns the number of levels (>= 1), or a negative pt_Result. */
+int pt_debug_display_level(pt_context* ctx, int disp_width, int disp_height, int level, float* rgba32f_out, int* width, int* height);
+
 /* Device-side view of the local shard for the RCCL gather: pointer to [maxTilesPerRank][PT_TILE*PT_TILE][4]
  * floats (owned tiles first, in increasing global tile id; padding zero).  Waits for the frames rendered since the last synchronising
  * call and returns PT_ERR_STATE if they overflowed the traversal stack. */

@@ -261,6 +261,7 @@ static void blit_linear(const float* src, int sw, int sh, float* dst, int dw, in
 struct MipImage {
   std::vector<std::vector<float>> level;
   std::vector<int>                w, h;
+  int                             sel[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the level texture(inImage, uv, bias) reads for bias 0..7 (select_levels)
   // the sampler RenderOutput creates (render_output.cpp:98-100, a zeroed VkSamplerCreateInfo): NEAREST texel, NEAREST mip, REPEAT
   vec4 fetch(vec2 uv, int lod) const
   {
@@ -287,6 +288,17 @@ static void build_mips(MipImage& im, bool chain)
     im.h.push_back(nh);
   }
 }
+// texture(inImage, uvCoords * zoom, bias) of the full-screen pass, Vulkan "LOD Operation" and "Image Level(s) Selection": lambda_base = log2(zoom)
+// (uvCoords * zoom steps `zoom` texels of level 0 per pixel), lambda = clamp(lambda_base + bias, minLod = 0, maxLod = FLT_MAX), level = nearest(min(lambda, levels - 1)).
+static void select_levels(MipImage& im, float zoom)
+{
+  const float base = std::log2(zoom);
+  for(int i = 0; i < 8; ++i)
+    im.sel[i] = (int)std::fmin(std::floor(std::fmax(base + float(i), 0.0f) + 0.5f), float(im.level.size() - 1));
+}
+// float -> UNORM8, Vulkan "Conversion from Floating-Point to Normalized Fixed-Point": clamp to [0, 1], scale by 255, nearest integer; NaN stores 0 (the
+// comparisons pick 0 for it before the conversion to an integer, which is undefined for NaN).
+static inline uint8_t unorm8(float v) { return (uint8_t)std::floor((v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f) * 255.0f + 0.5f); }
 // level `lod` of the chain (test access)
 int orc_mip_chain(const float* rgba, int W, int H, int lod, float* out, int* outW, int* outH)
 {
@@ -316,6 +328,7 @@ int orc_tonemap_zoom(const pt_Tonemapper* tm, const float* accum, int w, int h, 
   for(int y = 0; y < h; ++y)
     std::memcpy(&im.level[0][size_t(y) * dispW * 4], accum + size_t(y) * w * 4, size_t(w) * 16);
   build_mips(im, (tm->autoExposure & 1) != 0);  // sample_example.cpp:423-427: the chain is only generated with auto-exposure on
+  select_levels(im, tm->zoom);
   auto luminance = [](vec3 c) { return dot(c, vec3(0.2126f, 0.7152f, 0.0722f)); };
 #pragma omp parallel for schedule(static)
   for(int y = 0; y < dispH; ++y)
@@ -324,7 +337,7 @@ int orc_tonemap_zoom(const pt_Tonemapper* tm, const float* accum, int w, int h, 
     {
       vec2 uvCoords((float(x) + 0.5f) / float(dispW), (float(y) + 0.5f) / float(dispH));  // passthrough.vert interpolated at the pixel centre
       vec2 uvz = uvCoords * tm->zoom;
-      vec4 hdr4 = im.fetch(uvz, 0);  // post.frag:101
+      vec4 hdr4 = im.fetch(uvz, im.sel[0]);  // post.frag:101 (no bias: the level of bias 0)
       vec3 hdr  = hdr4.xyz();
       if(((tm->autoExposure >> 0) & 1) == 1)
       {
@@ -343,8 +356,8 @@ int orc_tonemap_zoom(const pt_Tonemapper* tm, const float* accum, int w, int h, 
           const float scale[7] = {1, 2, 4, 8, 16, 32, 64};
           for(int i = 0; i < 7; ++i)
           {
-            float v1 = luminance(im.fetch(uvz, i).xyz()) * factor;
-            float v2 = luminance(im.fetch(uvz, i + 1).xyz()) * factor;
+            float v1 = luminance(im.fetch(uvz, im.sel[i]).xyz()) * factor;  // :82-83: the third argument of texture() is a LOD bias
+            float v2 = luminance(im.fetch(uvz, im.sel[i + 1]).xyz()) * factor;
             if(std::fabs(v1 - v2) / ((tm->key * mpow(2.0f, phi) / (scale[i] * scale[i])) + v1) > epsilon)
             {
               La = v1;
@@ -382,11 +395,18 @@ int orc_tonemap_zoom(const pt_Tonemapper* tm, const float* accum, int w, int h, 
       if(out8)
       {
         for(int k = 0; k < 3; ++k)
-          out8[o + k] = (uint8_t)std::floor(gclamp(color[k], 0.0f, 1.0f) * 255.0f + 0.5f);
-        out8[o + 3] = (uint8_t)std::floor(gclamp(hdr4.w, 0.0f, 1.0f) * 255.0f + 0.5f);
+          out8[o + k] = unorm8(color[k]);
+        out8[o + 3] = unorm8(hdr4.w);
       }
     }
   }
+  return 0;
+}
+// the store on its own: n floats -> n codes (tests/test_display_model.py quantises the compiled reference's fragColor with it)
+int orc_unorm8(uint64_t n, const float* in, uint8_t* out)
+{
+  for(uint64_t i = 0; i < n; ++i)
+    out[i] = unorm8(in[i]);
   return 0;
 }
 int orc_tonemap(const pt_Tonemapper* tm, const float* accum, int W, int H, uint8_t* out) { return orc_tonemap_zoom(tm, accum, W, H, W, H, out, nullptr); }

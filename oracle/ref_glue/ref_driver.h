@@ -41,6 +41,7 @@ struct sampler2D {
   int           w = 0, h = 0;
   const RefMip* mips = nullptr;
   int           numMips = 0;
+  float         baseLod = 0.0f;  // kind 2: lambda_base of an implicit-LOD fetch, log2 of the texels of level 0 stepped per pixel (set by the pass that binds the image)
 };
 struct image2D {
   float* px = nullptr;  // RGBA32F, row-major
@@ -73,8 +74,9 @@ inline vec4 texture(const sampler2D& s, vec2 uv, float bias = 0.0f)
     g_hooks.sample_env(g_hooks.user, uv.x, uv.y, r);
     return vec4(r[0], r[1], r[2], 1.0f);
   }
-  // full-screen pass at 1:1 (or magnified): implicit LOD 0, so the level is the bias, rounded (mipmapMode NEAREST)
-  return fetch_nearest(s, uv, (int)::floorf(bias + 0.5f));
+  // Vulkan "LOD Operation": lambda = clamp(lambda_base + bias, minLod = 0, maxLod = FLT_MAX); "Image Level(s) Selection": the level is the nearest
+  // integer to min(lambda, numMips - 1) (mipmapMode NEAREST).  `bias` is a LOD bias, not a LOD: under a magnifying pass lambda_base is negative.
+  return fetch_nearest(s, uv, (int)::fminf(::floorf(::fmaxf(s.baseLod + bias, 0.0f) + 0.5f), float(s.numMips - 1)));
 }
 inline vec4 textureLod(const sampler2D& s, vec2 uv, float lod)
 {

@@ -111,6 +111,7 @@ int ref_tonemap(const pt_Tonemapper* t, const float* rgba, int W, int H, float* 
   std::memcpy(&tm, t, sizeof(Tonemapper));
   inImage.kind = 2; inImage.w = W; inImage.h = H;
   inImage.mips = mc.mips.data(); inImage.numMips = (int)mc.mips.size();
+  inImage.baseLod = ::log2f(t->zoom);  // the full-screen pass steps uvCoords * zoom: `zoom` texels of level 0 per pixel on both axes
 #pragma omp parallel for schedule(static)
   for(int y = 0; y < H; ++y)
     for(int x = 0; x < W; ++x)

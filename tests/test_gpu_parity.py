@@ -394,7 +394,9 @@ def test_pipelined_display_equals_the_synchronous_loop(env_small):
 
 def test_tonemap_matches_oracle(env_small):
     """post.frag incl. dithering, global and local auto-exposure on the vkCmdBlitImage mip chain (odd sizes: 150 -> 75 -> 37 ...), and the
-    de-scaled preview (Tonemapper.zoom): RGBA8 output identical to the oracle's."""
+    de-scaled preview (Tonemapper.zoom): RGBA8 output identical to the oracle's.  Under zoom 1/2 with autoExposure = 3 both sides read the levels
+    nearest(max(0, i - 1)) that texture()'s LOD bias selects (lambda_base = log2(zoom)), no longer level i: the oracle and the kernel moved together,
+    held to the model of tests/golden/gen_display_kat.py by tests/test_display_gpu.py."""
     cfg = Config(synth.feature_box(tex_size=64), env_small, 160, 120)
     h, r = render_hip(cfg, 4, return_obj=True)
     for dither, auto in ((0, 0), (1, 0), (1, 1), (0, 3), (1, 3)):

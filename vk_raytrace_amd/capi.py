@@ -49,6 +49,7 @@ API = [
     ("pt_tonemap_begin", C.c_int, [_P, C.POINTER(hd.Tonemapper), C.c_int, C.c_int]),
     ("pt_tonemap_end", C.c_int, [_P, _P]),
     ("pt_tonemap_pending", C.c_int, [_P]),
+    ("pt_debug_display_level", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_local_shard", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_scatter_shards", C.c_int, [_P, _P, C.c_int]),
     ("pt_comm_get_unique_id", C.c_int, [_P]),

@@ -1006,13 +1006,12 @@ int pt_pick(pt_context* c, float pick_x, float pick_y, const float* view_inverse
 }
 
 }  // extern "C"
-// The display pass enqueued on the context's stream, ending with the copy of the RGBA8 image to `out` (host memory; the caller synchronises).
-// readDone: recorded once the accumulation image has been read, and made the event the next frame's accumulate step waits for -- frames
-// rendered after this call may then overlap the rest of the pass.
-static int enqueue_tonemap(pt_context* c, const pt_Tonemapper* tm, int dispW, int dispH, uint8_t* out, hipEvent_t readDone)
+// The offscreen image as post.frag samples it, enqueued on the context's stream from the row-major accumulation image (untile_to_rowmajor): level 0 is
+// the accumulation image itself, or a viewport-sized image with it in the top-left corner (texels outside: zero); levels 1.. only with `chain`
+// (src/sample_example.cpp:423-427 generates the chain only with auto-exposure): extent max(1, e / 2), floor(log2(max(w, h))) + 1 levels.
+// readDone (may be null): recorded once the accumulation image has been read, and made the event the next frame's accumulate step waits for.
+int display_chain(pt_context* c, int dispW, int dispH, bool chain, hipEvent_t readDone, MipView& mv)
 {
-  if(!tm || !out)
-    return c->fail(PT_ERR_INVALID, "pt_tonemap: null");
   if(c->width == 0)
     return c->fail(PT_ERR_STATE, "pt_tonemap before pt_resize");
   if(dispW < c->width || dispH < c->height || dispW > 32768 || dispH > 32768)
@@ -1026,13 +1025,10 @@ static int enqueue_tonemap(pt_context* c, const pt_Tonemapper* tm, int dispW, in
     HIP_TRY(c, hipEventRecord(readDone, c->stream));
     c->lastAccum = readDone;
   }
-  // level 0: the accumulation image itself, or a viewport-sized image with it in the corner; levels 1.. only with auto-exposure
-  // (src/sample_example.cpp:423-427 generates the chain only then)
-  MipView mv{};
   const bool padded = dispW != c->width || dispH != c->height;
   size_t     texels = padded ? size_t(dispW) * dispH : 0, offset = texels;
   int        lw = dispW, lh = dispH, levels = 1;
-  if(tm->autoExposure & 1)
+  if(chain)
     for(int m = dispW > dispH ? dispW : dispH; m > 1; m >>= 1)
     {
       lw = lw > 1 ? lw / 2 : 1;
@@ -1041,8 +1037,6 @@ static int enqueue_tonemap(pt_context* c, const pt_Tonemapper* tm, int dispW, in
       levels++;
     }
   if(texels && (rc = dev_alloc(c, c->dMips, sizeof(float4) * texels)) != PT_OK)
-    return rc;
-  if((rc = dev_alloc(c, c->dRgba8, 4 * size_t(dispW) * dispH)) != PT_OK)
     return rc;
   float4* pool = (float4*)c->dMips.p;
   if(padded)
@@ -1057,6 +1051,36 @@ static int enqueue_tonemap(pt_context* c, const pt_Tonemapper* tm, int dispW, in
     pt_launch_blit_linear(c->stream, mv.level[i - 1], mv.w[i - 1], mv.h[i - 1], pool + offset, mv.w[i], mv.h[i]);
     offset += size_t(mv.w[i]) * mv.h[i];
   }
+  HIP_TRY(c, hipGetLastError());
+  return PT_OK;
+}
+// The level texture(inImage, uvCoords * zoom, bias) reads, bias 0..7 (post.frag:82-83, :101), by the Vulkan rules "Scale Factor Operation, LOD
+// Operation and Image Level(s) Selection": in the full-screen pass uvCoords * zoom advances `zoom` texels of level 0 per pixel on both axes, so
+// lambda_base = log2(zoom); lambda = clamp(lambda_base + bias, minLod = 0, maxLod = FLT_MAX) (the sampler of render_output.cpp:98-100); with
+// mipmapMode NEAREST the level is the nearest integer to min(lambda, levels - 1).  Computed here so that the kernel needs no log2.
+static void select_levels(MipView& mv, float zoom)
+{
+  const float base = log2f(zoom);
+  for(int i = 0; i < 8; ++i)
+  {
+    const float lambda = fmaxf(base + float(i), 0.0f);  // fmaxf: 0 for a NaN (zoom < 0)
+    mv.sel[i]          = int(fminf(floorf(lambda + 0.5f), float(mv.n - 1)));
+  }
+}
+// The display pass enqueued on the context's stream, ending with the copy of the RGBA8 image to `out` (host memory; the caller synchronises).
+// readDone: recorded once the accumulation image has been read, and made the event the next frame's accumulate step waits for -- frames
+// rendered after this call may then overlap the rest of the pass.
+static int enqueue_tonemap(pt_context* c, const pt_Tonemapper* tm, int dispW, int dispH, uint8_t* out, hipEvent_t readDone)
+{
+  if(!tm || !out)
+    return c->fail(PT_ERR_INVALID, "pt_tonemap: null");
+  int     rc;
+  MipView mv{};
+  if((rc = display_chain(c, dispW, dispH, (tm->autoExposure & 1) != 0, readDone, mv)) != PT_OK)
+    return rc;
+  select_levels(mv, tm->zoom);
+  if((rc = dev_alloc(c, c->dRgba8, 4 * size_t(dispW) * dispH)) != PT_OK)
+    return rc;
   pt_launch_tonemap(c->stream, mv, *tm, (uint32_t*)c->dRgba8.p);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(out, c->dRgba8.p, 4 * size_t(dispW) * dispH, hipMemcpyDeviceToHost, c->stream));

@@ -167,6 +167,7 @@ int        flush_pending(pt_context* c);    // launches the frames handed to pt_
 hipError_t sync_all(pt_context* c);         // flush_pending, then waits for every stream of the context
 int        check_traversal(pt_context* c);  // after a synchronisation: PT_ERR_STATE once a traversal ran out of stack
 void       clear_overflow(pt_context* c);
+int        display_chain(pt_context* c, int dispW, int dispH, bool chain, hipEvent_t readDone, MipView& mv);  // the display pass's offscreen image and its mip chain, enqueued
 void       refresh_scene_ptrs(pt_context* c);
 int        upload_instances(pt_context* c);
 std::vector<InstanceRec> effective_instances(const pt_context* c);  // the instance records as the kernels see them

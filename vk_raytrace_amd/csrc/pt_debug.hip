@@ -266,3 +266,24 @@ extern "C" __attribute__((visibility("default"))) int pt_debug_surface_probe(pt_
     k_surface_probe<<<dim3((n + 63) / 64), dim3(64), 0, c->stream>>>(c->scene, lim, kind, n, dIn, in_stride, dOut, out_stride);
   });
 }
+// One level of the offscreen image the display pass samples (pt_capi.hip display_chain: the very function pt_tonemap_zoom runs), copied back for
+// tests/test_display_gpu.py: the zero padding of a de-scaled viewport and every vkCmdBlitImage(LINEAR) level, which the RGBA8 image only shows through
+// the exposure.  Returns the number of levels of the full chain; a level outside it copies nothing.
+extern "C" __attribute__((visibility("default"))) int pt_debug_display_level(pt_context* c, int disp_w, int disp_h, int level, float* out, int* w, int* h)
+{
+  CTX_CHECK(c);
+  MipView mv{};
+  int     rc = display_chain(c, disp_w, disp_h, true, nullptr, mv);
+  if(rc != PT_OK)
+    return rc;
+  if(level >= 0 && level < mv.n)
+  {
+    if(w) *w = mv.w[level];
+    if(h) *h = mv.h[level];
+    if(out)
+      HIP_TRY(c, hipMemcpyAsync(out, mv.level[level], sizeof(float4) * size_t(mv.w[level]) * mv.h[level], hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, sync_all(c));
+  rc = check_traversal(c);
+  return rc != PT_OK ? rc : mv.n;
+}

@@ -183,6 +183,7 @@ struct MipView {
   const float4* level[20];
   int           w[20], h[20];
   int           n;
+  int           sel[8];  // level read by texture(inImage, uv, bias) for bias 0..7 under the pass's zoom (pt_capi.hip select_levels)
 };
 void pt_launch_tonemap(hipStream_t stream, const MipView& mv, const pt_Tonemapper& tm, uint32_t* outRgba8);
 void pt_launch_blit_linear(hipStream_t stream, const float4* src, int sw, int sh, float4* dst, int dw, int dh);

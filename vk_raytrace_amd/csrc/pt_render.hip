@@ -995,7 +995,7 @@ __global__ void k_tonemap(MipView mv, pt_Tonemapper tm, uint32_t* __restrict__ o
     return;
   f2     uvc = f2{(float(x) + 0.5f) / float(width), (float(y) + 0.5f) / float(height)};  // passthrough.vert at the pixel centre
   f2     uvz = uvc * tm.zoom;
-  float4 p   = mip_fetch(mv, uvz.x, uvz.y, 0);  // post.frag:101
+  float4 p   = mip_fetch(mv, uvz.x, uvz.y, mv.sel[0]);  // post.frag:101 (no bias: the level of bias 0)
   f3     hdr = xyz(p);
   if(tm.autoExposure & 1)
   {
@@ -1010,8 +1010,9 @@ __global__ void k_tonemap(MipView mv, pt_Tonemapper tm, uint32_t* __restrict__ o
       const float factor = tm.key / avgLum2, epsilon = 0.05f, phi = 2.0f;
       for(int i = 0; i < 7; ++i)
       {
-        float v1 = lum709(mip_fetch(mv, uvz.x, uvz.y, i)) * factor;
-        float v2 = lum709(mip_fetch(mv, uvz.x, uvz.y, i + 1)) * factor;
+        // :82-83 texture(inImage, uv, bias): the third argument is a LOD bias; the level it selects under tm.zoom comes from the host (MipView::sel)
+        float v1 = lum709(mip_fetch(mv, uvz.x, uvz.y, mv.sel[i])) * factor;
+        float v2 = lum709(mip_fetch(mv, uvz.x, uvz.y, mv.sel[i + 1])) * factor;
         float sc = float(1 << i);
         if(fabsf(v1 - v2) / ((tm.key * pt_pow(2.0f, phi) / (sc * sc)) + v1) > epsilon)
         {
@@ -1050,7 +1051,9 @@ __global__ void k_tonemap(MipView mv, pt_Tonemapper tm, uint32_t* __restrict__ o
   color    = lerp(splat3(i), color, tm.saturation);
   f2 uv    = f2{(uvc.x * tm.renderingRatio[0] - 0.5f) * 2.0f, (uvc.y * tm.renderingRatio[1] - 0.5f) * 2.0f};
   color *= 1.0f - (uv.x * uv.x + uv.y * uv.y) * tm.vignette;
-  auto q8 = [](float v) { return uint32_t(floorf(clampf(v, 0.f, 1.f) * 255.0f + 0.5f)); };
+  // float -> UNORM8 (Vulkan "Conversion from Floating-Point to Normalized Fixed-Point"): clamp to [0, 1], scale, nearest integer; NaN stores 0.
+  // The comparisons pick 0 for NaN before the conversion to an integer, which is undefined for it.
+  auto q8 = [](float v) { return uint32_t(floorf((v > 0.f ? (v < 1.f ? v : 1.f) : 0.f) * 255.0f + 0.5f)); };
   out[size_t(y) * width + x] = q8(color.x) | (q8(color.y) << 8) | (q8(color.z) << 16) | (q8(p.w) << 24);
 }
 
