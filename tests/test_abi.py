@@ -101,7 +101,7 @@ def _parse_tuning(s):
     L.pt_debug_parse_tuning.restype = C.c_int
     n = L.pt_debug_parse_tuning(s.encode() if s is not None else None, out, 32, unk, 512)
     keys = ["stateMB", "stateGB", "packetClosest", "mergeSingles", "cnodes", "shadeTris", "tail", "warm", "texTile", "texGroups", "regen", "packetTwo", "blasWorkers", "batch",
-            "inflight", "displaySlots", "bands", "bandTiles", "fuse", "build", "accel"]
+            "inflight", "displaySlots", "bands", "bandTiles", "fuse", "build", "accel", "arena"]
     assert n == len(keys)
     return dict(zip(keys, list(out)[:n])), unk.value.decode()
 
@@ -118,6 +118,7 @@ def test_pt_tune_is_parsed_key_by_key():
     for k, v in (("build=lbvh", 0), ("build=sah", 1), ("build=ploc", 2), ("build=sahdev", 3)):
         assert _parse_tuning(k)[0]["build"] == v
     assert _parse_tuning("bandTiles=0")[0]["bandTiles"] == 1
-    every = "stateMB=1,stateGB=2,packetClosest=3,mergeSingles=0,cnodes=0,shadeTris=0,tail=7,warm=0,texTile=0,texGroups=0,regen=0,packetTwo=0,blasWorkers=2,batch=9,inflight=2,displaySlots=1,bands=5,bandTiles=6,fuse=0"
+    assert _parse_tuning(None)[0]["arena"] == 1 and _parse_tuning("arena=0")[0]["arena"] == 0   # 0: builds take no arena, every temporary is its own allocation
+    every = "stateMB=1,stateGB=2,packetClosest=3,mergeSingles=0,cnodes=0,shadeTris=0,tail=7,warm=0,texTile=0,texGroups=0,regen=0,packetTwo=0,blasWorkers=2,batch=9,inflight=2,displaySlots=1,bands=5,bandTiles=6,fuse=0,arena=0"
     d, unk = _parse_tuning(every)
     assert unk == "" and [d[t.split("=")[0]] for t in every.split(",")] == [int(t.split("=")[1]) for t in every.split(",")]

@@ -48,7 +48,7 @@ def test_spill_scene_path_traced_through_every_traversal_kernel():
     for tune in ("", "tail=0", "tail=1000000000", "packetClosest=0", "cnodes=0", "fuse=0", "fuse=2", "build=lbvh", "build=ploc", "build=sah",
                  "accel=two", "accel=two,tail=0", "accel=two,tail=1000000000", "accel=two,packetClosest=0", "accel=two,cnodes=0", "accel=two,fuse=0",
                  "accel=two,fuse=2", "accel=two,build=lbvh", "accel=two,build=sah", "accel=two,mergeSingles=0", "accel=two,mergeSingles=0,tail=0",
-                 "accel=two,mergeSingles=0,tail=1000000000"):
+                 "accel=two,mergeSingles=0,tail=1000000000", "arena=0", "accel=two,arena=0"):
         assert_identical(_render_in_subprocess(tune, frames=3, max_samples=2, scene="spill"), ref, f"PT_TUNE={tune!r}")
 
 

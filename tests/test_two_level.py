@@ -345,11 +345,15 @@ def test_two_level_forest_build_runs_and_small_meshes(env_small):
     _assert_identical(render_hip(cfg, 3), want, "flat structure")
     aov = Config(sc, env_small, 192, 96, debug=hd.eNormal)
     assert np.array_equal(render_hip(aov, 1, accel=capi.PT_ACCEL_TWO_LEVEL), render_oracle(aov, 1))
-    # the per-mesh path (any builder but the device SAH one): PT_TUNE is read by pt_create into the context's own knobs
+    # the per-mesh path (any builder but the device SAH one) and the builds without an arena (every temporary its own allocation; with one worker and
+    # a BLAS per mesh the worker's scratch is reused build after build): PT_TUNE is read by pt_create into the context's own knobs
     keep = os.environ.get("PT_TUNE")
-    os.environ["PT_TUNE"] = "build=lbvh"
     try:
-        _assert_identical(render_hip(cfg, 3, accel=capi.PT_ACCEL_TWO_LEVEL), want, "one build per mesh")
+        for tune in ("build=lbvh", "arena=0", "arena=0,build=ploc", "arena=0,mergeSingles=0,blasWorkers=1"):
+            os.environ["PT_TUNE"] = tune
+            _assert_identical(render_hip(cfg, 3, accel=capi.PT_ACCEL_TWO_LEVEL), want, f"two-level, PT_TUNE={tune}")
+            if tune == "arena=0":
+                _assert_identical(render_hip(cfg, 3), want, f"flat, PT_TUNE={tune}")
     finally:
         if keep is None:
             del os.environ["PT_TUNE"]

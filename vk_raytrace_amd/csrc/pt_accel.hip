@@ -11,7 +11,7 @@
 // It is used three ways: over the world-space triangles of every node (the flat structure, default), over the object-space triangles of
 // one prim-mesh (a BLAS of the two-level structure: pt_blas_build), and over the world boxes of the instances given as "diagonal" records
 // (the TLAS: pt_tlas_build).  Temporaries come out of the caller's arena (PtScratch) or are allocated singly; everything runs on the
-// caller's stream.
+// caller's stream.  The kernels come first; the host side is one function per stage, and binary_tree lists every builder's sequence.
 #include <hip/hip_runtime.h>
 #include <vector>
 #include <cfloat>
@@ -1076,372 +1076,431 @@ __global__ void k_collapse(const BvhNode* __restrict__ b2, const CollapseItem* _
   out[it.wide] = w;
 }
 
-}  // namespace
+// ---- pt_accel_build: the stages ---------------------------------------------------------------------------------------------------------
+// One build: what every stage needs, and the lists the stages share (n entries each unless noted; all out of `sc`).  Lists that one builder alone
+// uses are obtained in that builder's function.
+struct Build {
+  hipStream_t stream;
+  PtScratch&  sc;
+  uint32_t    n;  // primitives (>= 1)
+  uint32_t    G;  // blocks of kBlock threads over n
+  char*       err;
+  size_t      errLen;
+  TriRec*   trisOut;  // the caller's arrays
+  AlphaRec* alphaOut;
+  BvhNode*  nodesOut;
+  WideNode* wideOut;
+  // primitives as given: records, any-hit inputs, centroids, the centroids' bounds (6 words of ordered bits)
+  TriRec*   unsorted      = nullptr;
+  AlphaRec* alphaUnsorted = nullptr;
+  float4*   cen           = nullptr;
+  uint32_t* bounds        = nullptr;
+  // the binary tree: leaf slot -> primitive, Morton keys in leaf order (morton_order only), boxes, links, arrival counters of the bottom-up passes
+  uint32_t *order = nullptr, *mortonKeys = nullptr;
+  float4 *  leafLo = nullptr, *leafHi = nullptr, *nodeLo = nullptr, *nodeHi = nullptr;
+  uint32_t *childL = nullptr, *childR = nullptr, *parI = nullptr, *parL = nullptr;
+  unsigned* arrive = nullptr;
 
-#define HIPCHK(x)                                                                                              \
+  // Every failing return of a stage passes here or through HIP_OR_FAIL.  Draining before reuse: nothing of the build may still be running -- nor any
+  // copy to or from a stage's stack be pending -- when the stage's frame goes and the scratch is rewound.
+  int fail(const char* msg) const
+  {
+    snprintf(err, errLen, "%s", msg);
+    (void)hipStreamSynchronize(stream);
+    return -1;
+  }
+};
+constexpr int      kBlock    = 256;
+const uint32_t     kNoParent = BVH_NONE;  // static storage: the source of async copies
+enum { REFIT = 1, ROTATE = 2 };           // what a topology leaves for binary_boxes_and_emit to do
+
+// A failing stage drains the stream and returns at once; pt_accel_build rewinds the scratch.
+#define HIP_OR_FAIL(b, x)                                                                                      \
   do                                                                                                           \
   {                                                                                                            \
-    hipError_t e_ = (x);                                                                                       \
+    const hipError_t e_ = (x);                                                                                 \
     if(e_ != hipSuccess)                                                                                       \
     {                                                                                                          \
-      snprintf(err, errLen, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__);           \
-      goto fail;                                                                                               \
+      snprintf((b).err, (b).errLen, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__);   \
+      (void)hipStreamSynchronize((b).stream);                                                                  \
+      return -1;                                                                                               \
     }                                                                                                          \
   } while(0)
 
-// Builds TriRec[numTris] (leaf order) and BvhNode[max(1,numTris-1)] into caller-allocated device memory.
-// dProxies (may be null): the primitives are given as ready-made records instead of (instance, triangle) pairs -- the TLAS of the two-level
-// structure is built over one "diagonal" record per instance (p0 = box min, e1 = box extent, e2 = 0: its bounding box is the instance's box).
-// scratch (may be null): temporaries come out of the caller's arena instead of one device allocation each (a scene of hundreds of BLASes).
+int shared_lists(Build& b)
+{
+  static const uint32_t initBounds[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+  const size_t          n = b.n;
+  PtScratch&            sc = b.sc;
+  if(!(sc.take(b.unsorted, n) && sc.take(b.alphaUnsorted, n) && sc.take(b.cen, n) && sc.take(b.bounds, 6) && sc.take(b.order, n) && sc.take(b.leafLo, n) && sc.take(b.leafHi, n) &&
+       sc.take(b.nodeLo, n) && sc.take(b.nodeHi, n) && sc.take(b.childL, n) && sc.take(b.childR, n) && sc.take(b.parI, n) && sc.take(b.parL, n) && sc.take(b.arrive, n)))
+    return b.fail("out of device memory for the build's lists");
+  HIP_OR_FAIL(b, hipMemcpyAsync(b.bounds, initBounds, sizeof(initBounds), hipMemcpyHostToDevice, b.stream));
+  HIP_OR_FAIL(b, hipMemsetAsync(b.arrive, 0, 4 * n, b.stream));
+  return 0;
+}
+
+// primitives: the world-space triangles of the instances (trace contract T1), or the caller's ready-made records
+int primitives(Build& b, const InstanceRec* dInst, uint32_t numInst, const float4* dVertices, const uint32_t* dIndices, const TriRec* dProxies)
+{
+  if(dProxies)
+  {
+    HIP_OR_FAIL(b, hipMemcpyAsync(b.unsorted, dProxies, sizeof(TriRec) * size_t(b.n), hipMemcpyDeviceToDevice, b.stream));
+    HIP_OR_FAIL(b, hipMemsetAsync(b.alphaUnsorted, 0, sizeof(AlphaRec) * size_t(b.n), b.stream));
+    k_proxy_centroids<<<b.G, kBlock, 0, b.stream>>>(b.n, dProxies, b.cen, b.bounds);
+  }
+  else
+    k_world_tris<<<b.G, kBlock, 0, b.stream>>>(b.n, dInst, numInst, dVertices, dIndices, b.unsorted, b.alphaUnsorted, b.cen, b.bounds);
+  return 0;
+}
+
+// leaf order of the LBVH and PLOC builders: Morton codes of the centroids, radix sorted
+int morton_order(Build& b)
+{
+  const uint32_t sortBlocks = (b.n + SORT_ITEMS - 1) / SORT_ITEMS;
+  uint32_t *     keysB = nullptr, *valsB = nullptr, *hist = nullptr;
+  if(!(b.sc.take(b.mortonKeys, b.n) && b.sc.take(keysB, b.n) && b.sc.take(valsB, b.n) && b.sc.take(hist, size_t(256) * sortBlocks)))
+    return b.fail("out of device memory for the radix sort");
+  k_morton<<<b.G, kBlock, 0, b.stream>>>(b.n, b.cen, b.bounds, b.mortonKeys, b.order);
+  uint32_t *kin = b.mortonKeys, *kout = keysB, *vin = b.order, *vout = valsB;
+  for(int pass = 0; pass < 4; ++pass)
+  {
+    int shift = pass * 8;
+    k_sort_hist<<<sortBlocks, 64, 0, b.stream>>>(kin, b.n, shift, hist, sortBlocks);
+    k_sort_scan<<<1, 256, 0, b.stream>>>(hist, 256u * sortBlocks);
+    k_sort_scatter<<<sortBlocks, 64, 0, b.stream>>>(kin, vin, kout, vout, b.n, shift, hist, sortBlocks);
+    std::swap(kin, kout);
+    std::swap(vin, vout);
+  }
+  // after 4 passes the sorted data is back in mortonKeys / order
+  return 0;
+}
+
+// records in leaf order + padded leaf boxes
+void leaf_gather(Build& b)
+{
+  k_gather<<<b.G, kBlock, 0, b.stream>>>(b.n, b.order, b.unsorted, b.trisOut, b.alphaUnsorted, b.alphaOut, b.leafLo, b.leafHi);
+}
+
+// LBVH: the Karras radix tree over the sorted keys (n == 1: no links, binary_boxes_and_emit writes the single leaf)
+void topology_lbvh(Build& b)
+{
+  if(b.n >= 2)
+    k_hierarchy<<<b.G, kBlock, 0, b.stream>>>(int(b.n), b.mortonKeys, b.childL, b.childR, b.parI, b.parL);
+}
+
+// PLOC rounds over the gathered leaves; the cluster count comes back to the host between rounds (the build is not on the timed path).  A round merges
+// at least the globally best pair.  False -- out of memory, a failed launch, or rounds that crawl on an adversarial input -- means that the caller falls
+// back to the radix tree; the failure is soft, so the HIP error is cleared.  PLOC writes the inner boxes while merging: nothing is left to refit.
+bool topology_ploc(Build& b)
+{
+  const uint32_t n = b.n;
+  uint32_t *     cidA = nullptr, *cidB = nullptr, *dNn = nullptr, *dValid = nullptr, *dPos = nullptr, *dBlockSum = nullptr, *dCnt = nullptr;
+  float4 *       cloA = nullptr, *cloB = nullptr, *chiA = nullptr, *chiB = nullptr;
+  PtScratch&     sc = b.sc;
+  bool           ok = sc.take(cidA, n) && sc.take(cidB, n) && sc.take(dNn, n) && sc.take(dValid, n) && sc.take(dPos, n) && sc.take(dBlockSum, size_t((n + 1023) / 1024 + 1)) && sc.take(dCnt, 2) &&
+            sc.take(cloA, n) && sc.take(cloB, n) && sc.take(chiA, n) && sc.take(chiB, n);
+  uint32_t m = n;
+  if(ok)
+  {
+    (void)hipMemsetAsync(dCnt, 0, 8, b.stream);
+    k_ploc_init<<<b.G, kBlock, 0, b.stream>>>(n, b.leafLo, b.leafHi, cidA, cloA, chiA);
+    int rounds = 0, maxRounds = 64;
+    for(uint32_t t = n; t > 1; t >>= 1)
+      maxRounds += 6;
+    while(m > 1 && rounds < maxRounds && ok)
+    {
+      const uint32_t g = (m + 255) / 256, nb = (m + 1023) / 1024;
+      k_ploc_nn<<<g, 256, 0, b.stream>>>(m, PT_PLOC_RADIUS, cloA, chiA, dNn);
+      k_ploc_merge<<<g, 256, 0, b.stream>>>(m, n - 1, dNn, cidA, cloA, chiA, dValid, dCnt, b.childL, b.childR, b.parI, b.parL, b.nodeLo, b.nodeHi);
+      k_ploc_scan_blocks<<<nb, 1024, 0, b.stream>>>(m, dValid, dPos, dBlockSum);
+      k_ploc_scan_sums<<<1, 1024, 0, b.stream>>>(nb, dBlockSum, dCnt + 1);
+      k_ploc_compact<<<g, 256, 0, b.stream>>>(m, dValid, dPos, dBlockSum, cidA, cloA, chiA, cidB, cloB, chiB);
+      uint32_t m2 = 0;
+      ok = hipMemcpyAsync(&m2, dCnt + 1, 4, hipMemcpyDeviceToHost, b.stream) == hipSuccess && hipStreamSynchronize(b.stream) == hipSuccess && m2 >= 1 && m2 < m;
+      m = m2;
+      std::swap(cidA, cidB); std::swap(cloA, cloB); std::swap(chiA, chiB);
+      ++rounds;
+    }
+    ok = ok && m == 1;
+    if(ok)
+      (void)hipMemcpyAsync(b.parI, &kNoParent, 4, hipMemcpyHostToDevice, b.stream);  // the root (node 0) has no parent
+  }
+  if(!ok)
+    (void)hipStreamSynchronize(b.stream);  // no copy to this frame's m2 stays pending
+  (void)hipGetLastError();
+  return ok;
+}
+
+// host SAH, the cross-check of the device SAH builder: topology and leaf order on the host from the records (pt_sah.hip); boxes stay on the device
+int topology_host_sah(Build& b)
+{
+  const size_t          n = b.n;
+  std::vector<TriRec>   hTris(n);
+  std::vector<uint32_t> hVals(n), hL(n), hR(n), hPI(n), hPL(n);
+  HIP_OR_FAIL(b, hipMemcpyAsync(hTris.data(), b.unsorted, sizeof(TriRec) * n, hipMemcpyDeviceToHost, b.stream));
+  HIP_OR_FAIL(b, hipStreamSynchronize(b.stream));
+  pt_sah_topology(b.n, hTris.data(), hVals.data(), hL.data(), hR.data(), hPI.data(), hPL.data());
+  hipError_t upload = hipSuccess;
+  auto       up     = [&](uint32_t* d, const std::vector<uint32_t>& h) { upload = upload != hipSuccess ? upload : hipMemcpyAsync(d, h.data(), 4 * n, hipMemcpyHostToDevice, b.stream); };
+  up(b.order, hVals); up(b.childL, hL); up(b.childR, hR); up(b.parI, hPI); up(b.parL, hPL);
+  const hipError_t uploadSync = hipStreamSynchronize(b.stream);  // the host vectors feed async copies and die with this scope: drained on success and on failure
+  HIP_OR_FAIL(b, upload);
+  HIP_OR_FAIL(b, uploadSync);
+  return 0;
+}
+
+// device binned SAH (pt_sahdev.h), level-synchronous: the number of open nodes comes back to the host between levels.  Every root opens a node of its
+// own -- the big ones in the first level's work list, those of <= SD_SMALL primitives in the small-node list.
+bool device_sah_levels(Build& b, const PtForest* forest)
+{
+  const uint32_t n = b.n;
+  const size_t   maxWork = size_t(n) / (SD_SMALL + 1) + 2, maxSmall = size_t(n) / 2 + 2;
+  float4 *       plo = nullptr, *phi = nullptr;
+  uint32_t *     idxA = nullptr, *idxB = nullptr, *pwA = nullptr, *pwB = nullptr, *binCnt = nullptr, *binBox = nullptr, *dCounts = nullptr;
+  SdWork *       workA = nullptr, *workB = nullptr, *small = nullptr;
+  PtScratch&     sc = b.sc;
+  if(!(sc.take(plo, n) && sc.take(phi, n) && sc.take(idxA, n) && sc.take(idxB, n) && sc.take(pwA, n) && sc.take(pwB, n) && sc.take(workA, maxWork) && sc.take(workB, maxWork) &&
+       sc.take(small, maxSmall) && sc.take(binCnt, maxWork * 3 * SD_BINS) && sc.take(binBox, maxWork * 3 * SD_BINS * 6) && sc.take(dCounts, 2)))
+    return false;
+  // the roots: one per hierarchy of a forest, else the one over all primitives.  The host lists below feed async copies: every path from here on
+  // synchronises before it returns.
+  const uint32_t        numRoots = forest ? forest->numRoots : 1u;
+  std::vector<SdWork>   big, little;
+  std::vector<uint32_t> rootWork(forest ? numRoots : 0u);  // a forest's primitives find their root's work item through these
+  for(uint32_t r = 0; r < numRoots; ++r)
+  {
+    const uint32_t first = forest ? forest->first[r] : 0u, count = forest ? forest->count[r] : n;
+    SdWork         w;
+    sd_init_work(w, first, count, first);
+    if(forest)
+      rootWork[r] = count <= SD_SMALL ? SD_NONE : uint32_t(big.size());
+    (count <= SD_SMALL ? little : big).push_back(w);
+  }
+  uint32_t       nActive = uint32_t(big.size()), nSmall = uint32_t(little.size());
+  const uint32_t counts0[2] = {0u, nSmall};  // next-level counter, small-node counter
+  bool           ok = nActive <= maxWork && nSmall <= maxSmall;
+  auto           up = [&](void* d, const void* h, size_t bytes) { ok = ok && (bytes == 0 || hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, b.stream) == hipSuccess); };
+  up(workA, big.data(), sizeof(SdWork) * big.size());
+  up(small, little.data(), sizeof(SdWork) * little.size());
+  up(dCounts, counts0, 8);
+  if(forest)
+  {
+    uint32_t *dRootWork = nullptr, *dRootNode = nullptr;
+    ok = ok && sc.take(dRootWork, numRoots) && sc.take(dRootNode, numRoots);
+    up(dRootWork, rootWork.data(), 4 * size_t(numRoots));
+    up(dRootNode, forest->first, 4 * size_t(numRoots));  // a root's node id is its first primitive
+    // ids nobody owns (one per root: a root of k leaves uses k - 1 of its k ids) must still be readable by k_emit
+    ok = ok && hipMemsetAsync(b.childL, 0, 4 * size_t(n), b.stream) == hipSuccess && hipMemsetAsync(b.childR, 0, 4 * size_t(n), b.stream) == hipSuccess &&
+         hipMemsetAsync(b.nodeLo, 0, 16 * size_t(n), b.stream) == hipSuccess && hipMemsetAsync(b.nodeHi, 0, 16 * size_t(n), b.stream) == hipSuccess;
+    if(ok)
+    {
+      k_sd_prims<<<b.G, kBlock, 0, b.stream>>>(n, b.unsorted, plo, phi, idxA, pwA, SD_NONE);
+      k_forest_prim_work<<<b.G, kBlock, 0, b.stream>>>(n, b.unsorted, dRootWork, pwA);
+      k_forest_roots<<<(numRoots + 255) / 256, 256, 0, b.stream>>>(numRoots, dRootNode, b.parI);
+      ok = hipStreamSynchronize(b.stream) == hipSuccess;
+    }
+  }
+  else
+  {
+    up(b.parI, &kNoParent, 4);
+    k_sd_prims<<<b.G, kBlock, 0, b.stream>>>(n, b.unsorted, plo, phi, idxA, pwA, nActive ? 0u : SD_NONE);
+  }
+  int levels = 0;
+  while(nActive && ok && levels < 4096)
+  {
+    const size_t nBins = size_t(nActive) * 3 * SD_BINS;
+    k_sd_init_bins<<<unsigned((nBins + 255) / 256), 256, 0, b.stream>>>(nBins, binCnt, binBox);
+    if(levels == 0)  // deeper levels get their centroid bounds from their parents' partition pass
+      k_sd_cbounds<<<b.G, kBlock, 0, b.stream>>>(n, idxA, pwA, workA, plo, phi);
+    k_sd_bin<<<b.G, kBlock, 0, b.stream>>>(n, idxA, pwA, workA, plo, phi, binCnt, binBox);
+    (void)hipMemsetAsync(dCounts, 0, 4, b.stream);  // next-level counter; the small-node counter keeps running
+    SdLists L{workB, dCounts, small, dCounts + 1};
+    k_sd_split<<<(nActive + 63) / 64, 64, 0, b.stream>>>(nActive, workA, binCnt, binBox, L, b.childL, b.childR, b.parI, b.parL);
+    k_sd_partition<<<b.G, kBlock, 0, b.stream>>>(n, idxA, pwA, workA, workB, plo, phi, idxB, pwB);
+    uint32_t counts[2] = {0u, 0u};
+    ok = hipMemcpyAsync(counts, dCounts, 8, hipMemcpyDeviceToHost, b.stream) == hipSuccess && hipStreamSynchronize(b.stream) == hipSuccess && counts[0] <= maxWork && counts[1] <= maxSmall;
+    nActive = counts[0];
+    nSmall  = counts[1];
+    std::swap(idxA, idxB); std::swap(pwA, pwB); std::swap(workA, workB);
+    ++levels;
+  }
+  if(!ok || nActive)
+  {
+    (void)hipStreamSynchronize(b.stream);
+    return false;
+  }
+  if(nSmall)
+    k_sd_small<<<(nSmall + 63) / 64, 64, 0, b.stream>>>(nSmall, small, idxA, plo, phi, b.childL, b.childR, b.parI, b.parL);
+  ok = hipMemcpyAsync(b.order, idxA, 4 * size_t(n), hipMemcpyDeviceToDevice, b.stream) == hipSuccess;
+  return hipStreamSynchronize(b.stream) == hipSuccess && ok && hipGetLastError() == hipSuccess;
+}
+int topology_device_sah(Build& b, const PtForest* forest)
+{
+  const bool ok = device_sah_levels(b, forest);
+  (void)hipGetLastError();  // a forest's failure is soft (pt_blas_build falls back): the error must not surface in a later HIP_TRY
+  return ok ? 0 : b.fail("device SAH build failed (out of memory or a kernel error)");
+}
+
+// inner boxes (refit, unless the topology wrote them), tree rotations (the builders without a SAH), the 64-byte binary nodes; then the build's first
+// checkpoint: launch errors surface here and the stream is drained
+int binary_boxes_and_emit(Build& b, int todo, uint32_t leafOffset)
+{
+  const uint32_t n = b.n;
+  if(n == 1)
+    k_single_leaf<<<1, 1, 0, b.stream>>>(b.leafLo, b.leafHi, b.trisOut, b.nodesOut);
+  else
+  {
+    if(todo & REFIT)
+      k_refit<<<b.G, kBlock, 0, b.stream>>>(int(n), b.childL, b.childR, b.parI, b.parL, b.leafLo, b.leafHi, b.nodeLo, b.nodeHi, b.arrive);
+    for(int pass = 0; pass < PT_ROTATE_PASSES && (todo & ROTATE); ++pass)
+    {
+      (void)hipMemsetAsync(b.arrive, 0, 4 * size_t(n), b.stream);
+      k_rotate<<<b.G, kBlock, 0, b.stream>>>(int(n), b.childL, b.childR, b.parI, b.parL, b.leafLo, b.leafHi, b.nodeLo, b.nodeHi, b.arrive);
+    }
+    k_emit<<<(n - 1 + kBlock - 1) / kBlock, kBlock, 0, b.stream>>>(int(n - 1), b.childL, b.childR, b.leafLo, b.leafHi, b.nodeLo, b.nodeHi, b.trisOut, b.nodesOut, leafOffset);
+  }
+  HIP_OR_FAIL(b, hipGetLastError());
+  HIP_OR_FAIL(b, hipStreamSynchronize(b.stream));
+  return 0;
+}
+
+// The binary tree of one builder, stage by stage.  This is the launch sequence of each builder: the SAH builders deliver leaf order and links
+// together and gather afterwards; the Morton builders sort, gather, and link the gathered leaves.
+int binary_tree(Build& b, PtBuilder builder, const PtForest* forest)
+{
+  switch(builder)
+  {
+    case PT_BUILD_SAHDEV:
+      if(topology_device_sah(b, forest) != 0)
+        return -1;
+      leaf_gather(b);
+      return binary_boxes_and_emit(b, REFIT, forest ? forest->leafOffset : 0u);
+    case PT_BUILD_SAH:
+      if(topology_host_sah(b) != 0)
+        return -1;
+      leaf_gather(b);
+      return binary_boxes_and_emit(b, REFIT, 0u);
+    case PT_BUILD_PLOC:
+    case PT_BUILD_LBVH:
+      break;
+  }
+  if(morton_order(b) != 0)
+    return -1;
+  leaf_gather(b);
+  if(builder == PT_BUILD_PLOC && topology_ploc(b))
+    return binary_boxes_and_emit(b, ROTATE, 0u);
+  topology_lbvh(b);  // LBVH, and the PLOC fallback: a PLOC build that stalls or fails continues as the radix tree over the same leaves
+  return binary_boxes_and_emit(b, REFIT | ROTATE, 0u);
+}
+
+// collapse to the wide layout, one BVH level per launch (the queue sizes come back to the host between levels; the build is not on the timed path).
+// With a forest every root starts a queue entry of its own: binary root first[r] becomes wide node wideBase[r], its descendants are allocated behind it.
+int collapse_to_wide(Build& b, const PtForest* forest, uint32_t* numWideOut)
+{
+  CollapseItem* dQ[2] = {nullptr, nullptr};
+  uint32_t *    dCnt = nullptr, *dRootCount = nullptr, *dRootBase = nullptr;
+  if(!(b.sc.take(dQ[0], b.n) && b.sc.take(dQ[1], b.n) && b.sc.take(dCnt, 2)))
+    return b.fail("out of device memory for the collapse queues");
+  uint32_t cnt[2] = {0u, 1u};  // next-queue size, wide nodes allocated (root = 0)
+  uint32_t nIn    = 1;
+  if(forest)
+  {
+    std::vector<CollapseItem> roots(forest->numRoots);
+    std::vector<uint32_t>     ones(forest->numRoots, 1u);
+    for(uint32_t r = 0; r < forest->numRoots; ++r)
+      roots[r] = CollapseItem{forest->first[r], forest->wideBase[r], r};
+    if(!(b.sc.take(dRootCount, forest->numRoots) && b.sc.take(dRootBase, forest->numRoots)))
+      return b.fail("out of device memory for the collapse queues");
+    hipError_t upload = hipMemcpyAsync(dQ[0], roots.data(), sizeof(CollapseItem) * roots.size(), hipMemcpyHostToDevice, b.stream);
+    upload            = upload != hipSuccess ? upload : hipMemcpyAsync(dRootCount, ones.data(), 4 * ones.size(), hipMemcpyHostToDevice, b.stream);
+    upload            = upload != hipSuccess ? upload : hipMemcpyAsync(dRootBase, forest->wideBase, 4 * size_t(forest->numRoots), hipMemcpyHostToDevice, b.stream);
+    const hipError_t uploadSync = hipStreamSynchronize(b.stream);  // the host vectors die with this scope: drained on success and on failure
+    HIP_OR_FAIL(b, upload);
+    HIP_OR_FAIL(b, uploadSync);
+    nIn = forest->numRoots;
+  }
+  else
+  {
+    static const CollapseItem first{0u, 0u, 0u};
+    HIP_OR_FAIL(b, hipMemcpyAsync(dQ[0], &first, sizeof(first), hipMemcpyHostToDevice, b.stream));
+  }
+  int cur = 0;
+  while(nIn)
+  {
+    HIP_OR_FAIL(b, hipMemcpyAsync(dCnt, cnt, 8, hipMemcpyHostToDevice, b.stream));
+    k_collapse<<<(nIn + 63) / 64, 64, 0, b.stream>>>(b.nodesOut, dQ[cur], nIn, dQ[cur ^ 1], dCnt, b.wideOut, dRootCount, dRootBase);
+    HIP_OR_FAIL(b, hipMemcpyAsync(cnt, dCnt, 8, hipMemcpyDeviceToHost, b.stream));
+    HIP_OR_FAIL(b, hipStreamSynchronize(b.stream));
+    nIn    = cnt[0];
+    cnt[0] = 0;
+    cur ^= 1;
+  }
+  *numWideOut = cnt[1];
+  if(forest)
+  {
+    HIP_OR_FAIL(b, hipMemcpyAsync(forest->numWide, dRootCount, 4 * size_t(forest->numRoots), hipMemcpyDeviceToHost, b.stream));
+    HIP_OR_FAIL(b, hipStreamSynchronize(b.stream));
+    uint32_t total = 0;
+    for(uint32_t r = 0; r < forest->numRoots; ++r)
+      total += forest->numWide[r];
+    *numWideOut = total;
+  }
+  return 0;
+}
+
+}  // namespace
+
 int pt_accel_build(hipStream_t stream, const PtTuning& tune, const InstanceRec* dInst, uint32_t numInst, const float4* dVertices, const uint32_t* dIndices, uint32_t numTris,
-                   TriRec* dTrisOut, AlphaRec* dAlphaOut, BvhNode* dNodesOut, WideNode* dWideOut, uint32_t* numWideOut, char* err, size_t errLen, const TriRec* dProxies,
-                   PtScratch* scratch, const PtForest* forest)
+                   TriRec* dTrisOut, AlphaRec* dAlphaOut, BvhNode* dNodesOut, WideNode* dWideOut, uint32_t* numWideOut, char* err, size_t errLen, PtScratch& scratch,
+                   const TriRec* dProxies, const PtForest* forest)
 {
   *numWideOut = 0;
   if(numTris == 0)
     return 0;
-  PtScratch  localScratch;
-  PtScratch& sc = scratch ? *scratch : localScratch;
-  const uint32_t n          = numTris;
-  const uint32_t sortBlocks = (n + SORT_ITEMS - 1) / SORT_ITEMS;
-  const int      B          = 256;
-  const uint32_t G          = (n + B - 1) / B;
-
-  TriRec*   dUnsorted = nullptr;
-  AlphaRec* dAlphaUnsorted = nullptr;
-  float4 *  dCen = nullptr, *dLeafLo = nullptr, *dLeafHi = nullptr, *dNodeLo = nullptr, *dNodeHi = nullptr;
-  uint32_t *dKeysA = nullptr, *dKeysB = nullptr, *dValsA = nullptr, *dValsB = nullptr, *dHist = nullptr, *dBounds = nullptr;
-  uint32_t *dChildL = nullptr, *dChildR = nullptr, *dParI = nullptr, *dParL = nullptr;
-  unsigned* dArrive = nullptr;
-  bool      sah     = false, ploc = false, sahDev = false;
-  uint32_t  initBounds[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-
-  HIPCHK(sc.get((void**)&dUnsorted, sizeof(TriRec) * size_t(n)));
-  HIPCHK(sc.get((void**)&dAlphaUnsorted, sizeof(AlphaRec) * size_t(n)));
-  HIPCHK(sc.get((void**)&dCen, sizeof(float4) * size_t(n)));
-  HIPCHK(sc.get((void**)&dLeafLo, sizeof(float4) * size_t(n)));
-  HIPCHK(sc.get((void**)&dLeafHi, sizeof(float4) * size_t(n)));
-  HIPCHK(sc.get((void**)&dNodeLo, sizeof(float4) * size_t(n)));
-  HIPCHK(sc.get((void**)&dNodeHi, sizeof(float4) * size_t(n)));
-  HIPCHK(sc.get((void**)&dKeysA, 4 * size_t(n)));
-  HIPCHK(sc.get((void**)&dKeysB, 4 * size_t(n)));
-  HIPCHK(sc.get((void**)&dValsA, 4 * size_t(n)));
-  HIPCHK(sc.get((void**)&dValsB, 4 * size_t(n)));
-  HIPCHK(sc.get((void**)&dHist, 4 * size_t(256) * sortBlocks));
-  HIPCHK(sc.get((void**)&dBounds, 4 * 6));
-  HIPCHK(sc.get((void**)&dChildL, 4 * size_t(n)));
-  HIPCHK(sc.get((void**)&dChildR, 4 * size_t(n)));
-  HIPCHK(sc.get((void**)&dParI, 4 * size_t(n)));
-  HIPCHK(sc.get((void**)&dParL, 4 * size_t(n)));
-  HIPCHK(sc.get((void**)&dArrive, 4 * size_t(n)));
-  HIPCHK(hipMemcpyAsync(dBounds, initBounds, sizeof(initBounds), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemsetAsync(dArrive, 0, 4 * size_t(n), stream));
-
-  if(dProxies)
-  {
-    HIPCHK(hipMemcpyAsync(dUnsorted, dProxies, sizeof(TriRec) * size_t(n), hipMemcpyDeviceToDevice, stream));
-    HIPCHK(hipMemsetAsync(dAlphaUnsorted, 0, sizeof(AlphaRec) * size_t(n), stream));
-    k_proxy_centroids<<<G, B, 0, stream>>>(n, dProxies, dCen, dBounds);
-  }
-  else
-    k_world_tris<<<G, B, 0, stream>>>(n, dInst, numInst, dVertices, dIndices, dUnsorted, dAlphaUnsorted, dCen, dBounds);
-  sah = tune.sahBuild == 1 && n >= 2;  // sahBuild: 0 device LBVH (Karras), 1 host SAH topology, 2 device PLOC, 3 device binned SAH (default)
-  ploc = tune.sahBuild == 2 && n >= 2;
-  sahDev = tune.sahBuild == 3 && n >= 2;
-  if(sahDev)
-  {
-    // ---- device binned SAH (pt_sahdev.h): level-synchronous; the number of open nodes comes back to the host between levels
-    float4 *  plo = nullptr, *phi = nullptr;
-    uint32_t *idxA = nullptr, *idxB = nullptr, *pwA = nullptr, *pwB = nullptr, *binCnt = nullptr, *binBox = nullptr, *dCounts = nullptr;
-    SdWork *  workA = nullptr, *workB = nullptr, *small = nullptr;
-    const size_t maxWork = size_t(n) / (SD_SMALL + 1) + 2, maxSmall = size_t(n) / 2 + 2;
-    bool      okAlloc = true;
-    auto      grab = [&](void** p, size_t bytes) { okAlloc = okAlloc && sc.get(p, bytes) == hipSuccess; };
-    grab((void**)&plo, 16 * size_t(n)); grab((void**)&phi, 16 * size_t(n)); grab((void**)&idxA, 4 * size_t(n)); grab((void**)&idxB, 4 * size_t(n)); grab((void**)&pwA, 4 * size_t(n));
-    grab((void**)&pwB, 4 * size_t(n)); grab((void**)&workA, sizeof(SdWork) * maxWork); grab((void**)&workB, sizeof(SdWork) * maxWork); grab((void**)&small, sizeof(SdWork) * maxSmall);
-    grab((void**)&binCnt, 4 * maxWork * 3 * SD_BINS); grab((void**)&binBox, 4 * maxWork * 3 * SD_BINS * 6); grab((void**)&dCounts, 8);
-    bool  done  = false;
-    if(okAlloc)
-    {
-      uint32_t nActive = 0, nSmall = 0;
-      SdWork   root;
-      sd_init_work(root, 0, n, 0);
-      uint32_t zero2[2] = {0u, 0u};
-      const uint32_t noneParent = BVH_NONE;
-      bool     ok = true;
-      if(forest)
-      {  // one root per hierarchy: the big ones open the first level's work list, the small ones go to the small-node list
-        std::vector<SdWork>   big, little;
-        std::vector<uint32_t> rootWork(forest->numRoots), rootNode(forest->numRoots);
-        for(uint32_t r = 0; r < forest->numRoots; ++r)
-        {
-          SdWork w;
-          sd_init_work(w, forest->first[r], forest->count[r], forest->first[r]);
-          rootNode[r] = forest->first[r];
-          if(forest->count[r] <= SD_SMALL)
-          {
-            rootWork[r] = SD_NONE;
-            little.push_back(w);
-          }
-          else
-          {
-            rootWork[r] = uint32_t(big.size());
-            big.push_back(w);
-          }
-        }
-        nActive  = uint32_t(big.size());
-        nSmall   = uint32_t(little.size());
-        zero2[1] = nSmall;
-        uint32_t *dRootWork = nullptr, *dRootNode = nullptr;
-        ok = nActive <= maxWork && nSmall <= maxSmall && sc.get((void**)&dRootWork, 4 * size_t(forest->numRoots)) == hipSuccess && sc.get((void**)&dRootNode, 4 * size_t(forest->numRoots)) == hipSuccess;
-        ok = ok && hipMemcpyAsync(dRootWork, rootWork.data(), 4 * rootWork.size(), hipMemcpyHostToDevice, stream) == hipSuccess &&
-             hipMemcpyAsync(dRootNode, rootNode.data(), 4 * rootNode.size(), hipMemcpyHostToDevice, stream) == hipSuccess;
-        if(ok && nActive)
-          ok = hipMemcpyAsync(workA, big.data(), sizeof(SdWork) * big.size(), hipMemcpyHostToDevice, stream) == hipSuccess;
-        if(ok && nSmall)
-          ok = hipMemcpyAsync(small, little.data(), sizeof(SdWork) * little.size(), hipMemcpyHostToDevice, stream) == hipSuccess;
-        // ids nobody owns (one per root: a root of k leaves uses k - 1 of its k ids) must still be readable by k_emit
-        ok = ok && hipMemsetAsync(dChildL, 0, 4 * size_t(n), stream) == hipSuccess && hipMemsetAsync(dChildR, 0, 4 * size_t(n), stream) == hipSuccess &&
-             hipMemsetAsync(dNodeLo, 0, 16 * size_t(n), stream) == hipSuccess && hipMemsetAsync(dNodeHi, 0, 16 * size_t(n), stream) == hipSuccess;
-        ok = ok && hipMemcpyAsync(dCounts, zero2, 8, hipMemcpyHostToDevice, stream) == hipSuccess;
-        if(ok)
-        {
-          k_sd_prims<<<G, B, 0, stream>>>(n, dUnsorted, plo, phi, idxA, pwA, SD_NONE);
-          k_forest_prim_work<<<G, B, 0, stream>>>(n, dUnsorted, dRootWork, pwA);
-          k_forest_roots<<<(forest->numRoots + 255) / 256, 256, 0, stream>>>(forest->numRoots, dRootNode, dParI);
-          ok = hipStreamSynchronize(stream) == hipSuccess;  // the host vectors above die with this scope
-        }
-      }
-      else
-      {
-      ok = hipMemcpyAsync(dParI, &noneParent, 4, hipMemcpyHostToDevice, stream) == hipSuccess;
-      if(n <= SD_SMALL)
-      {
-        nSmall   = 1;
-        zero2[1] = 1;
-        ok       = ok && hipMemcpyAsync(small, &root, sizeof(root), hipMemcpyHostToDevice, stream) == hipSuccess;
-      }
-      else
-      {
-        nActive = 1;
-        ok      = ok && hipMemcpyAsync(workA, &root, sizeof(root), hipMemcpyHostToDevice, stream) == hipSuccess;
-      }
-      ok = ok && hipMemcpyAsync(dCounts, zero2, 8, hipMemcpyHostToDevice, stream) == hipSuccess;
-      k_sd_prims<<<G, B, 0, stream>>>(n, dUnsorted, plo, phi, idxA, pwA, nActive ? 0u : SD_NONE);
-      }
-      int levels = 0;
-      while(nActive && ok && levels < 4096)
-      {
-        const size_t nBins = size_t(nActive) * 3 * SD_BINS;
-        k_sd_init_bins<<<unsigned((nBins + 255) / 256), 256, 0, stream>>>(nBins, binCnt, binBox);
-        if(levels == 0)  // deeper levels get their centroid bounds from their parents' partition pass
-          k_sd_cbounds<<<G, B, 0, stream>>>(n, idxA, pwA, workA, plo, phi);
-        k_sd_bin<<<G, B, 0, stream>>>(n, idxA, pwA, workA, plo, phi, binCnt, binBox);
-        (void)hipMemsetAsync(dCounts, 0, 4, stream);  // next-level counter; the small-node counter keeps running
-        SdLists L{workB, dCounts, small, dCounts + 1};
-        k_sd_split<<<(nActive + 63) / 64, 64, 0, stream>>>(nActive, workA, binCnt, binBox, L, dChildL, dChildR, dParI, dParL);
-        k_sd_partition<<<G, B, 0, stream>>>(n, idxA, pwA, workA, workB, plo, phi, idxB, pwB);
-        uint32_t counts[2] = {0u, 0u};
-        ok = hipMemcpyAsync(counts, dCounts, 8, hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess && counts[0] <= maxWork && counts[1] <= maxSmall;
-        nActive = counts[0];
-        nSmall  = counts[1];
-        std::swap(idxA, idxB); std::swap(pwA, pwB); std::swap(workA, workB);
-        ++levels;
-      }
-      if(ok && nActive == 0)
-      {
-        if(nSmall)
-          k_sd_small<<<(nSmall + 63) / 64, 64, 0, stream>>>(nSmall, small, idxA, plo, phi, dChildL, dChildR, dParI, dParL);
-        ok   = hipMemcpyAsync(dValsA, idxA, 4 * size_t(n), hipMemcpyDeviceToDevice, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess && hipGetLastError() == hipSuccess;
-        done = ok;
-      }
-    }
-    (void)hipGetLastError();
-    if(!done)
-    {
-      snprintf(err, errLen, "device SAH build failed (out of memory or a kernel error)");
-      goto fail;
-    }
-    sah = true;  // from here on like the host SAH builder: topology + leaf order are given
-  }
-  else
-  if(sah)
-  {
-    // cross-check build: SAH topology on the host from the world-space triangles (pt_sah.hip); boxes stay on the device
-    std::vector<TriRec>   hTris(n);
-    std::vector<uint32_t> hVals(n), hL(n), hR(n), hPI(n), hPL(n);
-    HIPCHK(hipMemcpyAsync(hTris.data(), dUnsorted, sizeof(TriRec) * size_t(n), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    pt_sah_topology(n, hTris.data(), hVals.data(), hL.data(), hR.data(), hPI.data(), hPL.data());
-    HIPCHK(hipMemcpyAsync(dValsA, hVals.data(), 4 * size_t(n), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(dChildL, hL.data(), 4 * size_t(n), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(dChildR, hR.data(), 4 * size_t(n), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(dParI, hPI.data(), 4 * size_t(n), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(dParL, hPL.data(), 4 * size_t(n), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream));  // the host vectors die at the end of this scope
-  }
-  else
-  {
-    k_morton<<<G, B, 0, stream>>>(n, dCen, dBounds, dKeysA, dValsA);
-    uint32_t *kin = dKeysA, *kout = dKeysB, *vin = dValsA, *vout = dValsB;
-    for(int pass = 0; pass < 4; ++pass)
-    {
-      int shift = pass * 8;
-      k_sort_hist<<<sortBlocks, 64, 0, stream>>>(kin, n, shift, dHist, sortBlocks);
-      k_sort_scan<<<1, 256, 0, stream>>>(dHist, 256u * sortBlocks);
-      k_sort_scatter<<<sortBlocks, 64, 0, stream>>>(kin, vin, kout, vout, n, shift, dHist, sortBlocks);
-      std::swap(kin, kout);
-      std::swap(vin, vout);
-    }
-    // after 4 passes the sorted data is back in A
-  }
-  k_gather<<<G, B, 0, stream>>>(n, dValsA, dUnsorted, dTrisOut, dAlphaUnsorted, dAlphaOut, dLeafLo, dLeafHi);
-  if(ploc)
-  {
-    // PLOC rounds; the cluster count comes back to the host between rounds (the build is not on the timed path).  A round merges at least the
-    // globally best pair; if an adversarial input makes the rounds crawl, the radix tree takes over.
-    uint32_t *cidA = nullptr, *cidB = nullptr, *dNn = nullptr, *dValid = nullptr, *dPos = nullptr, *dBlockSum = nullptr, *dCnt = nullptr;
-    float4 *  cloA = nullptr, *cloB = nullptr, *chiA = nullptr, *chiB = nullptr;
-    bool      okAlloc = true;
-    auto      grab = [&](void** p, size_t bytes) { okAlloc = okAlloc && sc.get(p, bytes) == hipSuccess; };
-    grab((void**)&cidA, 4 * size_t(n)); grab((void**)&cidB, 4 * size_t(n)); grab((void**)&dNn, 4 * size_t(n)); grab((void**)&dValid, 4 * size_t(n)); grab((void**)&dPos, 4 * size_t(n));
-    grab((void**)&dBlockSum, 4 * size_t((n + 1023) / 1024 + 1)); grab((void**)&dCnt, 8);
-    grab((void**)&cloA, 16 * size_t(n)); grab((void**)&cloB, 16 * size_t(n)); grab((void**)&chiA, 16 * size_t(n)); grab((void**)&chiB, 16 * size_t(n));
-    bool done = false;
-    if(okAlloc)
-    {
-      const int radius = PT_PLOC_RADIUS;
-      (void)hipMemsetAsync(dCnt, 0, 8, stream);
-      k_ploc_init<<<G, B, 0, stream>>>(n, dLeafLo, dLeafHi, cidA, cloA, chiA);
-      uint32_t m = n;
-      int      rounds = 0, maxRounds = 64;
-      for(uint32_t t = n; t > 1; t >>= 1)
-        maxRounds += 6;
-      bool ok = true;
-      while(m > 1 && rounds < maxRounds && ok)
-      {
-        const uint32_t g = (m + 255) / 256, nb = (m + 1023) / 1024;
-        // the top of the tree decides how many subtrees a ray enters: once few clusters are left every cluster considers ALL others
-        // (exact agglomerative clustering), not just its Morton neighbourhood
-        const int rad = radius;
-        k_ploc_nn<<<g, 256, 0, stream>>>(m, rad, cloA, chiA, dNn);
-        k_ploc_merge<<<g, 256, 0, stream>>>(m, n - 1, dNn, cidA, cloA, chiA, dValid, dCnt, dChildL, dChildR, dParI, dParL, dNodeLo, dNodeHi);
-        k_ploc_scan_blocks<<<nb, 1024, 0, stream>>>(m, dValid, dPos, dBlockSum);
-        k_ploc_scan_sums<<<1, 1024, 0, stream>>>(nb, dBlockSum, dCnt + 1);
-        k_ploc_compact<<<g, 256, 0, stream>>>(m, dValid, dPos, dBlockSum, cidA, cloA, chiA, cidB, cloB, chiB);
-        uint32_t m2 = 0;
-        ok = hipMemcpyAsync(&m2, dCnt + 1, 4, hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess && m2 >= 1 && m2 < m;
-        m = m2;
-        std::swap(cidA, cidB); std::swap(cloA, cloB); std::swap(chiA, chiB);
-        ++rounds;
-      }
-      done = ok && m == 1;
-      if(done)
-      {
-        const uint32_t none = BVH_NONE;
-        (void)hipMemcpyAsync(dParI, &none, 4, hipMemcpyHostToDevice, stream);  // the root (node 0) has no parent
-      }
-    }
-    (void)hipGetLastError();
-    if(!done)
-      ploc = false;  // fall back to the radix tree below
-  }
-  if(n == 1)
-  {
-    k_single_leaf<<<1, 1, 0, stream>>>(dLeafLo, dLeafHi, dTrisOut, dNodesOut);
-  }
-  else
-  {
-    if(!sah && !ploc)
-      k_hierarchy<<<G, B, 0, stream>>>(int(n), dKeysA, dChildL, dChildR, dParI, dParL);
-    if(!ploc)  // PLOC wrote the inner boxes while merging
-      k_refit<<<G, B, 0, stream>>>(int(n), dChildL, dChildR, dParI, dParL, dLeafLo, dLeafHi, dNodeLo, dNodeHi, dArrive);
-    for(int pass = 0; pass < PT_ROTATE_PASSES && !sah; ++pass)
-    {
-      (void)hipMemsetAsync(dArrive, 0, 4 * size_t(n), stream);
-      k_rotate<<<G, B, 0, stream>>>(int(n), dChildL, dChildR, dParI, dParL, dLeafLo, dLeafHi, dNodeLo, dNodeHi, dArrive);
-    }
-    k_emit<<<(n - 1 + B - 1) / B, B, 0, stream>>>(int(n - 1), dChildL, dChildR, dLeafLo, dLeafHi, dNodeLo, dNodeHi, dTrisOut, dNodesOut, forest ? forest->leafOffset : 0u);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(stream));
-  if(forest && !sahDev)
-  {
-    snprintf(err, errLen, "a forest is built by the device SAH builder only");
-    goto fail;
-  }
-
-  // ---- collapse to the wide layout, one BVH level per launch (the queue sizes come back to the host between levels;
-  // the build is not on the timed path)
-  {
-    CollapseItem* dQ[2] = {nullptr, nullptr};
-    uint32_t*     dCnt  = nullptr;
-    HIPCHK(sc.get((void**)&dQ[0], sizeof(CollapseItem) * size_t(n)));
-    HIPCHK(sc.get((void**)&dQ[1], sizeof(CollapseItem) * size_t(n)));
-    HIPCHK(sc.get((void**)&dCnt, 8));
-    CollapseItem first{0u, 0u, 0u};
-    uint32_t     cnt[2] = {0u, 1u};  // next-queue size, wide nodes allocated (root = 0)
-    uint32_t     nIn = 1;
-    uint32_t *   dRootCount = nullptr, *dRootBase = nullptr;
-    if(forest)
-    {  // every root starts a queue entry of its own: binary root first[r] becomes wide node wideBase[r], its descendants are allocated behind it
-      std::vector<CollapseItem> roots(forest->numRoots);
-      std::vector<uint32_t>     ones(forest->numRoots, 1u);
-      for(uint32_t r = 0; r < forest->numRoots; ++r)
-        roots[r] = CollapseItem{forest->first[r], forest->wideBase[r], r};
-      HIPCHK(sc.get((void**)&dRootCount, 4 * size_t(forest->numRoots)));
-      HIPCHK(sc.get((void**)&dRootBase, 4 * size_t(forest->numRoots)));
-      HIPCHK(hipMemcpyAsync(dQ[0], roots.data(), sizeof(CollapseItem) * roots.size(), hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(dRootCount, ones.data(), 4 * ones.size(), hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(dRootBase, forest->wideBase, 4 * size_t(forest->numRoots), hipMemcpyHostToDevice, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      nIn = forest->numRoots;
-    }
-    else
-      HIPCHK(hipMemcpyAsync(dQ[0], &first, sizeof(first), hipMemcpyHostToDevice, stream));
-    int      cur = 0;
-    bool     ok  = true;
-    while(nIn && ok)
-    {
-      HIPCHK(hipMemcpyAsync(dCnt, cnt, 8, hipMemcpyHostToDevice, stream));
-      k_collapse<<<(nIn + 63) / 64, 64, 0, stream>>>(dNodesOut, dQ[cur], nIn, dQ[cur ^ 1], dCnt, dWideOut, dRootCount, dRootBase);
-      HIPCHK(hipMemcpyAsync(cnt, dCnt, 8, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      nIn    = cnt[0];
-      cnt[0] = 0;
-      cur ^= 1;
-    }
-    *numWideOut = cnt[1];
-    if(forest)
-    {
-      HIPCHK(hipMemcpyAsync(forest->numWide, dRootCount, 4 * size_t(forest->numRoots), hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      uint32_t total = 0;
-      for(uint32_t r = 0; r < forest->numRoots; ++r)
-        total += forest->numWide[r];
-      *numWideOut = total;
-    }
-  }
-
-  sc.release();
-  return 0;
-fail:
-  (void)hipStreamSynchronize(stream);  // nothing of this build may still be running when the arena is reused
-  sc.release();
-  return -1;
+  // a single primitive has no topology to choose: it takes the radix-tree stages, which end in k_single_leaf
+  const PtBuilder builder = numTris >= 2 && tune.sahBuild >= PT_BUILD_LBVH && tune.sahBuild <= PT_BUILD_SAHDEV ? PtBuilder(tune.sahBuild) : PT_BUILD_LBVH;
+  Build b{stream, scratch, numTris, (numTris + kBlock - 1) / kBlock, err, errLen, dTrisOut, dAlphaOut, dNodesOut, dWideOut};
+  if(forest && builder != PT_BUILD_SAHDEV)  // forest builder: refused before anything is launched
+    return b.fail("a forest is built by the device SAH builder only");
+  const PtScratch::Mark mark = scratch.mark();
+  int                   rc   = shared_lists(b);
+  rc = rc ? rc : primitives(b, dInst, numInst, dVertices, dIndices, dProxies);
+  rc = rc ? rc : binary_tree(b, builder, forest);
+  rc = rc ? rc : collapse_to_wide(b, forest, numWideOut);
+  // the stream is drained here: the last stage ends in a synchronisation, and a failing stage drains before it returns (Build::fail)
+  scratch.rewind(mark);
+  return rc;
 }
 
 // ---- two-level structure: the builds -------------------------------------------------------------------------------------------------
-// Every BLAS is an ordinary pt_accel_build over ONE pseudo-instance with the identity transform (object space), written at its bases in the
+// Every BLAS is an ordinary pt_accel_build over pseudo-instances with the identity transform (object space), written at its bases in the
 // shared arrays; then its leaf records are turned into vertex form and its references made global.
-int pt_blas_build(hipStream_t stream, const PtTuning& tune, PtBlasDesc* blas, uint32_t numBlas, const float4* dVertices, const uint32_t* dIndices, TriRec* dTris, AlphaRec* dAlpha, WideNode* dWide,
-                  char* err, size_t errLen)
+namespace {
+
+// A driver's failing exit: the reason (null: err holds it already), then draining before the driver's scratch goes.  Returns -1.
+int driver_fail(hipStream_t stream, char* err, size_t errLen, const char* who, const char* why)
 {
-  if(numBlas == 0)
-    return 0;
-  uint32_t maxTris = 1;
-  for(uint32_t b = 0; b < numBlas; ++b)
-    maxTris = std::max(maxTris, blas[b].triCount);
+  if(why)
+    snprintf(err, errLen, "%s: %s", who, why);
+  (void)hipStreamSynchronize(stream);
+  return -1;
+}
+
+// the scene's arrays the bottom-level builds read and write
+struct BlasArrays {
+  const float4*   vertices;
+  const uint32_t* indices;
+  TriRec*         tris;
+  AlphaRec*       alpha;
+  WideNode*       wide;
+};
+
+bool wide_count_ok(const PtBlasDesc& d) { return d.numWide > 0 && d.numWide <= std::max(1u, d.triCount - 1); }
+
+// one identity-transform instance per mesh, its triangles numbered from 0
+std::vector<InstanceRec> pseudo_instances(const PtBlasDesc* blas, uint32_t numBlas)
+{
   std::vector<InstanceRec> pseudo(numBlas);
   for(uint32_t b = 0; b < numBlas; ++b)
   {
@@ -1458,177 +1517,186 @@ int pt_blas_build(hipStream_t stream, const PtTuning& tune, PtBlasDesc* blas, ui
     I.triCount      = blas[b].triCount;
     I.flags         = blas[b].flags & ~TRI_FLIP;
   }
-  InstanceRec* dPseudo = nullptr;
-  int          device  = 0;
+  return pseudo;
+}
+
+// One forest: the meshes `ids` (contiguous in the slot range, two triangles or more each) in one level-synchronous pass with a root per mesh.
+// False with the reason in msg when anything stopped it.  That failure is soft: the stream is drained before the scratch goes and the HIP error is
+// cleared, and the caller hands the meshes to the per-mesh path, which rewrites everything the attempt may have left in their ranges.
+bool build_forest_run(hipStream_t stream, const PtTuning& tune, PtBlasDesc* blas, const std::vector<uint32_t>& ids, const std::vector<InstanceRec>& pseudo, const BlasArrays& A, char* msg,
+                      size_t msgLen)
+{
+  const uint32_t           slot0 = blas[ids.front()].slotBase;
+  uint32_t                 nF    = 0;
+  std::vector<uint32_t>    first(ids.size()), count(ids.size()), wideBase(ids.size()), numWide(ids.size(), 0u);
+  std::vector<InstanceRec> pf(ids.size());
+  for(size_t q = 0; q < ids.size(); ++q)
+  {
+    const PtBlasDesc& d = blas[ids[q]];
+    first[q] = d.slotBase - slot0; count[q] = d.triCount; wideBase[q] = d.nodeBase;
+    pf[q]         = pseudo[ids[q]];
+    pf[q].triBase = first[q];
+    nF += d.triCount;
+  }
+  PtScratch    sc;
+  InstanceRec* dPf    = nullptr;
+  BvhNode*     dNodes = nullptr;
+  uint32_t     total  = 0;
+  auto         give_up = [&](const char* why) {
+    driver_fail(stream, msg, msgLen, "forest", why);
+    (void)hipGetLastError();
+    return false;
+  };
+  if(!(sc.keep(dPf, pf.size()) && sc.keep(dNodes, nF)))
+    return give_up("out of device memory");
+  if(hipMemcpyAsync(dPf, pf.data(), sizeof(InstanceRec) * pf.size(), hipMemcpyHostToDevice, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+    return give_up("upload failed");
+  sc.reserve(pt_scratch_bytes(tune, nF, true));
+  PtForest F{uint32_t(ids.size()), first.data(), count.data(), wideBase.data(), slot0, numWide.data()};
+  if(pt_accel_build(stream, tune, dPf, uint32_t(pf.size()), A.vertices, A.indices, nF, A.tris + slot0, A.alpha + slot0, dNodes, A.wide, &total, msg, msgLen, sc, nullptr, &F) != 0)
+    return give_up(nullptr);
+  k_forest_vertex_form<<<(nF + 255) / 256, 256, 0, stream>>>(nF, A.tris + slot0, dPf, A.vertices, A.indices);
+  if(hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess)
+    return give_up("a kernel failed");
+  for(size_t q = 0; q < ids.size(); ++q)
+  {
+    PtBlasDesc& d = blas[ids[q]];
+    d.numWide     = numWide[q];
+    if(!wide_count_ok(d))  // numWide bound check: 0 < numWide <= max(1, n - 1)
+    {
+      snprintf(msg, msgLen, "BLAS %u: %u wide nodes for %u triangles", ids[q], d.numWide, d.triCount);
+      return give_up(nullptr);
+    }
+  }
+  return true;
+}
+
+// what the per-mesh workers share
+struct BlasJob {
+  const PtTuning&          tune;
+  PtBlasDesc*              blas;
+  uint32_t                 numBlas, maxTris;
+  const InstanceRec*       dPseudo;
+  const std::vector<char>& done;  // built in a forest
+  BlasArrays               A;
+  int                      device;
+  char*                    err;  // of the first worker that failed
+  size_t                   errLen;
+  std::atomic<uint32_t>    next{0};
+  std::atomic<int>         failed{0};
+  std::mutex               errLock;
+};
+
+// A build is a chain of small level-synchronous launches with a host round trip per level: one mesh alone leaves the GPU and the host idle
+// most of the time.  A few host threads, each with its own stream, arena and binary-node scratch, take the meshes from a shared counter
+// (largest first would balance better; the meshes of a scene are usually of similar size).  A failure here is an error: the first one is reported.
+void blas_worker(BlasJob& J)
+{
+  (void)hipSetDevice(J.device);
+  hipStream_t ws     = nullptr;
+  BvhNode*    dNodes = nullptr;
+  PtScratch   sc;  // dNodes is kept below the mark of every build that reuses the arena
+  char        msg[256] = "";
+  bool        ok = hipStreamCreateWithFlags(&ws, hipStreamNonBlocking) == hipSuccess && sc.keep(dNodes, J.maxTris);
+  if(!ok)
+    snprintf(msg, sizeof(msg), "BLAS build: out of device memory");
+  else
+    sc.reserve(pt_scratch_bytes(J.tune, J.maxTris, false));
+  while(ok && !J.failed.load())
+  {
+    const uint32_t b = J.next.fetch_add(1);
+    if(b >= J.numBlas)
+      break;
+    if(J.done[b])
+      continue;
+    PtBlasDesc&    d = J.blas[b];
+    const uint32_t n = d.triCount;
+    ok = pt_accel_build(ws, J.tune, J.dPseudo + b, 1, J.A.vertices, J.A.indices, n, J.A.tris + d.slotBase, J.A.alpha + d.slotBase, dNodes, J.A.wide + d.nodeBase, &d.numWide, msg, sizeof(msg), sc) == 0;
+    if(ok && !wide_count_ok(d))  // numWide bound check: 0 < numWide <= max(1, n - 1)
+    {
+      snprintf(msg, sizeof(msg), "BLAS %u: %u wide nodes for %u triangles", b, d.numWide, n);
+      ok = false;
+    }
+    if(!ok)
+      break;
+    k_blas_vertex_form<<<(n + 255) / 256, 256, 0, ws>>>(n, J.A.tris + d.slotBase, J.A.vertices, J.A.indices, d.vertexOffset, d.firstIndex);
+    k_blas_rebase<<<(d.numWide + 255) / 256, 256, 0, ws>>>(d.numWide, J.A.wide + d.nodeBase, d.nodeBase, d.slotBase);
+  }
+  // draining before the scratch goes, on every path
+  if(ws && (hipStreamSynchronize(ws) != hipSuccess || hipGetLastError() != hipSuccess) && ok)
+  {
+    snprintf(msg, sizeof(msg), "BLAS build: a kernel failed");
+    ok = false;
+  }
+  if(!ok)
+  {
+    std::lock_guard<std::mutex> g(J.errLock);
+    if(!J.failed.exchange(1))
+      snprintf(J.err, J.errLen, "%s", msg);
+  }
+  if(ws)
+    (void)hipStreamDestroy(ws);
+}
+
+}  // namespace
+
+int pt_blas_build(hipStream_t stream, const PtTuning& tune, PtBlasDesc* blas, uint32_t numBlas, const float4* dVertices, const uint32_t* dIndices, TriRec* dTris, AlphaRec* dAlpha, WideNode* dWide,
+                  char* err, size_t errLen)
+{
+  if(numBlas == 0)
+    return 0;
+  const BlasArrays               A{dVertices, dIndices, dTris, dAlpha, dWide};
+  const std::vector<InstanceRec> pseudo = pseudo_instances(blas, numBlas);
+  PtScratch                      sc;  // outlives the workers
+  InstanceRec*                   dPseudo = nullptr;
+  int                            device  = 0;
   (void)hipGetDevice(&device);
-  if(hipMalloc(&dPseudo, sizeof(InstanceRec) * size_t(numBlas)) != hipSuccess)
+  if(!sc.keep(dPseudo, numBlas))
   {
     snprintf(err, errLen, "BLAS build: out of device memory");
     return -1;
   }
   if(hipMemcpyAsync(dPseudo, pseudo.data(), sizeof(InstanceRec) * size_t(numBlas), hipMemcpyHostToDevice, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
   {
-    (void)hipFree(dPseudo);
     snprintf(err, errLen, "BLAS build: upload failed");
     return -1;
   }
-  // Round 6: with the device SAH builder ALL meshes of two or more triangles are built as one forest -- one level-synchronous pass over the concatenated
+  // Round 6: with the device SAH builder ALL meshes of two or more triangles are built as forests -- one level-synchronous pass over the concatenated
   // triangles with a root per mesh (pt_internal.h PtForest) instead of one build and ~20 host round trips per mesh (C5 stand-in, 201 meshes: the two-level build 172 -> 70 ms, profiles/r06_forest_build.txt).
-  // The arrays' layout is unchanged: mesh b's leaf records at slotBase, its wide nodes from nodeBase on, references global.  What is left for the per-mesh
-  // path below: one-triangle meshes, and every mesh under the other builders (build=sah|ploc|lbvh).
+  // The arrays' layout is unchanged: mesh b's leaf records at slotBase, its wide nodes from nodeBase on, references global.  A forest wants its meshes
+  // contiguous in the slot range (build_two_level hands out slotBase in order): every maximal run of two or more meshes with at least two triangles each
+  // is one forest.  What is left for the per-mesh path: one-triangle meshes, every mesh under the other builders (build=sah|ploc|lbvh), and -- the forest
+  // fallback -- the meshes of a run that failed: a forest is an optimisation, whatever stopped it.
   std::vector<char> done(numBlas, 0);
-  if(tune.sahBuild == 3)
+  for(uint32_t runStart = 0; runStart < numBlas && tune.sahBuild == PT_BUILD_SAHDEV;)
   {
-    // a forest wants its meshes contiguous in the slot range (build_two_level hands out slotBase in order): every maximal run of two or more meshes with
-    // at least two triangles each is one forest; what lies between the runs (one-triangle meshes) takes the per-mesh path
-    for(uint32_t runStart = 0; runStart < numBlas;)
-    {
-      std::vector<uint32_t> ids;
-      uint32_t              b = runStart;
-      while(b < numBlas && blas[b].triCount >= 2 && (ids.empty() || blas[b].slotBase == blas[b - 1].slotBase + blas[b - 1].triCount))
-        ids.push_back(b++);
-      runStart = ids.empty() ? b + 1 : b;
-      if(ids.size() >= 2)
-      {
-        const uint32_t b0 = ids.front(), slot0 = blas[b0].slotBase;
-        uint32_t       nF = 0;
-        std::vector<uint32_t> first(ids.size()), count(ids.size()), wideBase(ids.size()), numWide(ids.size(), 0u);
-        std::vector<InstanceRec> pf(ids.size());
-        for(size_t q = 0; q < ids.size(); ++q)
-        {
-          const PtBlasDesc& d = blas[ids[q]];
-          first[q] = d.slotBase - slot0; count[q] = d.triCount; wideBase[q] = d.nodeBase;
-          pf[q]         = pseudo[ids[q]];
-          pf[q].triBase = first[q];
-          nF += d.triCount;
-        }
-        InstanceRec* dPf    = nullptr;
-        BvhNode*     dNodes = nullptr;
-        PtScratch    arena;
-        uint32_t     total = 0;
-        char         msg[256] = "";
-        bool ok = hipMalloc(&dPf, sizeof(InstanceRec) * pf.size()) == hipSuccess && hipMalloc(&dNodes, sizeof(BvhNode) * size_t(nF)) == hipSuccess &&
-                  hipMemcpyAsync(dPf, pf.data(), sizeof(InstanceRec) * pf.size(), hipMemcpyHostToDevice, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
-        const size_t arenaBytes = size_t(nF) * 704 + (size_t(4) << 20);
-        if(ok && hipMalloc((void**)&arena.base, arenaBytes) == hipSuccess)
-          arena.cap = arenaBytes;
-        else
-        {
-          arena.base = nullptr;
-          (void)hipGetLastError();
-        }
-        if(ok)
-        {
-          PtForest F{uint32_t(ids.size()), first.data(), count.data(), wideBase.data(), slot0, numWide.data()};
-          ok = pt_accel_build(stream, tune, dPf, uint32_t(pf.size()), dVertices, dIndices, nF, dTris + slot0, dAlpha + slot0, dNodes, dWide, &total, msg, sizeof(msg), nullptr, &arena, &F) == 0;
-        }
-        if(ok)
-        {
-          k_forest_vertex_form<<<(nF + 255) / 256, 256, 0, stream>>>(nF, dTris + slot0, dPf, dVertices, dIndices);
-          ok = hipStreamSynchronize(stream) == hipSuccess && hipGetLastError() == hipSuccess;
-        }
-        for(size_t q = 0; q < ids.size() && ok; ++q)
-        {
-          PtBlasDesc& d = blas[ids[q]];
-          d.numWide     = numWide[q];
-          done[ids[q]]  = 1;
-          if(d.numWide == 0 || d.numWide > std::max(1u, d.triCount - 1))
-          {
-            snprintf(msg, sizeof(msg), "BLAS %u: %u wide nodes for %u triangles", ids[q], d.numWide, d.triCount);
-            ok = false;
-          }
-        }
-        arena.release();
-        if(arena.base)
-          (void)hipFree(arena.base);
-        (void)hipFree(dPf);
-        (void)hipFree(dNodes);
-        if(!ok)
-        {  // the forest is an optimisation: whatever stopped it (memory for its arena, a failed launch), these meshes take the per-mesh path below, which
-           // rewrites everything the attempt may have left in their ranges
-          (void)hipStreamSynchronize(stream);
-          (void)hipGetLastError();
-          for(uint32_t q : ids)
-            done[q] = 0;
-        }
-      }
-    }
+    std::vector<uint32_t> ids;
+    uint32_t              b = runStart;
+    while(b < numBlas && blas[b].triCount >= 2 && (ids.empty() || blas[b].slotBase == blas[b - 1].slotBase + blas[b - 1].triCount))
+      ids.push_back(b++);
+    runStart = ids.empty() ? b + 1 : b;
+    if(ids.size() < 2)
+      continue;
+    char       msg[256] = "";
+    const bool ok       = build_forest_run(stream, tune, blas, ids, pseudo, A, msg, sizeof(msg));
+    for(uint32_t q : ids)
+      done[q] = ok;
+    static std::atomic<bool> warned{false};
+    if(!ok && !warned.exchange(true))
+      fprintf(stderr, "libptmi: a forest build of %zu meshes fell back to one build per mesh (reported once): %s\n", ids.size(), msg);
   }
-  // A build is a chain of small level-synchronous launches with a host round trip per level: one mesh alone leaves the GPU and the host idle
-  // most of the time.  A few host threads, each with its own stream, arena and binary-node scratch, take the meshes from a shared counter
-  // (largest first would balance better; the meshes of a scene are usually of similar size).
-  const unsigned       numWorkers = std::max(1u, std::min(std::min(numBlas, 16u), uint32_t(tune.blasWorkers > 0 ? tune.blasWorkers : 1)));
-  std::atomic<uint32_t> next{0};
-  std::atomic<int>      failed{0};
-  std::mutex            errLock;
-  auto                  worker = [&](unsigned w) {
-    (void)hipSetDevice(device);
-    hipStream_t ws = nullptr;
-    BvhNode*    dNodes = nullptr;
-    PtScratch   arena;
-    char        msg[256] = "";
-    bool        ok = hipStreamCreateWithFlags(&ws, hipStreamNonBlocking) == hipSuccess && hipMalloc(&dNodes, sizeof(BvhNode) * size_t(maxTris)) == hipSuccess;
-    if(!ok)
-      snprintf(msg, sizeof(msg), "BLAS build: out of device memory");
-    // temporaries of one build: < 640 B per triangle (pt_accel_build's lists + the SAH builder's bins); whatever does not fit is allocated singly
-    const size_t arenaBytes = size_t(maxTris) * 640 + (size_t(1) << 20);
-    if(ok && hipMalloc((void**)&arena.base, arenaBytes) == hipSuccess)
-      arena.cap = arenaBytes;
-    else
-    {
-      arena.base = nullptr;  // no arena: every temporary is its own allocation
-      (void)hipGetLastError();
-    }
-    while(ok && !failed.load())
-    {
-      const uint32_t b = next.fetch_add(1);
-      if(b >= numBlas)
-        break;
-      if(done[b])
-        continue;  // built in the forest above
-      PtBlasDesc&    d = blas[b];
-      const uint32_t n = d.triCount;
-      if(pt_accel_build(ws, tune, dPseudo + b, 1, dVertices, dIndices, n, dTris + d.slotBase, dAlpha + d.slotBase, dNodes, dWide + d.nodeBase, &d.numWide, msg, sizeof(msg), nullptr, &arena) != 0)
-      {
-        ok = false;
-        break;
-      }
-      if(d.numWide == 0 || d.numWide > std::max(1u, n - 1))
-      {
-        snprintf(msg, sizeof(msg), "BLAS %u: %u wide nodes for %u triangles", b, d.numWide, n);
-        ok = false;
-        break;
-      }
-      k_blas_vertex_form<<<(n + 255) / 256, 256, 0, ws>>>(n, dTris + d.slotBase, dVertices, dIndices, d.vertexOffset, d.firstIndex);
-      k_blas_rebase<<<(d.numWide + 255) / 256, 256, 0, ws>>>(d.numWide, dWide + d.nodeBase, d.nodeBase, d.slotBase);
-    }
-    if(ws && (hipStreamSynchronize(ws) != hipSuccess || hipGetLastError() != hipSuccess) && ok)
-    {
-      snprintf(msg, sizeof(msg), "BLAS build: a kernel failed");
-      ok = false;
-    }
-    if(!ok)
-    {
-      std::lock_guard<std::mutex> g(errLock);
-      if(!failed.exchange(1))
-        snprintf(err, errLen, "%s", msg);
-    }
-    arena.release();
-    if(arena.base)
-      (void)hipFree(arena.base);
-    if(dNodes)
-      (void)hipFree(dNodes);
-    if(ws)
-      (void)hipStreamDestroy(ws);
-  };
+  uint32_t maxTris = 1;
+  for(uint32_t b = 0; b < numBlas; ++b)
+    maxTris = std::max(maxTris, blas[b].triCount);
+  BlasJob        J{tune, blas, numBlas, maxTris, dPseudo, done, A, device, err, errLen};
+  const unsigned numWorkers = std::max(1u, std::min(std::min(numBlas, 16u), uint32_t(tune.blasWorkers > 0 ? tune.blasWorkers : 1)));
   std::vector<std::thread> threads;
   for(unsigned w = 1; w < numWorkers; ++w)
-    threads.emplace_back(worker, w);
-  worker(0);
+    threads.emplace_back(blas_worker, std::ref(J));
+  blas_worker(J);
   for(std::thread& t : threads)
     t.join();
-  (void)hipFree(dPseudo);
-  return failed.load() ? -1 : 0;
+  return J.failed.load() ? -1 : 0;
 }
 
 // WideNode -> CompactNode (pt_cnode.h cn_encode), one thread per node.  bad[0] counts nodes that cannot be represented (non-finite boxes): the
@@ -1755,61 +1823,34 @@ int pt_merged_build(hipStream_t stream, const PtTuning& tune, const InstanceRec*
                     const uint32_t* dIndices, TriRec* dTris, AlphaRec* dAlpha, WideNode* dWide, uint32_t slotBase, uint32_t nodeBase, uint32_t* numWideOut, float* boxOut6, char* err,
                     size_t errLen)
 {
-  InstanceRec* dInst = nullptr;
-  uint32_t*    dIds  = nullptr;
+  PtScratch    sc;
+  InstanceRec* dInst  = nullptr;
+  uint32_t*    dIds   = nullptr;  // ids, then world bases
   BvhNode*     dNodes = nullptr;
-  PtScratch    arena;
-  int          rc = -1;
   BvhNode      root{};
-  const size_t arenaBytes = size_t(numTris) * 640 + (size_t(1) << 20);
-  if(hipMalloc(&dInst, sizeof(InstanceRec) * size_t(numInst)) != hipSuccess || hipMalloc(&dIds, 8 * size_t(numInst)) != hipSuccess ||
-     hipMalloc(&dNodes, sizeof(BvhNode) * size_t(std::max(1u, numTris))) != hipSuccess)
-  {
-    snprintf(err, errLen, "merged BLAS build: out of device memory");
-    goto done;
-  }
-  if(hipMalloc((void**)&arena.base, arenaBytes) == hipSuccess)
-    arena.cap = arenaBytes;
-  else
-  {
-    arena.base = nullptr;
-    (void)hipGetLastError();
-  }
+  auto fail = [&](const char* why) { return driver_fail(stream, err, errLen, "merged BLAS build", why); };
+  if(!(sc.keep(dInst, numInst) && sc.keep(dIds, 2 * size_t(numInst)) && sc.keep(dNodes, std::max(1u, numTris))))
+    return fail("out of device memory");
+  sc.reserve(pt_scratch_bytes(tune, numTris, false));
   if(hipMemcpyAsync(dInst, hInst, sizeof(InstanceRec) * size_t(numInst), hipMemcpyHostToDevice, stream) != hipSuccess ||
      hipMemcpyAsync(dIds, hIds, 4 * size_t(numInst), hipMemcpyHostToDevice, stream) != hipSuccess ||
      hipMemcpyAsync(dIds + numInst, hWorldBase, 4 * size_t(numInst), hipMemcpyHostToDevice, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-  {
-    snprintf(err, errLen, "merged BLAS build: upload failed");
-    goto done;
-  }
-  if(pt_accel_build(stream, tune, dInst, numInst, dVertices, dIndices, numTris, dTris + slotBase, dAlpha + slotBase, dNodes, dWide + nodeBase, numWideOut, err, errLen, nullptr, &arena) != 0)
-    goto done;
+    return fail("upload failed");
+  if(pt_accel_build(stream, tune, dInst, numInst, dVertices, dIndices, numTris, dTris + slotBase, dAlpha + slotBase, dNodes, dWide + nodeBase, numWideOut, err, errLen, sc) != 0)
+    return fail(nullptr);
   k_merged_identity<<<(numTris + 255) / 256, 256, 0, stream>>>(numTris, dTris + slotBase, dIds, dIds + numInst);
   k_blas_rebase<<<(*numWideOut + 255) / 256, 256, 0, stream>>>(*numWideOut, dWide + nodeBase, nodeBase, slotBase);
   if(hipMemcpyAsync(&root, dNodes, sizeof(BvhNode), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess)
+    return fail("a kernel failed");
+  // world box = union of the binary root's child boxes (one child when the structure is a single triangle)
+  const bool  two   = numTris > 1 && root.d.y != BVH_NONE;
+  const float l[6]  = {root.a.x, root.a.y, root.a.z, root.a.w, root.b.x, root.b.y}, r[6] = {root.b.z, root.b.w, root.c.x, root.c.y, root.c.z, root.c.w};
+  for(int k = 0; k < 3; ++k)
   {
-    snprintf(err, errLen, "merged BLAS build: a kernel failed");
-    goto done;
+    boxOut6[k]     = two ? std::min(l[k], r[k]) : l[k];
+    boxOut6[3 + k] = two ? std::max(l[3 + k], r[3 + k]) : l[3 + k];
   }
-  {  // world box = union of the binary root's child boxes (one child when the structure is a single triangle)
-    const bool  two   = numTris > 1 && root.d.y != BVH_NONE;
-    const float l[6]  = {root.a.x, root.a.y, root.a.z, root.a.w, root.b.x, root.b.y}, r[6] = {root.b.z, root.b.w, root.c.x, root.c.y, root.c.z, root.c.w};
-    for(int k = 0; k < 3; ++k)
-    {
-      boxOut6[k]     = two ? std::min(l[k], r[k]) : l[k];
-      boxOut6[3 + k] = two ? std::max(l[3 + k], r[3 + k]) : l[3 + k];
-    }
-  }
-  rc = 0;
-done:
-  (void)hipStreamSynchronize(stream);
-  arena.release();
-  if(arena.base)
-    (void)hipFree(arena.base);
-  if(dInst) (void)hipFree(dInst);
-  if(dIds) (void)hipFree(dIds);
-  if(dNodes) (void)hipFree(dNodes);
-  return rc;
+  return 0;
 }
 
 int pt_tlas_build(hipStream_t stream, const PtTuning& tune, const InstanceRec* dInst, const uint32_t* dActive, uint32_t numActive, const uint32_t* dInstNodeBase, const float* dInstPad,
@@ -1820,16 +1861,13 @@ int pt_tlas_build(hipStream_t stream, const PtTuning& tune, const InstanceRec* d
   const uint32_t n = numActive + (mergedBox ? 1u : 0u);  // the merged structure is one more primitive of the TLAS
   if(n == 0)
     return 0;
-  TriRec *       dProx = nullptr, *dLeafOrder = nullptr;
-  AlphaRec*      dAlpha = nullptr;
-  BvhNode*       dNodes = nullptr;
-  int            rc = -1;
-  if(hipMalloc(&dProx, sizeof(TriRec) * size_t(n)) != hipSuccess || hipMalloc(&dLeafOrder, sizeof(TriRec) * size_t(n)) != hipSuccess ||
-     hipMalloc(&dAlpha, sizeof(AlphaRec) * size_t(n)) != hipSuccess || hipMalloc(&dNodes, sizeof(BvhNode) * size_t(n)) != hipSuccess)
-  {
-    snprintf(err, errLen, "TLAS build: out of device memory");
-    goto done;
-  }
+  PtScratch sc;  // no arena: a TLAS is one small build
+  TriRec *  dProx = nullptr, *dLeafOrder = nullptr;
+  AlphaRec* dAlpha = nullptr;
+  BvhNode*  dNodes = nullptr;
+  auto fail = [&](const char* why) { return driver_fail(stream, err, errLen, "TLAS build", why); };
+  if(!(sc.keep(dProx, n) && sc.keep(dLeafOrder, n) && sc.keep(dAlpha, n) && sc.keep(dNodes, n)))
+    return fail("out of device memory");
   if(numActive)
     k_instance_proxies<<<numActive, 256, 0, stream>>>(dActive, dInst, dVertices, dIndices, dProx);
   if(mergedBox)
@@ -1842,25 +1880,12 @@ int pt_tlas_build(hipStream_t stream, const PtTuning& tune, const InstanceRec* d
     r.e1n = make_float4(mergedBox[3] - mergedBox[0], mergedBox[4] - mergedBox[1], mergedBox[5] - mergedBox[2], 0.f);
     r.e2p = make_float4(0.f, 0.f, 0.f, 0.f);
     if(hipMemcpyAsync(dProx + numActive, &r, sizeof(r), hipMemcpyHostToDevice, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-    {
-      snprintf(err, errLen, "TLAS build: upload failed");
-      goto done;
-    }
+      return fail("upload failed");
   }
-  if(pt_accel_build(stream, tune, nullptr, 0, nullptr, nullptr, n, dLeafOrder, dAlpha, dNodes, dTlasOut, numWideOut, err, errLen, dProx, nullptr) != 0)
-    goto done;
+  if(pt_accel_build(stream, tune, nullptr, 0, nullptr, nullptr, n, dLeafOrder, dAlpha, dNodes, dTlasOut, numWideOut, err, errLen, sc, dProx) != 0)
+    return fail(nullptr);
   k_tlas_leaves<<<(n + 255) / 256, 256, 0, stream>>>(n, dLeafOrder, dInst, dInstNodeBase, dInstPad, dLeavesOut, mergedNodeBase);
   if(hipMemcpyAsync(rootOut, dNodes, sizeof(BvhNode), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess)
-  {
-    snprintf(err, errLen, "TLAS build: a kernel failed");
-    goto done;
-  }
-  rc = 0;
-done:
-  (void)hipStreamSynchronize(stream);
-  void* all[] = {dProx, dLeafOrder, dAlpha, dNodes};
-  for(void* q : all)
-    if(q)
-      (void)hipFree(q);
-  return rc;
+    return fail("a kernel failed");
+  return 0;
 }

@@ -290,24 +290,13 @@ int pt_build_accel(pt_context* c)
   if((rc = dev_alloc(c, c->dWide, sizeof(WideNode) * size_t(c->numBvhNodes))) != PT_OK) return rc;
   auto t0 = std::chrono::steady_clock::now();
   char msg[256];
-  // the builder's ~30 temporaries come out of one arena (one allocation and one free instead of thirty each: 3-5 ms of a 15 ms build); whatever
-  // does not fit -- or everything, if the arena cannot be had -- is allocated singly
-  PtScratch arena;
-  {
-    const size_t want = size_t(c->numTris) * 640 + (size_t(1) << 20);
-    if(hipMalloc((void**)&arena.base, want) == hipSuccess)
-      arena.cap = want;
-    else
-    {
-      arena.base = nullptr;
-      (void)hipGetLastError();
-    }
+  int brc;
+  {  // the arena goes back before the compact nodes and shading lines are allocated, and inside the timed window
+    PtScratch scratch;
+    scratch.reserve(pt_scratch_bytes(c->tune, c->numTris, false));
+    brc = pt_accel_build(c->stream, c->tune, (const InstanceRec*)c->dInstances.p, c->numInstances, (const float4*)c->dVertices.p, (const uint32_t*)c->dIndices.p, c->numTris,
+                         (TriRec*)c->dTris.p, (AlphaRec*)c->dAlphaRecs.p, (BvhNode*)c->dBvh.p, (WideNode*)c->dWide.p, &c->numWideNodes, msg, sizeof(msg), scratch);
   }
-  const int brc = pt_accel_build(c->stream, c->tune, (const InstanceRec*)c->dInstances.p, c->numInstances, (const float4*)c->dVertices.p, (const uint32_t*)c->dIndices.p, c->numTris,
-                                 (TriRec*)c->dTris.p, (AlphaRec*)c->dAlphaRecs.p, (BvhNode*)c->dBvh.p, (WideNode*)c->dWide.p, &c->numWideNodes, msg, sizeof(msg), nullptr, &arena);
-  arena.release();
-  if(arena.base)
-    (void)hipFree(arena.base);
   if(brc != 0)
     return c->fail(PT_ERR_HIP, "pt_build_accel: %s", msg);
   build_cnodes(c, c->numWideNodes);

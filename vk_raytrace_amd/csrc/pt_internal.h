@@ -13,35 +13,62 @@
 #endif
 
 // pt_accel.hip
-// Bump arena for a build's temporaries (one device allocation for many builds); what does not fit is allocated individually and freed by release().
+// Device scratch of the acceleration-structure builds: a bump arena (ONE device allocation for the ~30 temporaries of a build, reused by the builds
+// that follow: 3-5 ms of a 15 ms build) plus single allocations for what does not fit -- or for everything, when there is no arena.  The destructor
+// frees both, so a driver returns from anywhere.  The owner makes sure that the stream is drained before a rewind or the destructor runs.
 struct PtScratch {
+  struct Mark { size_t off; int numOwned; };
+  PtScratch() = default;
+  PtScratch(const PtScratch&) = delete;
+  ~PtScratch()
+  {
+    rewind(Mark{0, 0});
+    (void)hipFree(base);
+  }
+  // Called once: tries to get the arena with one allocation (bytes == 0: none wanted).  A failure is soft: the error is cleared, so that it does not surface in a
+  // later HIP_TRY, and every temporary becomes its own allocation.
+  void reserve(size_t bytes)
+  {
+    if(bytes && hipMalloc((void**)&base, bytes) != hipSuccess)
+    {
+      base = nullptr;
+      (void)hipGetLastError();
+    }
+    cap = base ? bytes : 0;
+  }
+  // take: `count` elements out of the arena, or an allocation of their own when they do not fit.  keep: always an allocation of its own -- what a driver
+  // holds while the builds below it use the arena (a worker's binary nodes).  False: out of memory.
+  template <class T>
+  bool take(T*& p, size_t count) { return (p = (T*)alloc(sizeof(T) * count, true)) != nullptr; }
+  template <class T>
+  bool keep(T*& p, size_t count) { return (p = (T*)alloc(sizeof(T) * count, false)) != nullptr; }
+  // pt_accel_build takes a mark on entry and rewinds to it on exit: what its caller got before stays
+  Mark mark() const { return Mark{off, numOwned}; }
+  void rewind(Mark m)
+  {
+    while(numOwned > m.numOwned)
+      (void)hipFree(owned[--numOwned]);
+    off = m.off;
+  }
+
+private:
+  void* alloc(size_t bytes, bool fromArena)
+  {
+    bytes   = bytes ? ((bytes + 255) & ~size_t(255)) : 256;
+    void* p = nullptr;
+    if(fromArena && base && off + bytes <= cap)
+    {
+      p = base + off;
+      off += bytes;
+    }
+    else if(numOwned < 96 && hipMalloc(&p, bytes) == hipSuccess)
+      owned[numOwned++] = p;
+    return p;
+  }
   char*  base = nullptr;
   size_t cap = 0, off = 0;
   void*  owned[96];
   int    numOwned = 0;
-  hipError_t get(void** p, size_t bytes)
-  {
-    bytes = bytes ? ((bytes + 255) & ~size_t(255)) : 256;
-    if(base && off + bytes <= cap)
-    {
-      *p = base + off;
-      off += bytes;
-      return hipSuccess;
-    }
-    if(numOwned >= 96)
-      return hipErrorOutOfMemory;
-    hipError_t e = hipMalloc(p, bytes);
-    if(e == hipSuccess)
-      owned[numOwned++] = *p;
-    return e;
-  }
-  void release()
-  {
-    for(int i = 0; i < numOwned; ++i)
-      (void)hipFree(owned[i]);
-    numOwned = 0;
-    off      = 0;
-  }
 };
 // Launch-policy knobs (performance only, never results): one set PER CONTEXT, parsed key by key from the PT_TUNE environment variable when the context is
 // created ("tail=0,batch=4,build=sah"; unknown keys are reported on stderr once).  Defaults chosen from measurements.  Knobs whose sweeps said "the default is
@@ -52,7 +79,7 @@ struct PtTuning {
   int framesInFlight       = 4;    // independent frame batches overlapped on separate streams (accumulate stays ordered)
   int stateGB              = 0;    // cap of the in-flight path state in GB (0: 85 % of the free device memory); the batch shrinks to fit
   int stateMB              = 0;    // the same cap in MB (tests of the shrink path: a budget smaller than one default batch)
-  int sahBuild             = 3;    // 3: device binned SAH (default; pt_sahdev.h), 2: device PLOC, 1: host SAH topology (the cross-check of 3), 0: device LBVH (Karras radix tree)
+  int sahBuild             = 3;    // a PtBuilder.  3: device binned SAH (default; pt_sahdev.h), 2: device PLOC, 1: host SAH topology (the cross-check of 3), 0: device LBVH (Karras radix tree)
   int tailBelow            = 65536;  // a launch sequence hands the remaining bounces to k_tail (one launch, paths carried to their end) from the first bounce whose
                                    // queue is expected to hold at most this many paths (0: never)
   int warm                 = 1;    // pt_resize with scene, camera and environment in place: write every frame slot's path state once and run one throw-away launch
@@ -71,6 +98,8 @@ struct PtTuning {
   int cnodes               = 1;    // flat-format structures: 80-byte compact nodes for the persistent trace kernels (see pt_device.h CompactNode)
   int mergeSingles         = 1;    // two-level structure: prim-meshes instantiated once share one world-space bottom-level structure (0: a BLAS each)
   int accelTwoLevel        = 0;    // 1: the context starts with the two-level acceleration structure (PT_TUNE accel=two; pt_set_accel_mode overrides)
+  int arena                = 1;    // builds take their temporaries out of one arena (PtScratch); 0: every temporary is its own allocation (the path a build takes when the
+                                   // arena cannot be had; the tests run it)
   int batch                = 64;   // upper bound of the frames traced as one wavefront; the per-context value also keeps a batch below 2^26 paths (32 frames at 1080p)
 };
 // Parses a PT_TUNE string key by key ("key=value" tokens separated by commas) into `t`; every token whose key is not a knob is appended to `unknown`
@@ -80,6 +109,26 @@ void pt_parse_tuning(const char* tune, PtTuning& t, std::string& unknown);
 #define PT_PACKET_WAVES_LAUNCH 8192u  // persistent waves of the packet kernel (8 per SIMD)
 #define PT_ROTATE_PASSES 2            // device builders: bottom-up tree-rotation passes after the topology is built
 #define PT_PLOC_RADIUS 16             // PLOC: clusters examined on either side of a cluster per round
+
+// The builders of pt_accel_build, numbered as PT_TUNE build= and PtTuning::sahBuild number them
+enum PtBuilder { PT_BUILD_LBVH = 0, PT_BUILD_SAH = 1, PT_BUILD_PLOC = 2, PT_BUILD_SAHDEV = 3 };
+
+// Size of the arena for builds of up to numTris triangles (0 under PT_TUNE arena=0).  What the default builder (device binned SAH) takes per triangle:
+//   primitives  unsorted TriRec 48 + AlphaRec 32 + centroid 16                                              96
+//   boxes       leaf lo / hi 32 + inner lo / hi 32                                                          64
+//   tree        leaf order 4 + child and parent links 16 + arrival counters 4                               24
+//   SAH         prim boxes 32 + index and work-id lists A / B 16 + small-node list 72 / 2 = 36              84
+//               per 13 triangles (SD_SMALL + 1) one entry of: work lists A / B 144, bin counts 384, bin boxes 2304   218
+//   collapse    two queues of 12-byte items                                                                 24
+// = 510 bytes plus the rounding of every list to 256.  The radix sort of the LBVH and PLOC builders adds 13, and PLOC's cluster lists take 84 where SAH takes
+// 302.  A forest adds 16 bytes per root (the root lists of the builder and of the collapse; a root has two triangles or more, so at most 8 per triangle).
+// The sizes below leave a quarter of headroom over that; a build that needs more than its arena holds gets the rest as single allocations.
+inline size_t pt_scratch_bytes(const PtTuning& tune, uint32_t numTris, bool forest)
+{
+  if(!tune.arena)
+    return 0;
+  return forest ? size_t(numTris) * 704 + (size_t(4) << 20) : size_t(numTris) * 640 + (size_t(1) << 20);
+}
 
 // A FOREST (round 6): several hierarchies in ONE level-synchronous device-SAH build -- root r owns the primitives [first[r], first[r] + count[r]) (count >= 2;
 // the instances are numbered like the roots and their triBase is first[r]), its binary nodes take the ids first[r] .. first[r] + count[r] - 2, its wide nodes are
@@ -93,10 +142,15 @@ struct PtForest {
   uint32_t        leafOffset;
   uint32_t*       numWide;    // out: wide nodes of every root
 };
+// Builds TriRec[numTris] (leaf order), BvhNode[max(1, numTris - 1)] and the wide nodes (*numWideOut of them) into caller-allocated device memory.
+// scratch: where the temporaries come from; it is left as it was found.
+// dProxies (may be null): the primitives are given as ready-made records instead of (instance, triangle) pairs -- the TLAS of the two-level
+// structure is built over one "diagonal" record per instance (p0 = box min, e1 = box extent, e2 = 0: its bounding box is the instance's box).
+// forest (may be null): see above; the device SAH builder only.
 int pt_accel_build(hipStream_t stream, const PtTuning& tune, const InstanceRec* dInst, uint32_t numInst, const float4* dVertices, const uint32_t* dIndices, uint32_t numTris,
-                   TriRec* dTrisOut, AlphaRec* dAlphaOut, BvhNode* dNodesOut, WideNode* dWideOut, uint32_t* numWideOut, char* err, size_t errLen,
-                   const TriRec* dProxies = nullptr, PtScratch* scratch = nullptr, const PtForest* forest = nullptr);
-// Two-level structure (reference: src/accelstruct.cpp:110-162).  One BLAS per prim-mesh in object space ...
+                   TriRec* dTrisOut, AlphaRec* dAlphaOut, BvhNode* dNodesOut, WideNode* dWideOut, uint32_t* numWideOut, char* err, size_t errLen, PtScratch& scratch,
+                   const TriRec* dProxies = nullptr, const PtForest* forest = nullptr);
+// Two-level structure (reference: src/accelstruct.cpp:110-162).  One BLAS per prim-mesh in object space, built at its bases in the shared arrays ...
 struct PtBlasDesc {
   uint32_t primMesh, vertexOffset, firstIndex, triCount, flags;  // flags: TRI_OPAQUE / TRI_NOCULL of the mesh's material (no TRI_FLIP: that is per instance)
   int32_t  materialIndex;
@@ -105,21 +159,24 @@ struct PtBlasDesc {
 };
 int pt_blas_build(hipStream_t stream, const PtTuning& tune, PtBlasDesc* blas, uint32_t numBlas, const float4* dVertices, const uint32_t* dIndices, TriRec* dTris, AlphaRec* dAlpha, WideNode* dWide,
                   char* err, size_t errLen);
-// ... and one TLAS over the world boxes of the `numActive` non-empty instances listed in dActive (exact bounds of the T1 world triangles).
-// dInstNodeBase[inst]: root node of the instance's BLAS; dInstPad[2 * inst + {0,1}]: TlasLeaf::padC0 / padC1.  rootOut: the binary root (world bounds).
-int pt_tlas_build(hipStream_t stream, const PtTuning& tune, const InstanceRec* dInst, const uint32_t* dActive, uint32_t numActive, const uint32_t* dInstNodeBase, const float* dInstPad,
-                  const float4* dVertices, const uint32_t* dIndices, WideNode* dTlasOut, TlasLeaf* dLeavesOut, BvhNode* rootOut, uint32_t* numWideOut, char* err, size_t errLen,
-                  const float* mergedBox = nullptr, uint32_t mergedNodeBase = 0);
-// ... with mergedBox (lo xyz, hi xyz) one more TLAS primitive: the merged world-space structure of the prim-meshes instantiated once
-// (pt_trace.h PT_INST_MERGED), built by pt_merged_build into dTris / dAlpha / dWide at slotBase / nodeBase like a BLAS.
-// WideNode -> CompactNode for the first n nodes; -1 when a node cannot be represented (the caller keeps the WideNode walk)
-void pt_launch_shade_tris(hipStream_t stream, uint32_t n, const TriRec* tris, const InstanceRec* inst, const float4* vertices, const uint32_t* indices, float4* out);
-int pt_compact_nodes(hipStream_t stream, uint32_t n, const WideNode* in, CompactNode* out, float* reachOut = nullptr);  // reachOut: max |p| + 2047 step over the nodes
-// ... over numRanges node ranges given as (base, count) pairs
-int pt_compact_node_ranges(hipStream_t stream, const uint32_t* hBaseCount, uint32_t numRanges, const WideNode* in, CompactNode* out);
+// ... one merged world-space structure of the prim-meshes instantiated once (pt_trace.h PT_INST_MERGED), built into dTris / dAlpha / dWide at slotBase /
+// nodeBase like a BLAS: the flat build over the instances listed in hInst, whose records then get the instance id hIds[j] and the world index
+// hWorldBase[j] + primitive they have in the scene.  boxOut6: its world box (lo xyz, hi xyz) ...
 int pt_merged_build(hipStream_t stream, const PtTuning& tune, const InstanceRec* hInst, const uint32_t* hIds, const uint32_t* hWorldBase, uint32_t numInst, uint32_t numTris, const float4* dVertices,
                     const uint32_t* dIndices, TriRec* dTris, AlphaRec* dAlpha, WideNode* dWide, uint32_t slotBase, uint32_t nodeBase, uint32_t* numWideOut, float* boxOut6, char* err,
                     size_t errLen);
+// ... and one TLAS over the world boxes of the `numActive` non-empty instances listed in dActive (exact bounds of the T1 world triangles).
+// dInstNodeBase[inst]: root node of the instance's BLAS; dInstPad[2 * inst + {0,1}]: TlasLeaf::padC0 / padC1.  rootOut: the binary root (world bounds).
+// mergedBox (may be null): the merged structure's box, one more TLAS primitive whose leaf points at mergedNodeBase.
+int pt_tlas_build(hipStream_t stream, const PtTuning& tune, const InstanceRec* dInst, const uint32_t* dActive, uint32_t numActive, const uint32_t* dInstNodeBase, const float* dInstPad,
+                  const float4* dVertices, const uint32_t* dIndices, WideNode* dTlasOut, TlasLeaf* dLeavesOut, BvhNode* rootOut, uint32_t* numWideOut, char* err, size_t errLen,
+                  const float* mergedBox = nullptr, uint32_t mergedNodeBase = 0);
+// WideNode -> CompactNode for the first n nodes; -1 when a node cannot be represented (the caller keeps the WideNode walk).  reachOut: max |p| + 2047 step over the nodes
+int pt_compact_nodes(hipStream_t stream, uint32_t n, const WideNode* in, CompactNode* out, float* reachOut = nullptr);
+// ... over numRanges node ranges given as (base, count) pairs
+int pt_compact_node_ranges(hipStream_t stream, const uint32_t* hBaseCount, uint32_t numRanges, const WideNode* in, CompactNode* out);
+// DeviceScene::shadeTris of a flat-format structure: one 128-byte shading line per leaf slot
+void pt_launch_shade_tris(hipStream_t stream, uint32_t n, const TriRec* tris, const InstanceRec* inst, const float4* vertices, const uint32_t* indices, float4* out);
 
 // pt_render.hip -- one frame of the wavefront pipeline, enqueued on `stream`
 // Per-bounce counter block (CNT_STRIDE words per bounce; zero when a sample pass starts: pt_resize clears it, k_accumulate leaves it cleared):

@@ -403,7 +403,7 @@ void pt_parse_tuning(const char* tune, PtTuning& t, std::string& unknown)
                              {"cnodes", &PtTuning::cnodes}, {"shadeTris", &PtTuning::shadeTris}, {"tail", &PtTuning::tailBelow}, {"warm", &PtTuning::warm}, {"texTile", &PtTuning::texTile},
                              {"texGroups", &PtTuning::texGroups}, {"regen", &PtTuning::regen}, {"packetTwo", &PtTuning::packetTwo}, {"blasWorkers", &PtTuning::blasWorkers},
                              {"batch", &PtTuning::batch}, {"inflight", &PtTuning::framesInFlight}, {"displaySlots", &PtTuning::displaySlots}, {"bands", &PtTuning::bands},
-                             {"bandTiles", &PtTuning::bandTiles}, {"fuse", &PtTuning::fuse}};
+                             {"bandTiles", &PtTuning::bandTiles}, {"fuse", &PtTuning::fuse}, {"arena", &PtTuning::arena}};
   const std::string all(tune);
   size_t            at = 0;
   while(at <= all.size())
@@ -425,10 +425,10 @@ void pt_parse_tuning(const char* tune, PtTuning& t, std::string& unknown)
     if(key == "build")
     {
       ok = true;
-      if(val == "lbvh") t.sahBuild = 0;
-      else if(val == "sah") t.sahBuild = 1;
-      else if(val == "ploc") t.sahBuild = 2;
-      else if(val == "sahdev") t.sahBuild = 3;
+      if(val == "lbvh") t.sahBuild = PT_BUILD_LBVH;
+      else if(val == "sah") t.sahBuild = PT_BUILD_SAH;
+      else if(val == "ploc") t.sahBuild = PT_BUILD_PLOC;
+      else if(val == "sahdev") t.sahBuild = PT_BUILD_SAHDEV;
       else ok = false;
     }
     else if(key == "accel")
@@ -457,7 +457,7 @@ void pt_parse_tuning(const char* tune, PtTuning& t, std::string& unknown)
     t.bandTiles = 1;
 }
 
-// test hook (no GPU involved): parses `tune` as pt_create would and reports the knobs in the order of the keys below plus build / accel;
+// test hook (no GPU involved): parses `tune` as pt_create would and reports the knobs in the order of the keys below plus build / accel / arena;
 // `unknown` receives the tokens that name no knob.  Returns the number of values written.
 extern "C" __attribute__((visibility("default"))) int pt_debug_parse_tuning(const char* tune, int* out, int maxOut, char* unknownOut, size_t unknownLen)
 {
@@ -465,7 +465,7 @@ extern "C" __attribute__((visibility("default"))) int pt_debug_parse_tuning(cons
   std::string unknown;
   pt_parse_tuning(tune, t, unknown);
   const int v[] = {t.stateMB, t.stateGB, t.packetClosestBounces, t.mergeSingles, t.cnodes, t.shadeTris, t.tailBelow, t.warm, t.texTile, t.texGroups, t.regen, t.packetTwo,
-                   t.blasWorkers, t.batch, t.framesInFlight, t.displaySlots, t.bands, t.bandTiles, t.fuse, t.sahBuild, t.accelTwoLevel};
+                   t.blasWorkers, t.batch, t.framesInFlight, t.displaySlots, t.bands, t.bandTiles, t.fuse, t.sahBuild, t.accelTwoLevel, t.arena};
   const int n   = int(sizeof(v) / sizeof(v[0]));
   for(int i = 0; i < n && i < maxOut; ++i)
     out[i] = v[i];
