@@ -645,6 +645,59 @@ int orc_tonemap_curve(int fn, uint64_t n, const float* in, int in_stride, float*
 #define PROBE_CLAMP gclamp
 #include "probe_rows.h"  // orc_shading_probe: the probes above over arrays of states
 
+// The oracle's own copy of trace contract T1 - T3 one call at a time, with the row layouts of vk_raytrace_amd/csrc/pt_probe.h trace_probe.  Kind 0 (TRP_TRI): in p0[3]
+// e1[3] e2[3] flags o[3] d[3], out accept t u v (left alone on reject) through Scene::intersect.  Kind 1 (TRP_WORLD_TRI): in the objectToWorld rows r0[4] r1[4]
+// r2[4] and three object-space vertices, out p0 e1 e2 of the one world triangle Scene::build_world makes of a scene with that one node (rows whose matrix it
+// refuses are left alone).  -1: the other kinds are the product's box arithmetic, which the oracle does not have.
+int orc_trace_probe(int kind, uint64_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  if(kind < 0 || kind > 1 || in_stride < (kind == 0 ? 16 : 21) || out_stride < (kind == 0 ? 4 : 9))
+    return -1;
+  for(uint64_t i = 0; i < n; ++i)
+  {
+    const float* r = in + i * (uint64_t)in_stride;
+    float*       o = out + i * (uint64_t)out_stride;
+    if(kind == 0)
+    {
+      WorldTri tr;
+      tr.p0 = vec3(r[0], r[1], r[2]); tr.e1 = vec3(r[3], r[4], r[5]); tr.e2 = vec3(r[6], r[7], r[8]);
+      tr.node = 0; tr.prim = 0;
+      std::memcpy(&tr.flags, r + 9, 4);
+      float      t = o[1], u = o[2], v = o[3];
+      const bool hit = Scene::intersect(tr, vec3(r[10], r[11], r[12]), vec3(r[13], r[14], r[15]), t, u, v);
+      const uint32_t flag = hit ? 1u : 0u;
+      std::memcpy(o, &flag, 4);
+      if(hit)
+      {
+        o[1] = t; o[2] = u; o[3] = v;
+      }
+      continue;
+    }
+    pt_VertexAttributes vtx[3] = {};
+    for(int k = 0; k < 3; ++k)
+      for(int a = 0; a < 3; ++a)
+        vtx[k].position[a] = r[12 + 3 * k + a];
+    const uint32_t       idx[3] = {0u, 1u, 2u};
+    const pt_PrimMesh    pm{0u, 3u, 0u, 3u, 0};
+    pt_Node              nd{};
+    for(int row = 0; row < 3; ++row)
+      for(int col = 0; col < 4; ++col)
+        nd.worldMatrix[col * 4 + row] = r[4 * row + col];
+    nd.worldMatrix[15] = 1.0f;
+    nd.primMesh        = 0;
+    pt_GltfShadeMaterial mat{};
+    pt_SceneDesc         d{};
+    d.vertices = vtx; d.numVertices = 3; d.indices = idx; d.numIndices = 3; d.primMeshes = &pm; d.numPrimMeshes = 1; d.nodes = &nd; d.numNodes = 1;
+    d.materials = &mat; d.numMaterials = 1;
+    Scene sc;
+    if(!sc.set(&d) || sc.tris.size() != 1)
+      continue;
+    const WorldTri& w = sc.tris[0];
+    o[0] = w.p0.x; o[1] = w.p0.y; o[2] = w.p0.z; o[3] = w.e1.x; o[4] = w.e1.y; o[5] = w.e1.z; o[6] = w.e2.x; o[7] = w.e2.y; o[8] = w.e2.z;
+  }
+  return 0;
+}
+
 // A hit turned into the State every BSDF call reads: GetShadeState + the lines of PathTrace between it and the debug modes + GetMaterialsAndTextures, on the
 // scene the context holds.  Row layout of vk_raytrace_amd/csrc/pt_probe.h surface_probe (kind 0, SURF_STATE; the `path` word is the product's business and
 // ignored, the line-path word is left alone): in instance primitive bu bv rayDir[3] path, out 17 words after GetShadeState, 50 after the resolve, the material

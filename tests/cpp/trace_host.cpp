@@ -1386,6 +1386,27 @@ int th_surface_probe(void* p, int kind, uint64_t n, const float* in, int in_stri
     (void)surface_probe(s->dsFlat, lim, kind, in + size_t(i) * in_stride, out + size_t(i) * out_stride);
   return 0;
 }
+// ---- the intersection arithmetic one call at a time (pt_probe.h trace_probe): n rows, each read and written in place.  The device runs the same function per
+// lane (pt_debug_trace_probe).
+int th_trace_probe(int kind, uint64_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  int inWords = 0, outWords = 0;
+  trace_row_words(kind, inWords, outWords);
+  if(inWords == 0 || in_stride < inWords || out_stride < outWords)
+    return -1;
+#pragma omp parallel for schedule(static)
+  for(long long i = 0; i < (long long)n; ++i)
+  {
+    float row[TRP_IN], res[TRP_OUT];
+    for(int k = 0; k < TRP_IN; ++k)
+      row[k] = k < inWords ? in[size_t(i) * in_stride + k] : 0.0f;
+    for(int k = 0; k < TRP_OUT; ++k)
+      res[k] = k < outWords ? out[size_t(i) * out_stride + k] : 0.0f;
+    trace_probe(kind, row, res);
+    std::memcpy(out + size_t(i) * out_stride, res, sizeof(float) * size_t(outWords));
+  }
+  return 0;
+}
 // the scene's texture records (TexRec, 32 B each), material lines (PT_MAT_LINE_QUADS x 16 B per material), alpha view (AlphaMat, 80 B each), opacity maps
 // and texel pool as th_create_scene fetched them; null outputs: the counts only (records, materials, map words, pool texels)
 void th_texture_records(void* p, unsigned long long* counts4, void* texRecsOut, void* matLinesOut, void* alphaMatsOut, uint32_t* alphaMapsOut, uint32_t* texelsOut)

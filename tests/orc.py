@@ -67,7 +67,7 @@ def lib():
         L.orc_hook_sample_env.restype, L.orc_hook_sample_env.argtypes = None, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]   # (ctx, u, v, rgb): sample_env as the reference's hook
         L.orc_wrap_coord.restype, L.orc_wrap_coord.argtypes = C.c_int, [C.c_int, C.c_int, C.c_int]   # (i, n, mode)
         L.orc_trace_closest.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 7
-        for fn in (L.orc_shading_probe, L.orc_glsl_builtin, L.orc_tonemap_curve):  # (fn, n, in, in_stride, out, out_stride): oracle/probe_rows.h
+        for fn in (L.orc_shading_probe, L.orc_glsl_builtin, L.orc_tonemap_curve, L.orc_trace_probe):  # (fn, n, in, in_stride, out, out_stride): oracle/probe_rows.h, orc_trace_probe
             fn.restype, fn.argtypes = C.c_int, [C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         # (ctx, kind, n, in, in_stride, out, out_stride): a hit turned into a State on the context's scene, rows of csrc/pt_probe.h surface_probe; 1: no such data
         L.orc_surface_probe.restype, L.orc_surface_probe.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int]

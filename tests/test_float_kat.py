@@ -30,6 +30,8 @@ Oracle and reference only, because the product has no such FUNCTION (the entry a
     post.frag compiles it): all on the reference, the three its display pass uses on the oracle.  The product's display pass lives in pt_render.hip next to
     the shipped kernels and is held to the oracle's by tests/test_gpu_parity.py; it has no host build.
 The shaders use no transpose(), inverse() or mat3(mat4): no side defines them, there is nothing to probe.
+The intersection arithmetic (tri_test, world_tri, the box tests, enter_instance: csrc/pt_trace.h) is not shading math and is OUT OF SCOPE here: it has an exact
+rational model of its own, tests/golden/gen_trace_kat.py, held by tests/test_trace_model.py and tests/test_trace_gpu.py.
 sun_and_sky.glsl (603 lines of tables) is OUT OF SCOPE for the float64 model: it gets the bit-identity probes only (host build == oracle, device == host
 build, six variants x 1508 directions).
 "Thin-walled from inside" (dot(ffnormal, normal) < 0 -> F = 0, discriminant = 0 in DisneySample / PbrSample) is UNREACHABLE through the function-level

@@ -86,6 +86,7 @@ DEBUG_API = [
     ("pt_debug_shading_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h: (ctx, fn, n, in, in_stride, out, out_stride)
     ("pt_debug_texture_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h texture_probe, on the context's scene: (ctx, kind, n, in, in_stride, out, out_stride)
     ("pt_debug_surface_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h surface_probe, on the context's scene: (ctx, kind, n, in, in_stride, out, out_stride); 1: no such data
+    ("pt_debug_trace_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h trace_probe, every load inside the row: (ctx, kind, n, in, in_stride, out, out_stride)
 ]
 
 _lib = None

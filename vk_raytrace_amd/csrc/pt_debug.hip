@@ -266,6 +266,37 @@ extern "C" __attribute__((visibility("default"))) int pt_debug_surface_probe(pt_
     k_surface_probe<<<dim3((n + 63) / 64), dim3(64), 0, c->stream>>>(c->scene, lim, kind, n, dIn, in_stride, dOut, out_stride);
   });
 }
+// The intersection arithmetic one call at a time on the device (pt_probe.h trace_probe: tri_test, world_tri, make_raybox, a node visit in both node forms, cn_plane,
+// enter_instance), one row per lane; a row reads nothing but its own words.  tests/test_trace_gpu.py holds the result bit for bit to the host build of the same
+// function (tests/cpp/trace_host.cpp th_trace_probe) and to the exact model of tests/golden/gen_trace_kat.py.  Not part of the ABI.
+__global__ void k_trace_probe(int kind, uint32_t n, const float* __restrict__ in, int inStride, float* __restrict__ out, int outStride, int inWords, int outWords)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  float row[TRP_IN], res[TRP_OUT];
+  for(int k = 0; k < TRP_IN; ++k)
+    row[k] = k < inWords ? in[size_t(i) * inStride + k] : 0.0f;
+  for(int k = 0; k < TRP_OUT; ++k)
+    res[k] = k < outWords ? out[size_t(i) * outStride + k] : 0.0f;
+  trace_probe(kind, row, res);
+  for(int k = 0; k < outWords; ++k)
+    out[size_t(i) * outStride + k] = res[k];
+}
+extern "C" __attribute__((visibility("default"))) int pt_debug_trace_probe(pt_context* c, int kind, uint32_t n, const float* in, int in_stride, float* out, int out_stride)
+{
+  CTX_CHECK(c);
+  int inWords = 0, outWords = 0;
+  trace_row_words(kind, inWords, outWords);
+  if(inWords == 0 || inWords > TRP_IN || outWords > TRP_OUT || !in || !out || in_stride < inWords || out_stride < outWords || n > (1u << 24))
+    return c->fail(PT_ERR_INVALID, "pt_debug_trace_probe: bad arguments");
+  if(n == 0)
+    return PT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return run_rows(c, "pt_debug_trace_probe", n, in, in_stride, out, out_stride, [&](const float* dIn, float* dOut) {
+    k_trace_probe<<<dim3((n + 63) / 64), dim3(64), 0, c->stream>>>(kind, n, dIn, in_stride, dOut, out_stride, inWords, outWords);
+  });
+}
 // One level of the offscreen image the display pass samples (pt_capi.hip display_chain: the very function pt_tonemap_zoom runs), copied back for
 // tests/test_display_gpu.py: the zero padding of a de-scaled viewport and every vkCmdBlitImage(LINEAR) level, which the RGBA8 image only shows through
 // the exposure.  Returns the number of levels of the full chain; a level outside it copies nothing.

@@ -3,7 +3,9 @@
 // GLSL built-ins of pt_math.h (mirror, bend, lerp, smooth).  No formula lives here.  pt_debug.hip wraps it in a kernel (k_shading_probe, one state
 // per lane); tests/cpp/trace_host.cpp compiles the same function for the host (th_shading_probe).  tests/test_float_kat.py holds both to an
 // independent float64 model and to each other, bit for bit.  Below it: texture_probe (the software texture path one call at a time, tests/test_texture_model.py)
-// and surface_probe (a hit turned into the Surface: fetch_triangle, surface_at_hit, resolve_material_at, and the per-slot shading lines; tests/test_surface_model.py).
+// and surface_probe (a hit turned into the Surface: fetch_triangle, surface_at_hit, resolve_material_at, and the per-slot shading lines; tests/test_surface_model.py),
+// and trace_probe (the intersection arithmetic of pt_trace.h one call at a time: tri_test, world_tri, make_raybox, a node visit in both node forms, cn_plane,
+// enter_instance; tests/test_trace_model.py).
 //
 // Row layouts (32-bit words; integers travel as bit patterns):
 //   PROBE_EVAL_DISNEY / PROBE_EVAL_GLTF      in  m[22] N[3] T[3] B[3] eta thin V[3] L[3] seed   (PROBE_BSDF_IN = 40; m = albedo3 specular anisotropy metallic roughness subsurface specularTint sheen sheenTint3 clearcoat clearcoatRoughness transmission ior ax ay f0_3)
@@ -27,6 +29,7 @@
 //   PROBE_BASIS_MUL                          in  c0[3] c1[3] c2[3] v[3]                         out 3   (mat3(c0, c1, c2) * v)
 #pragma once
 #include "pt_shade.h"
+#include "pt_cnode.h"
 
 enum {
   PROBE_EVAL_DISNEY = 0, PROBE_EVAL_GLTF, PROBE_SAMPLE_DISNEY, PROBE_SAMPLE_GLTF, PROBE_SUN_AND_SKY, PROBE_SPHERICAL_UV, PROBE_FRAME, PROBE_RANGE_ATTENUATION,
@@ -402,4 +405,146 @@ PT_DEV int surface_probe(const DeviceScene& S, const SurfProbeLimits& lim, int k
   o[48] = __uint_as_float(sf.unlit ? 1u : 0u); o[49] = __uint_as_float(sf.thinwalled ? 1u : 0u);
   o[50] = __uint_as_float(uint32_t(useMat)); o[51] = __uint_as_float(line ? 1u : 0u);
   return SURF_OK;
+}
+
+// ---- the intersection arithmetic one call at a time (tests/test_trace_model.py, tests/test_trace_gpu.py): tri_test (trace contract T2 / T3), world_tri (T1 at a
+// two-level leaf), make_raybox, one node visit on the 128-byte node (wide_node_step) and on its 80-byte form (cn_encode, then wide_node_step_c), cn_plane and
+// enter_instance.  No formula lives here.  Every load stays inside the row: the node, the instance record and the TLAS leaf a function reads are built from the
+// row's words on the stack.  Rows of up to TRP_IN words in, TRP_OUT words out (integers travel as bit patterns; trace_row_words has the counts per kind):
+//   TRP_TRI        in  p0[3] e1[3] e2[3] flags o[3] d[3]              out accept, t u v (left as the caller filled them on reject)
+//   TRP_WORLD_TRI  in  objectToWorld r0[4] r1[4] r2[4], v0[3] v1[3] v2[3] (object space)   out p0[3] e1[3] e2[3] of world_tri
+//   TRP_RAYBOX     in  o[3] d[3]                                      out idir[3] nlo[3] nhi[3] nearOff[3]
+//   TRP_NODE       in  one WideNode: minx[4] miny[4] minz[4] maxx[4] maxy[4] maxz[4] child[4], then o[3] d[3] lim alphaOnly
+//                  out the child returned, the number pushed, the pushed children in push order (the rest left alone)
+//   TRP_CNODE      in  the same row                                   out cn_encode's ok flag, then the same five words from the visit of the encoded node
+//                                                                         (left alone when the node cannot be encoded)
+//   TRP_CN_PLANE   in  one word                                       out cn_plane(word, 0), cn_plane(word, 1)
+//   TRP_ENTER      in  worldToObject r0[4] r1[4] r2[4], padC0 padC1, o[3] d[3]             out the RayBox of enter_instance, as TRP_RAYBOX
+enum { TRP_TRI = 0, TRP_WORLD_TRI, TRP_RAYBOX, TRP_NODE, TRP_CNODE, TRP_CN_PLANE, TRP_ENTER, TRP_COUNT };
+enum { TRP_IN = 36, TRP_OUT = 12 };
+
+__host__ __device__ inline void trace_row_words(int kind, int& in, int& out)
+{
+  switch(kind)
+  {
+    case TRP_TRI: in = 16; out = 4; break;
+    case TRP_WORLD_TRI: in = 21; out = 9; break;
+    case TRP_RAYBOX: in = 6; out = 12; break;
+    case TRP_NODE: in = 36; out = 5; break;
+    case TRP_CNODE: in = 36; out = 6; break;
+    case TRP_CN_PLANE: in = 1; out = 2; break;
+    case TRP_ENTER: in = 20; out = 12; break;
+    default: in = 0; out = 0; break;
+  }
+}
+
+PT_DEV void trp_put_raybox(float* out, const RayBox& rb)
+{
+  probe_put(out, rb.idir); probe_put(out + 3, rb.nlo); probe_put(out + 6, rb.nhi);
+  for(int a = 0; a < 3; ++a)
+    out[9 + a] = __uint_as_float(rb.nearOff[a]);
+}
+PT_DEV Affine trp_affine(const float* r)
+{
+  Affine m;
+  m.r0 = make_float4(r[0], r[1], r[2], r[3]); m.r1 = make_float4(r[4], r[5], r[6], r[7]); m.r2 = make_float4(r[8], r[9], r[10], r[11]);
+  return m;
+}
+
+PT_DEV void trace_probe(int kind, const float* in, float* out)
+{
+  switch(kind)
+  {
+    case TRP_TRI:
+    {
+      TriRec tr;
+      tr.p0w = make_float4(in[0], in[1], in[2], 0.0f); tr.e1n = make_float4(in[3], in[4], in[5], 0.0f); tr.e2p = make_float4(in[6], in[7], in[8], 0.0f);
+      float      t = out[1], u = out[2], v = out[3];
+      const bool hit = tri_test(tr, __float_as_uint(in[9]), probe_f3(in + 10), probe_f3(in + 13), t, u, v);
+      out[0] = __uint_as_float(hit ? 1u : 0u);
+      if(hit)
+      {
+        out[1] = t; out[2] = u; out[3] = v;
+      }
+      break;
+    }
+    case TRP_WORLD_TRI:
+    {
+      InstanceRec I;
+      memset(&I, 0, sizeof(I));
+      I.objectToWorld = trp_affine(in);
+      DeviceScene S;
+      memset(&S, 0, sizeof(S));
+      S.instances = &I; S.numInstances = 1;
+      TriRec obj;
+      obj.p0w = make_float4(in[12], in[13], in[14], __uint_as_float(0u)); obj.e1n = make_float4(in[15], in[16], in[17], 0.0f); obj.e2p = make_float4(in[18], in[19], in[20], 0.0f);
+      const TriRec r = world_tri(S, InstCtx{0u, 0, 0u}, obj);
+      probe_put(out, xyz(r.p0w)); probe_put(out + 3, xyz(r.e1n)); probe_put(out + 6, xyz(r.e2p));
+      break;
+    }
+    case TRP_RAYBOX: trp_put_raybox(out, make_raybox(probe_f3(in), probe_f3(in + 3))); break;
+    case TRP_NODE:
+    case TRP_CNODE:
+    {
+      WideNode w;
+      memset(&w, 0, sizeof(w));
+      float    planes[24];
+      uint32_t cw[4];
+      for(int k = 0; k < 24; ++k)
+        planes[k] = in[k];
+      for(int k = 0; k < 4; ++k)
+        cw[k] = __float_as_uint(in[24 + k]);
+      memcpy(&w, planes, sizeof(planes));  // minx .. maxz are the first 96 bytes of the node, in this order
+      w.child[0] = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+      const RayBox rb        = make_raybox(probe_f3(in + 28), probe_f3(in + 31));
+      const float  lim       = in[34];
+      const bool   alphaOnly = __float_as_uint(in[35]) != 0u;
+      uint32_t     pushed[PT_BVH_WIDTH];
+      int          np   = 0;
+      auto         push = [&](uint32_t c) {
+        if(np < PT_BVH_WIDTH)
+          pushed[np++] = c;
+      };
+      uint32_t nearest;
+      float*   o = out;
+      if(kind == TRP_CNODE)
+      {
+        CompactNode c;
+        const bool  ok = cn_encode(w, c);
+        out[0]         = __uint_as_float(ok ? 1u : 0u);
+        if(!ok)
+          break;
+        nearest = wide_node_step_c(&c, 0u, rb, lim, alphaOnly, push);
+        o       = out + 1;
+      }
+      else
+        nearest = wide_node_step(&w, 0u, rb, lim, alphaOnly, push);
+      o[0] = __uint_as_float(nearest);
+      o[1] = __uint_as_float(uint32_t(np));
+      for(int k = 0; k < np && k < 3; ++k)
+        o[2 + k] = __uint_as_float(pushed[k]);
+      break;
+    }
+    case TRP_CN_PLANE:
+    {
+      const uint32_t word = __float_as_uint(in[0]);
+      out[0] = cn_plane(word, 0); out[1] = cn_plane(word, 1);
+      break;
+    }
+    case TRP_ENTER:
+    {
+      InstanceRec I;
+      memset(&I, 0, sizeof(I));
+      I.worldToObject = trp_affine(in);
+      DeviceScene S;
+      memset(&S, 0, sizeof(S));
+      S.instances = &I; S.numInstances = 1;
+      TlasLeaf tl;
+      memset(&tl, 0, sizeof(tl));
+      tl.inst = 0u; tl.padC0 = in[12]; tl.padC1 = in[13];
+      trp_put_raybox(out, enter_instance(S, tl, probe_f3(in + 14), probe_f3(in + 17)));
+      break;
+    }
+    default: break;
+  }
 }
