@@ -894,8 +894,9 @@ uint32_t th_candidates(void* p, int mode, uint32_t nrays, const float* org, cons
 //   kind 0: closest-hit ray (T5), kind 1: shadow ray (T6, bounded by tmax[r]);  two: 0 flat structure, 1 two-level structure;
 //   exact 0: tail_closest / tail_shadow (pass A, pass B, consume_rejected_draws, fallback), exact 1: the key-ordered loop with one
 //   alpha_test per non-opaque candidate (k_closest_x / k_shadow_x = the definition), exact 2: the TRACE MACHINE of the persistent kernels
-//   (pt_machine.h lane_begin / lane_inner / lane_leaf / lane_pop / lane_begin_count driven like k_closest_p / k_shadow_p drive one lane; the
-//   few lines of their service round -- pass A -> pass B transition, bulk draws, hand-over to the exact loop -- are restated here).
+//   (pt_machine.h lane_fetch_* / lane_inner / lane_leaf / lane_pop / lane_begin_count driven like k_closest_p / k_shadow_p / k_trace_p drive one lane.
+//   What their service round decides -- pass A -> pass B transition, the draws, hand-over to the exact loop -- is the settle rule of pt_trace.h,
+//   needs_count_pass and settle_draws: the very functions the kernels call; only what is done with the verdict, writing out[], is this file's).
 // out per ray: w (world triangle index of the hit, 0xffffffff none; for shadow rays 1 / 0 = in shadow or not), t, u, v, seed afterwards,
 // number of alpha draws counted.  Returns the number of traversal-stack overflows.
 uint32_t th_settle(void* p, int kind, int two, int exact, int variant, uint32_t nrays, const float* org, const float* dir, const float* tmax, const uint32_t* seeds, uint32_t* outW,
@@ -934,7 +935,7 @@ uint32_t th_settle(void* p, int kind, int two, int exact, int variant, uint32_t 
         TraceLane             L;
         std::vector<uint32_t> spill(STACK_SPILL);
         int                   maxSp = 0;
-        lane_begin(L, o, d, kind == 0 ? PT_INFINITY : absorb[r].w, S.numTris == 0);
+        if(kind == 0) lane_fetch_closest(S, rb, uint32_t(r), L, seed); else lane_fetch_shadow(S, rb, uint32_t(r), L, seed);  // (the kernels' fetch)
         for(;;)
         {
           while(!L.done)
@@ -955,18 +956,15 @@ uint32_t th_settle(void* p, int kind, int two, int exact, int variant, uint32_t 
           }
           // service round of k_closest_p / k_shadow_p for this lane
           bool fallback = (L.flags & TF_SAW_FRAC) != 0;
-          if(!fallback && L.pass == 0 && (L.flags & TF_SAW_ZERO) && !pass_a_settles(L.bslot, L.bt, L.zeroMaxT, L.zeroMaxT2, L.zeroMaxT3, L.cnt))
+          if(needs_count_pass(L.flags, L.pass, L.bslot, L.bt, L.zeroMaxT, L.zeroMaxT2, L.zeroMaxT3, L.cnt))
           {
             if(two) lane_begin_count<true>(L); else lane_begin_count<false>(L);
             continue;
           }
           if(!fallback)
           {
-            uint32_t nDraw = L.cnt;
-            if(L.bslot != BVH_NONE && !((L.bw >> 29) & TRI_OPAQUE))
-              ++nDraw;
-            uint32_t s2 = seed;
-            if(consume_rejected_draws(s2, nDraw))
+            uint32_t nDraw, s2;
+            if(settle_draws(L.bslot, L.bw, L.cnt, seed, nDraw, s2))
             {
               draws = nDraw;
               if(kind == 0)

@@ -583,6 +583,43 @@ def test_launch_policy_sponza_like_and_samples_per_frame():
         assert np.array_equal(got, ref), tune
 
 
+def _stats_in_subprocess(tune):
+    """stats() after 3 frames of the policy test's feature box (160x96, depth 6), rendered in a fresh process with PT_TUNE = `tune` (None: unset)."""
+    import json
+    import subprocess
+    import sys
+    code = """
+import json, sys
+sys.path.insert(0, %r)
+from tests.common import Config, render_hip
+from vk_raytrace_amd import synth
+cfg = Config(synth.feature_box(tex_size=32), synth.procedural_sky(128, 64), 160, 96, depth=6)
+_, r = render_hip(cfg, 3, return_obj=True)
+print("STATS " + json.dumps({k: int(v) for k, v in r.stats().items()}))
+""" % ROOT
+    env = dict(os.environ)
+    env.pop("PT_TUNE", None)
+    if tune is not None:
+        env["PT_TUNE"] = tune
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=env)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    return json.loads([l for l in out.stdout.splitlines() if l.startswith("STATS ")][-1][6:])
+
+
+def test_launch_policy_never_changes_ray_and_draw_counts():
+    """The policy matrix above compares images; the places that settle a ray -- service rounds of k_closest_p / k_shadow_p / k_trace_p, the packet
+    kernel, k_tail's per-lane bodies -- are also where rays and alpha draws are counted.  Whichever of them a launch policy sends the paths through,
+    the counts are the oracle's: identical paths, identical work."""
+    cfg = Config(synth.feature_box(tex_size=32), synth.procedural_sky(128, 64), 160, 96, depth=6)
+    _, oo = render_oracle(cfg, 3, return_obj=True)
+    want = oo.stats()
+    assert want["alphaTests"] > 0 and want["shadowRays"] > 0   # the scene draws for alpha and casts shadow rays, or nothing below is tested
+    for tune in ("fuse=0,tail=0", "fuse=2,tail=0", "tail=0,packetClosest=0", "accel=two,fuse=2,tail=0", None):
+        got = _stats_in_subprocess(tune)
+        for k in ("closestRays", "shadowRays", "alphaTests", "shadedHits", "misses", "neeLookups"):
+            assert got[k] == want[k], (tune, k, got[k], want[k])
+
+
 def test_single_frames_cut_into_bands():
     """A frame launched alone on an idle GPU goes out as bands of its tiles on separate frame slots (PT_TUNE bands / bandTiles; the display
     slots take part): the accumulation image must not change, on either structure, with samples per frame, and against the batched run."""

@@ -11,6 +11,7 @@
 // Semantics are exactly those of traverse<TM_CLOSEST / TM_SHADOW / TM_COUNT> in pt_trace.h (same arithmetic,
 // same candidate rules); rays that need the exact key-ordered fallback are handed to the simple kernels.
 #pragma once
+#include "pt_internal.h"
 #include "pt_trace.h"
 
 // refill threshold: PT_REFILL_BELOW_DEFAULT in pt_internal.h (lanes still running below which idle lanes pull new rays)
@@ -287,4 +288,87 @@ PT_DEV uint32_t supply_next(RaySupply& rs, uint32_t* chunkCounter, uint32_t coun
     need = __ballot(wants && got == 0xffffffffu);
   }
   return got;
+}
+
+// ---- what the persistent kernels (pt_render.hip: k_closest_p, k_shadow_p, k_trace_p) share: entry, fetch, run loop, bookkeeping --------
+
+// Entry of a persistent kernel (block `block` of `grid`, a queue of `count` rays).  False: this block has nothing to do.
+// Small queue: fewer waves with full lanes.  Spreading such a queue over MORE waves (8 .. 56 rays each, so that the SIMDs hold more resident
+// waves and a wave waits for fewer rays) measured 4-7 % slower on the 20-step run and on an 8-GPU rank's shard (profiles/r04d_*): a
+// wave-instruction costs the same with 16 lanes as with 64.
+// Rays reserved per queue atomic: ~8 reservations per wave over the launch, at least `chunk`.  The lane starts idle.
+PT_DEV bool machine_enter(uint32_t block, uint32_t grid, uint32_t count, int chunk, RaySupply& rs, TraceLane& L)
+{
+  if(block > 0 && (unsigned long long)block * (TRACE_BLOCK * PT_MIN_GENERATIONS) >= count)
+    return false;
+  const uint32_t share = (count / (grid * 8u)) & ~63u, capped = share < 2048u ? share : 2048u;
+  rs.chunk = uint32_t(chunk) > capped ? uint32_t(chunk) : capped;
+  L.done   = true;
+  L.cur    = 0;
+  return true;
+}
+
+// A lane begins the closest-hit ray (T5) / the shadow ray (T6) of path `pslot` from the path state; seed: the path's RNG state before the ray's draws
+template <class RB>
+PT_DEV void lane_fetch_closest(const DeviceScene& S, const RB& rb, uint32_t pslot, TraceLane& L, uint32_t& seed)
+{
+  const float4 dw = rb.ps.rayD[pslot];
+  seed            = __float_as_uint(dw.w);
+  lane_begin(L, xyz(rb.ps.rayO[pslot]), xyz(dw), PT_INFINITY, S.numTris == 0);
+}
+template <class RB>
+PT_DEV void lane_fetch_shadow(const DeviceScene& S, const RB& rb, uint32_t pslot, TraceLane& L, uint32_t& seed)
+{
+  seed = __float_as_uint(rb.ps.rayD[pslot].w);
+  lane_begin(L, xyz(rb.ps.rayO[pslot]), xyz(rb.ps.neeDir[pslot]), rb.ps.absorb[pslot].w, S.numTris == 0);
+}
+
+// Lane-utilisation bookkeeping of the run loop: measurement build only (-DPT_HIST, tools/gpu_hist.py); without it the struct is empty and
+// every call vanishes.  Row 5 of g_hist: k_closest_p, row 6: k_shadow_p: [0] loop iterations, [1] / [2] lanes at an inner node / a leaf summed
+// over them, [3] service rounds, [4] iterations with both kinds, [5] / [6] with inner / leaf lanes.
+struct MachineHist {
+#ifdef PT_HIST
+  unsigned long long iter = 0, inner = 0, leaf = 0, service = 0, both = 0, innerIt = 0, leafIt = 0;
+  uint32_t           ni = 0;
+  PT_DEV void round() { ++service; }
+  PT_DEV void inner_step(const TraceLane& L) { ni = __popcll(__ballot(!L.done && !(L.cur & BVH_LEAF))); }
+  PT_DEV void leaf_step(const TraceLane& L)
+  {
+    const uint32_t nl = __popcll(__ballot(!L.done && (L.cur & BVH_LEAF)));
+    ++iter; inner += ni; leaf += nl; both += (ni && nl) ? 1 : 0; innerIt += ni ? 1 : 0; leafIt += nl ? 1 : 0;
+  }
+  PT_DEV void flush(int row) const
+  {
+    if((threadIdx.x & 63) != 0)
+      return;
+    atomicAdd(&g_hist[row][0], iter); atomicAdd(&g_hist[row][1], inner); atomicAdd(&g_hist[row][2], leaf); atomicAdd(&g_hist[row][3], service);
+    atomicAdd(&g_hist[row][4], both); atomicAdd(&g_hist[row][5], innerIt); atomicAdd(&g_hist[row][6], leafIt);
+  }
+#else
+  PT_DEV void round() {}
+  PT_DEV void inner_step(const TraceLane&) {}
+  PT_DEV void leaf_step(const TraceLane&) {}
+  PT_DEV void flush(int) const {}
+#endif
+};
+
+// The run loop: traversal steps until fewer than `target` lanes of the wave are still running.  anyHitEnds: the lane carries a shadow ray in an
+// all-opaque scene -- any hit inside (0, tmax) occludes and nothing draws, the nearest one need not be found.
+template <bool TWO>
+PT_DEV void machine_run(const DeviceScene& S, TraceLane& L, uint32_t* lds, uint32_t* spill, Counters* counters, int target, bool anyHitEnds, MachineHist& hist)
+{
+  hist.round();
+  while(__popcll(__ballot(!L.done)) >= target)
+  {
+    hist.inner_step(L);
+    if(!L.done && !(L.cur & BVH_LEAF))
+      lane_inner<false, TWO>(S, L, lds, spill, counters);
+    hist.leaf_step(L);
+    if(!L.done && (L.cur & BVH_LEAF))
+    {
+      lane_leaf<false, TWO>(S, L, lds, spill);
+      if(anyHitEnds && L.bslot != BVH_NONE)
+        L.done = true;
+    }
+  }
 }

@@ -175,41 +175,28 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
   uint32_t            spill[STACK_SPILL];
   uint32_t*           C     = rb.counts + bounce * CNT_STRIDE;
   const uint32_t      count = C[cntIn];
-  if(blockIdx.x > 0 && (unsigned long long)blockIdx.x * (TRACE_BLOCK * PT_MIN_GENERATIONS) >= count)
-    return;  // small queue: fewer waves with full lanes.  Spreading such a queue over MORE waves (8 .. 56 rays each, so that the SIMDs hold more
-             // resident waves and a wave waits for fewer rays) measured 4-7 % slower on the 20-step run and on an 8-GPU rank's shard
-             // (profiles/r04d_*): a wave-instruction costs the same with 16 lanes as with 64
-  uint32_t*           lds   = stack + threadIdx.x;
   TraceLane           L;
   RaySupply           rs;
-  // rays reserved per queue atomic: ~8 reservations per wave over the launch, at least `chunk`
-  rs.chunk = max(uint32_t(chunk), min(2048u, (count / (gridDim.x * 8u)) & ~63u));
+  MachineHist         hist;
+  if(!machine_enter(blockIdx.x, gridDim.x, count, chunk, rs, L))
+    return;
+  uint32_t*           lds   = stack + threadIdx.x;
   uint32_t            pslot = 0, seed = 0, nRays = 0, nAlpha = 0;
   bool                alive = false;
-  L.done                    = true;
-  L.cur                     = 0;
-#ifdef PT_HIST
-  unsigned long long hIter = 0, hInner = 0, hLeaf = 0, hService = 0, hBoth = 0, hInnerIt = 0, hLeafIt = 0;
-#endif
   for(;;)
   {
     // ---- service
     if(alive && L.done)
     {
       bool fallback = (L.flags & TF_SAW_FRAC) != 0;
-      if(!fallback && L.pass == 0 && (L.flags & TF_SAW_ZERO) && !pass_a_settles(L.bslot, L.bt, L.zeroMaxT, L.zeroMaxT2, L.zeroMaxT3, L.cnt))
-      {
+      if(needs_count_pass(L.flags, L.pass, L.bslot, L.bt, L.zeroMaxT, L.zeroMaxT2, L.zeroMaxT3, L.cnt))
         lane_begin_count<TWO>(L);  // stay alive: pass B runs in the same loop
-      }
       else
       {
         if(!fallback)
         {
-          uint32_t nDraw = L.cnt;  // pass A's count when it is final, else pass B's
-          if(L.bslot != BVH_NONE && !((L.bw >> 29) & TRI_OPAQUE))
-            ++nDraw;  // the certain non-opaque hit consumes its own (always passing) draw
-          uint32_t s2 = seed;
-          if(consume_rejected_draws(s2, nDraw))
+          uint32_t nDraw, s2;
+          if(settle_draws(L.bslot, L.bw, L.cnt, seed, nDraw, s2))  // L.cnt: pass A's count when it is final, else pass B's
           {
             store_hit(rb, pslot, L.bslot, L.bw, TWO, L.bt, L.bu, L.bv);
             if(nDraw)
@@ -229,10 +216,8 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
     const uint32_t qi = supply_next(rs, &C[cntChunk], count, !alive);
     if(qi != 0xffffffffu)
     {
-      pslot           = queueIn[qi];
-      const float4 dw = rb.ps.rayD[pslot];
-      seed            = __float_as_uint(dw.w);
-      lane_begin(L, xyz(rb.ps.rayO[pslot]), xyz(dw), PT_INFINITY, S.numTris == 0);
+      pslot = queueIn[qi];
+      lane_fetch_closest(S, rb, pslot, L, seed);
       alive = true;
       ++nRays;
       if(HEAT)
@@ -240,33 +225,9 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
     }
     if(!__ballot(alive))
       break;
-    // ---- run
-    const int target = rs.more ? minRun : 1;
-#ifdef PT_HIST
-    ++hService;
-#endif
-    while(__popcll(__ballot(!L.done)) >= target)
-    {
-#ifdef PT_HIST
-      const uint32_t ni = __popcll(__ballot(!L.done && !(L.cur & BVH_LEAF)));
-#endif
-      if(!L.done && !(L.cur & BVH_LEAF))
-        lane_inner<false, TWO>(S, L, lds, spill, rb.counters);
-#ifdef PT_HIST
-      const uint32_t nl = __popcll(__ballot(!L.done && (L.cur & BVH_LEAF)));
-      ++hIter; hInner += ni; hLeaf += nl; hBoth += (ni && nl) ? 1 : 0; hInnerIt += ni ? 1 : 0; hLeafIt += nl ? 1 : 0;
-#endif
-      if(!L.done && (L.cur & BVH_LEAF))
-        lane_leaf<false, TWO>(S, L, lds, spill);
-    }
+    machine_run<TWO>(S, L, lds, spill, rb.counters, rs.more ? minRun : 1, false, hist);
   }
-#ifdef PT_HIST
-  if((threadIdx.x & 63) == 0)
-  {
-    atomicAdd(&g_hist[5][0], hIter); atomicAdd(&g_hist[5][1], hInner); atomicAdd(&g_hist[5][2], hLeaf); atomicAdd(&g_hist[5][3], hService);
-    atomicAdd(&g_hist[5][4], hBoth); atomicAdd(&g_hist[5][5], hInnerIt); atomicAdd(&g_hist[5][6], hLeafIt);
-  }
-#endif
+  hist.flush(5);
   wave_add(&rb.counters->closestRays, nRays);
   wave_add(&rb.counters->alphaTests, nAlpha);
 }
@@ -325,14 +286,11 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_PACKET_WAVES_TWO : PT_PA
     uint32_t   seedOut = seed;
     if(valid && packet)
     {
-      redo = (h.flags & TF_SAW_FRAC) != 0 || ((h.flags & TF_SAW_ZERO) && !pass_a_settles(h.slot, h.t, h.zeroMaxT, h.zeroMaxT2, h.zeroMaxT3, h.count));
+      redo = (h.flags & TF_SAW_FRAC) != 0 || needs_count_pass(h.flags, 0, h.slot, h.t, h.zeroMaxT, h.zeroMaxT2, h.zeroMaxT3, h.count);
       if(!redo)
       {
-        uint32_t nDraw = h.count;
-        if(h.slot != BVH_NONE && !((h.w >> 29) & TRI_OPAQUE))
-          ++nDraw;
-        uint32_t s2 = seed;
-        if(consume_rejected_draws(s2, nDraw))
+        uint32_t nDraw, s2;
+        if(settle_draws(h.slot, h.w, h.count, seed, nDraw, s2))
         {
           store_hit(rb, slot, h.slot, h.w, TWO, h.t, h.u, h.v);
           if(nDraw && !regen)
@@ -458,22 +416,14 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
   uint32_t            spill[STACK_SPILL];
   uint32_t*           C     = rb.counts + bounce * CNT_STRIDE;
   const uint32_t      count = C[cntIn];
-  if(blockIdx.x > 0 && (unsigned long long)blockIdx.x * (TRACE_BLOCK * PT_MIN_GENERATIONS) >= count)
-    return;  // small queue: fewer waves with full lanes.  Spreading such a queue over MORE waves (8 .. 56 rays each, so that the SIMDs hold more
-             // resident waves and a wave waits for fewer rays) measured 4-7 % slower on the 20-step run and on an 8-GPU rank's shard
-             // (profiles/r04d_*): a wave-instruction costs the same with 16 lanes as with 64
-  uint32_t*           lds   = stack + threadIdx.x;
   TraceLane           L;
   RaySupply           rs;
-  // rays reserved per queue atomic: ~8 reservations per wave over the launch, at least `chunk`
-  rs.chunk = max(uint32_t(chunk), min(2048u, (count / (gridDim.x * 8u)) & ~63u));
+  MachineHist         hist;
+  if(!machine_enter(blockIdx.x, gridDim.x, count, chunk, rs, L))
+    return;
+  uint32_t*           lds   = stack + threadIdx.x;
   uint32_t            pslot = 0, seed = 0, nRays = 0, nAlpha = 0;
   bool                alive = false;
-  L.done                    = true;
-  L.cur                     = 0;
-#ifdef PT_HIST
-  unsigned long long hIter = 0, hInner = 0, hLeaf = 0, hService = 0, hBoth = 0, hInnerIt = 0, hLeafIt = 0;
-#endif
   for(;;)
   {
     // ---- service (see k_closest_p)
@@ -481,20 +431,15 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
     if(alive && L.done)
     {
       bool fallback = (L.flags & TF_SAW_FRAC) != 0;
-      if(!fallback && L.pass == 0 && (L.flags & TF_SAW_ZERO) && !pass_a_settles(L.bslot, L.bt, L.zeroMaxT, L.zeroMaxT2, L.zeroMaxT3, L.cnt))
-      {
+      if(needs_count_pass(L.flags, L.pass, L.bslot, L.bt, L.zeroMaxT, L.zeroMaxT2, L.zeroMaxT3, L.cnt))
         lane_begin_count<TWO>(L);
-      }
       else
       {
         bool inShadow = false;
         if(!fallback)
         {
-          uint32_t nDraw = L.cnt;  // zero-opacity candidates in front of the hit: one rejected draw each
-          if(L.bslot != BVH_NONE && !((L.bw >> 29) & TRI_OPAQUE))
-            ++nDraw;               // a certain non-opaque hit consumes its own (always passing) draw; an opaque one commits without
-          uint32_t s2 = seed;
-          if(consume_rejected_draws(s2, nDraw))
+          uint32_t nDraw, s2;
+          if(settle_draws(L.bslot, L.bw, L.cnt, seed, nDraw, s2))
           {
             seed     = variant == PT_VARIANT_RTX ? seed : s2;  // RTX: the any-hit shader draws from a copy (traceray_rtx.glsl:54-55)
             inShadow = L.bslot != BVH_NONE;
@@ -517,8 +462,7 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
     if(qi != 0xffffffffu)
     {
       pslot = queueIn[qi];
-      seed  = __float_as_uint(rb.ps.rayD[pslot].w);
-      lane_begin(L, xyz(rb.ps.rayO[pslot]), xyz(rb.ps.neeDir[pslot]), rb.ps.absorb[pslot].w, S.numTris == 0);
+      lane_fetch_shadow(S, rb, pslot, L, seed);
       alive = true;
       ++nRays;
       if(HEAT)
@@ -526,37 +470,9 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
     }
     if(!__ballot(alive))
       break;
-    // ---- run
-    const int target = rs.more ? minRun : 1;
-#ifdef PT_HIST
-    ++hService;
-#endif
-    while(__popcll(__ballot(!L.done)) >= target)
-    {
-#ifdef PT_HIST
-      const uint32_t ni = __popcll(__ballot(!L.done && !(L.cur & BVH_LEAF)));
-#endif
-      if(!L.done && !(L.cur & BVH_LEAF))
-        lane_inner<false, TWO>(S, L, lds, spill, rb.counters);
-#ifdef PT_HIST
-      const uint32_t nl = __popcll(__ballot(!L.done && (L.cur & BVH_LEAF)));
-      ++hIter; hInner += ni; hLeaf += nl; hBoth += (ni && nl) ? 1 : 0; hInnerIt += ni ? 1 : 0; hLeafIt += nl ? 1 : 0;
-#endif
-      if(!L.done && (L.cur & BVH_LEAF))
-      {
-        lane_leaf<false, TWO>(S, L, lds, spill);
-        if(S.allOpaque && L.bslot != BVH_NONE)
-          L.done = true;  // all-opaque scene: any hit inside (0, tmax) occludes and nothing draws -- the nearest one need not be found
-      }
-    }
+    machine_run<TWO>(S, L, lds, spill, rb.counters, rs.more ? minRun : 1, S.allOpaque, hist);
   }
-#ifdef PT_HIST
-  if((threadIdx.x & 63) == 0)
-  {
-    atomicAdd(&g_hist[6][0], hIter); atomicAdd(&g_hist[6][1], hInner); atomicAdd(&g_hist[6][2], hLeaf); atomicAdd(&g_hist[6][3], hService);
-    atomicAdd(&g_hist[6][4], hBoth); atomicAdd(&g_hist[6][5], hInnerIt); atomicAdd(&g_hist[6][6], hLeafIt);
-  }
-#endif
+  hist.flush(6);
   stage_flush(stage, nStage, queueOut, &C[CNT_STRIDE + CNT_IN]);
   wave_add(&rb.counters->shadowRays, nRays);
   wave_add(&rb.counters->alphaTests, nAlpha);
@@ -600,16 +516,14 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
   uint32_t*           C  = rb.counts + bounce * CNT_STRIDE;  // this bounce: shadow rays, paths without one
   uint32_t*           C1 = C + CNT_STRIDE;                   // the next bounce: its hit queue, its closest-hit fallbacks
   const uint32_t      nS = C[CNT_SHADOW], count = nS + C[CNT_NEXT];
-  if(blockIdx.x > 0 && (unsigned long long)blockIdx.x * (TRACE_BLOCK * PT_MIN_GENERATIONS) >= count)
+  TraceLane           L;
+  RaySupply           rs;
+  MachineHist         hist;  // (never flushed: g_hist has rows for the staged kernels only)
+  if(!machine_enter(blockIdx.x, gridDim.x, count, chunk, rs, L))
     return;
-  uint32_t* lds = stack + threadIdx.x;
-  TraceLane L;
-  RaySupply rs;
-  rs.chunk = max(uint32_t(chunk), min(2048u, (count / (gridDim.x * 8u)) & ~63u));
-  uint32_t pslot = 0, seed = 0, nShadow = 0, nClosest = 0, nAlpha = 0;
-  bool     alive = false, shadowRay = false;
-  L.done         = true;
-  L.cur          = 0;
+  uint32_t* lds   = stack + threadIdx.x;
+  uint32_t  pslot = 0, seed = 0, nShadow = 0, nClosest = 0, nAlpha = 0;
+  bool      alive = false, shadowRay = false;
   for(;;)
   {
     // ---- service
@@ -617,14 +531,12 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
     if(alive && L.done)
     {
       bool fallback = (L.flags & TF_SAW_FRAC) != 0;
-      if(!fallback && L.pass == 0 && (L.flags & TF_SAW_ZERO) && !pass_a_settles(L.bslot, L.bt, L.zeroMaxT, L.zeroMaxT2, L.zeroMaxT3, L.cnt))
+      if(needs_count_pass(L.flags, L.pass, L.bslot, L.bt, L.zeroMaxT, L.zeroMaxT2, L.zeroMaxT3, L.cnt))
         lane_begin_count<TWO>(L);  // stay alive: pass B runs in the same loop
       else
       {
-        uint32_t s2 = seed, nDraw = L.cnt;
-        if(L.bslot != BVH_NONE && !((L.bw >> 29) & TRI_OPAQUE))
-          ++nDraw;  // the certain non-opaque hit consumes its own (always passing) draw
-        if(!fallback && !consume_rejected_draws(s2, nDraw))
+        uint32_t nDraw = 0, s2 = seed;
+        if(!fallback && !settle_draws(L.bslot, L.bw, L.cnt, seed, nDraw, s2))
           fallback = true;
         if(!fallback)
           nAlpha += nDraw;
@@ -639,7 +551,7 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
           {
             seed = variant == PT_VARIANT_RTX ? seed : s2;  // RTX: the any-hit shader draws from a copy (traceray_rtx.glsl:54-55)
             if(finish_bounce_core(rb, pslot, L.bslot != BVH_NONE, seed))
-            {  // the path lives: its next closest-hit ray (written by k_shade) starts in this lane right away
+            {  // the path lives: its next closest-hit ray (written by k_shade) starts in this lane right away, `seed` is its RNG state already
               lane_begin(L, xyz(rb.ps.rayO[pslot]), xyz(rb.ps.rayD[pslot]), PT_INFINITY, S.numTris == 0);
               shadowRay = false;
               ++nClosest;
@@ -671,35 +583,20 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
       if(shadowRay)
       {
         pslot = queueS[qi];
-        seed  = __float_as_uint(rb.ps.rayD[pslot].w);
-        lane_begin(L, xyz(rb.ps.rayO[pslot]), xyz(rb.ps.neeDir[pslot]), rb.ps.absorb[pslot].w, S.numTris == 0);
+        lane_fetch_shadow(S, rb, pslot, L, seed);
         ++nShadow;
       }
       else
       {
-        pslot           = queueN[qi - nS];
-        const float4 dw = rb.ps.rayD[pslot];
-        seed            = __float_as_uint(dw.w);
-        lane_begin(L, xyz(rb.ps.rayO[pslot]), xyz(dw), PT_INFINITY, S.numTris == 0);
+        pslot = queueN[qi - nS];
+        lane_fetch_closest(S, rb, pslot, L, seed);
         ++nClosest;
       }
       alive = true;
     }
     if(!__ballot(alive))
       break;
-    // ---- run
-    const int target = rs.more ? minRun : 1;
-    while(__popcll(__ballot(!L.done)) >= target)
-    {
-      if(!L.done && !(L.cur & BVH_LEAF))
-        lane_inner<false, TWO>(S, L, lds, spill, rb.counters);
-      if(!L.done && (L.cur & BVH_LEAF))
-      {
-        lane_leaf<false, TWO>(S, L, lds, spill);
-        if(shadowRay && S.allOpaque && L.bslot != BVH_NONE)
-          L.done = true;  // all-opaque scene: any hit inside (0, tmax) occludes and nothing draws -- the nearest one need not be found
-      }
-    }
+    machine_run<TWO>(S, L, lds, spill, rb.counters, rs.more ? minRun : 1, shadowRay && S.allOpaque, hist);
   }
   stage_flush(stage, nStage, queueHit, &C1[CNT_IN]);
   wave_add(&rb.counters->shadowRays, nShadow);

@@ -1,6 +1,6 @@
 // Settling ONE ray per lane: the closest-hit ray (trace contract T5) and the shadow ray (T6) of a path, from the path state in HBM to the hit
 // record / the verdict, through the two-pass stochastic alpha of pt_trace.h with its exact key-ordered fallback.  These are the bodies k_tail
-// runs per lane (pt_render.hip); the exact-fallback kernels k_closest_x / k_shadow_x spell the same steps out per stage.
+// runs per lane (pt_render.hip); the exact-fallback kernels k_closest_x / k_shadow_x / k_trace_x call the same exact loops (settle_*_exact) per stage.
 // Plain inline functions of (scene, path state, slot): tests/cpp/trace_host.cpp compiles them for the host and holds them, ray by ray, to
 // the contract's exact loop -- hits AND the RNG state afterwards (tests/test_trace_host.py).
 #pragma once
@@ -18,7 +18,7 @@ PT_DEV void store_hit(const RB& rb, uint32_t slot, uint32_t bslot, uint32_t bw, 
     rb.ps.hit[slot] = make_float4(t, __uint_as_float(two ? (bw & TRI_INDEX_MASK) : bslot), u, v);
 }
 
-// The exact key-ordered loops (trace contract T5 / T6; k_closest_x / k_shadow_x spell the same steps out per stage): what a ray falls back to when the
+// The exact key-ordered loops (trace contract T5 / T6; k_closest_x / k_shadow_x / k_trace_x run nothing else): what a ray falls back to when the
 // two-pass scheme cannot settle it -- a candidate of fractional opacity in front of the hit, or a rejected-candidate draw of exactly 0.0.
 // `seed`: the path's RNG state before the ray's first draw; closest: hit record and the state afterwards go to the path state.
 template <bool TWO, class RB>
@@ -86,22 +86,19 @@ PT_DEV void tail_closest(const DeviceScene& S, const RenderBuffers& rb, uint32_t
   RayHit         h;
   bool           dummy;
   traverse<TM_CLOSEST, TWO>(S, o, d, PT_INFINITY, 0.0f, 0xffffffffu, 0u, stack, h, dummy, rb.counters);
-  bool       fallback = (h.flags & TF_SAW_FRAC) != 0;
-  const bool passB    = !fallback && (h.flags & TF_SAW_ZERO) && !pass_a_settles(h.slot, h.t, h.zeroMaxT, h.zeroMaxT2, h.zeroMaxT3, h.count);
-  uint32_t   nDraw    = h.count;
-  if(passB)
+  bool     fallback = (h.flags & TF_SAW_FRAC) != 0;
+  uint32_t nCount   = h.count;
+  if(needs_count_pass(h.flags, 0, h.slot, h.t, h.zeroMaxT, h.zeroMaxT2, h.zeroMaxT3, nCount))
   {
     RayHit c;
     traverse<TM_COUNT, TWO>(S, o, d, h.slot == BVH_NONE ? PT_INFINITY : h.t, 0.0f, 0xffffffffu, h.slot == BVH_NONE ? 0u : (h.w & TRI_INDEX_MASK), stack, c, dummy, rb.counters);
     fallback = (c.flags & TF_SAW_FRAC) != 0;
-    nDraw    = c.count;
+    nCount   = c.count;
   }
   if(!fallback)
   {
-    if(h.slot != BVH_NONE && !((h.w >> 29) & TRI_OPAQUE))
-      ++nDraw;
-    uint32_t s2 = seed;
-    if(consume_rejected_draws(s2, nDraw))
+    uint32_t nDraw, s2;
+    if(settle_draws(h.slot, h.w, nCount, seed, nDraw, s2))
     {
       store_hit(rb, slot, h.slot, h.w, TWO, h.t, h.u, h.v);
       if(nDraw)
@@ -125,22 +122,19 @@ PT_DEV bool tail_shadow(const DeviceScene& S, const RenderBuffers& rb, uint32_t 
   bool           dummy;
   RayHit         h;
   traverse<TM_CLOSEST, TWO>(S, o, d, maxDist, 0.0f, 0xffffffffu, 0u, stack, h, dummy, rb.counters);
-  bool       fallback = (h.flags & TF_SAW_FRAC) != 0;
-  const bool passB    = !fallback && (h.flags & TF_SAW_ZERO) && !pass_a_settles(h.slot, h.t, h.zeroMaxT, h.zeroMaxT2, h.zeroMaxT3, h.count);
-  uint32_t   nDraw    = h.count;
-  if(passB)
+  bool     fallback = (h.flags & TF_SAW_FRAC) != 0;
+  uint32_t nCount   = h.count;
+  if(needs_count_pass(h.flags, 0, h.slot, h.t, h.zeroMaxT, h.zeroMaxT2, h.zeroMaxT3, nCount))
   {
     RayHit c;
     traverse<TM_COUNT, TWO>(S, o, d, h.slot == BVH_NONE ? maxDist : h.t, 0.0f, 0xffffffffu, h.slot == BVH_NONE ? 0u : (h.w & TRI_INDEX_MASK), stack, c, dummy, rb.counters);
     fallback = (c.flags & TF_SAW_FRAC) != 0;
-    nDraw    = c.count;
+    nCount   = c.count;
   }
   if(!fallback)
   {
-    if(h.slot != BVH_NONE && !((h.w >> 29) & TRI_OPAQUE))
-      ++nDraw;
-    uint32_t s2 = seed;
-    if(consume_rejected_draws(s2, nDraw))
+    uint32_t nDraw, s2;
+    if(settle_draws(h.slot, h.w, nCount, seed, nDraw, s2))
     {
       seed = variant == PT_VARIANT_RTX ? seed : s2;  // RTX: the any-hit shader draws from a copy (traceray_rtx.glsl:54-55)
       nAlpha += nDraw;

@@ -613,3 +613,26 @@ PT_DEV bool consume_rejected_draws(uint32_t& seed, uint32_t n)
       return false;
   return true;
 }
+
+// ---- the two-pass settle rule (trace contract T5 / T6), stated once ------------------------------------------------------------------------
+// Every place that settles a ray -- the service round of the persistent kernels (pt_machine.h: lane_settle), the packet kernel k_closest_k, the
+// per-lane bodies of k_tail (pt_settle.h) -- asks these two functions, on plain values, so that a TraceLane and a RayHit can both feed them.
+//
+// May pass A stand?  True: the ray has to run the counting pass B -- no candidate of fractional opacity was seen (that ray goes to the exact
+// loop whatever is counted), this WAS pass A, it saw zero-opacity candidates, and their t's do not show that all of them lie in front of the hit.
+// `count` is corrected in place when pass A can stand with one or two candidates behind the hit (pass_a_settles).
+PT_DEV bool needs_count_pass(uint32_t flags, int pass, uint32_t bslot, float bt, float z1, float z2, float z3, uint32_t& count)
+{
+  return !(flags & TF_SAW_FRAC) && pass == 0 && (flags & TF_SAW_ZERO) && !pass_a_settles(bslot, bt, z1, z2, z3, count);
+}
+// The draws of a ray without a fractional candidate: one rejected draw per counted zero-opacity candidate in front of the hit, plus the certain
+// non-opaque hit's own (always passing) one; an opaque hit commits without.  s2: `seed` after them.  False: one of the rejected draws is exactly
+// 0.0 -- the ray goes to the exact key-ordered loop with `seed` untouched.
+PT_DEV bool settle_draws(uint32_t bslot, uint32_t bw, uint32_t count, uint32_t seed, uint32_t& nDraw, uint32_t& s2)
+{
+  nDraw = count;
+  if(bslot != BVH_NONE && !((bw >> 29) & TRI_OPAQUE))
+    ++nDraw;
+  s2 = seed;
+  return consume_rejected_draws(s2, nDraw);
+}
