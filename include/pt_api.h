@@ -14,7 +14,7 @@
  *    pt_get_stats and pt_synchronize wait for it.
  *  - Traversal-stack overflow: a ray whose walk needs more than 64 stack entries drops a subtree, so the image misses geometry.  Once
  *    such an overflow has been counted, every call that hands out results returns PT_ERR_STATE ("BVH traversal stack overflowed ...")
- *    instead of PT_OK: pt_synchronize, pt_read_accum, pt_tonemap, pt_tonemap_zoom, pt_tonemap_end, pt_pick, pt_local_shard,
+ *    instead of PT_OK: pt_synchronize, pt_read_accum, pt_tonemap, pt_tonemap_zoom, pt_tonemap_end, pt_pick, pt_trace_rays, pt_local_shard,
  *    pt_gather_shards and pt_get_stats, and pt_tonemap_begin once the overflow is known (it then enqueues nothing).  The state stays
  *    until pt_reset_stats or the next pt_build_accel (a new scene) clears it; images begun before the clear no longer report it.
  *  - there is no CPU fallback: without a gfx950 device pt_create fails with PT_ERR_NO_DEVICE.
@@ -258,6 +258,29 @@ int pt_sampler_from_gltf(int has_sampler, int gltf_mag, int gltf_min, int gltf_w
  * face culling or alpha test, like the picker's flag-less traceRayEXT.  Synchronous: waits for every frame in flight, then reports a
  * traversal-stack overflow of those frames or of its own ray with PT_ERR_STATE. */
 int pt_pick(pt_context* ctx, float pick_x, float pick_y, const float view_inverse[16], const float proj_inverse[16], pt_PickResult* out);
+
+/* Batched ray queries against the scene's acceleration structure (no reference counterpart beyond screenPicking: what a caller does with a
+ * renderer's scene besides rendering -- visibility and ambient-occlusion baking, light-map sample placement, many picks at once, line-of-sight
+ * tests, collision probes).  Traces rays[0 .. n) and writes hits_per_ray results per ray to hits[i * hits_per_ray ..].  Each kind is one piece of
+ * the trace contract:
+ *   PT_RAYS_CLOSEST    the path tracer's closest-hit ray (T5): face culling by the instance flags, opaque candidates commit, non-opaque ones
+ *                      draw in key order from `seed`; `seed` out is the state after the draws.  Unbounded like traceray_rq.glsl's ClosestHit:
+ *                      tmax is IGNORED (a caller who wants a bound compares t).
+ *   PT_RAYS_OCCLUDED   the shadow ray (T6), bounded by tmax: PT_RAY_HIT means in shadow, no hit field is filled.  `seed` follows the context's
+ *                      variant: under PT_VARIANT_RTX it comes back untouched.
+ *   PT_RAYS_NEAREST    pt_pick's query: every triangle counts (no culling, no alpha), the nearest key inside (0, tmax).
+ *   PT_RAYS_CANDIDATES the first hits_per_ray (1 .. PT_RAYS_MAX_HITS) candidates inside (0, tmax) in key order (t, world triangle index), with
+ *                      culling and without alpha; unused entries are misses.  Every other kind requires hits_per_ray == 1.
+ * A miss is t = u = v = 0, instanceID = 0xffffffff, primitiveID = instanceCustomIndex = -1; ids mean what they mean in pt_PickResult.  With
+ * pt_use_any_hit(0) every triangle is opaque, so no kind draws.  A ray with a non-finite origin or direction component, a zero direction or (bounded
+ * kinds) a NaN tmax is not walked: its results are misses with PT_RAY_INVALID set and `seed` unchanged.  tmax <= 0 is an empty range, a plain miss.
+ * flags: PT_RAYS_DEVICE -- rays and hits are device pointers on the context's GPU, 16-byte aligned, read and written in place.  Without it they
+ * are host arrays, staged in chunks of PT_QUERY_CHUNK records through two device buffers the context allocates on first use.
+ * Needs pt_set_scene and pt_build_accel (PT_ERR_STATE before), no pt_resize.  Synchronous like pt_pick: waits for the frames in flight, runs on
+ * the context's stream and reports a traversal-stack overflow of those frames or of its own rays with PT_ERR_STATE.  n == 0: PT_OK, nothing is
+ * launched.  Null pointers with n > 0, an unknown kind or flag bit, a bad hits_per_ray or a misaligned device pointer: PT_ERR_INVALID, nothing is
+ * launched.  A query touches neither the accumulation image, the path state, the frame slots nor any pt_Stats field. */
+int pt_trace_rays(pt_context* ctx, int kind, uint32_t flags, uint64_t n, const pt_Ray* rays, pt_RayHit* hits, uint32_t hits_per_ray);
 
 /* Measures, on this device, the two ceilings the measurement contract prices kernels against (no reference counterpart): VALU issue
  * (independent wave64 v_fma_f32 at 8 waves per SIMD on every CU, wave-instructions per second) and HBM streaming (float4 copy and

@@ -102,6 +102,10 @@ public:
   }
   // SampleExample::screenPicking (src/sample_example.cpp:468-511)
   bool pick(float x, float y, const pt_SceneCamera& cam, pt_PickResult* out) { return check(pt_pick(m_ctx, x, y, cam.viewInverse, cam.projInverse, out)); }
+  // many screenPicking-style rays at once (and the path tracer's own closest-hit / shadow rays): pt_trace_rays on host arrays ...
+  bool traceRays(int kind, uint64_t n, const pt_Ray* rays, pt_RayHit* hits, uint32_t hitsPerRay = 1) { return check(pt_trace_rays(m_ctx, kind, 0u, n, rays, hits, hitsPerRay)); }
+  // ... and on 16-byte aligned device memory of the context's GPU, in place
+  bool traceRaysDevice(int kind, uint64_t n, const pt_Ray* dRays, pt_RayHit* dHits, uint32_t hitsPerRay = 1) { return check(pt_trace_rays(m_ctx, kind, PT_RAYS_DEVICE, n, dRays, dHits, hitsPerRay)); }
   void readAccum(float* rgba32f) { check(pt_read_accum(m_ctx, rgba32f)); }
   void writeAccum(const float* rgba32f) { check(pt_write_accum(m_ctx, rgba32f)); }  // checkpoint restore
   void useAnyHit(bool enable) { check(pt_use_any_hit(m_ctx, enable ? 1 : 0)); }  // RtxPipeline::useAnyHit

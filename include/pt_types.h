@@ -232,6 +232,29 @@ typedef struct pt_PickResult {
   float    baryCoord[3];       /* (1 - u - v, u, v) */
 } pt_PickResult;
 
+/* pt_trace_rays: one ray in, hits_per_ray results out (32 bytes each).  The ray kinds are pieces of the trace contract (DESIGN.md section 3,
+ * "Ray queries"); what every field means per kind is stated at pt_trace_rays in pt_api.h. */
+typedef struct pt_Ray {
+  float    origin[3];
+  float    tmax;       /* exclusive upper bound of t for the bounded kinds (ignored by PT_RAYS_CLOSEST); <= 0: empty range, a plain miss */
+  float    direction[3]; /* not normalised by the library: t is in units of its length */
+  uint32_t seed;       /* RNG state before the ray's alpha draws */
+} pt_Ray;
+typedef struct pt_RayHit {
+  float    t, u, v;              /* hit distance and barycentrics (weights 1 - u - v, u, v); 0 on a miss */
+  uint32_t instanceID;           /* node (TLAS instance) index as in pt_PickResult, 0xffffffff: miss */
+  int32_t  primitiveID;          /* triangle inside the prim-mesh, -1: miss */
+  int32_t  instanceCustomIndex;  /* prim-mesh index, -1: miss */
+  uint32_t seed;                 /* RNG state after the ray's alpha draws (the input where the kind draws nothing) */
+  uint32_t status;               /* PT_RAY_HIT | PT_RAY_INVALID */
+} pt_RayHit;
+enum { PT_RAYS_CLOSEST = 0, PT_RAYS_OCCLUDED = 1, PT_RAYS_NEAREST = 2, PT_RAYS_CANDIDATES = 3 }; /* pt_trace_rays kind */
+#define PT_RAY_HIT 1u          /* pt_RayHit::status bit 0: something was hit / the ray is occluded */
+#define PT_RAY_INVALID 2u      /* bit 1: the ray was not walked (non-finite origin / direction, zero direction, NaN tmax of a bounded kind) */
+#define PT_RAYS_DEVICE 1u      /* pt_trace_rays flags bit 0: rays and hits are device pointers on the context's GPU */
+#define PT_RAYS_MAX_HITS 16u   /* largest hits_per_ray of PT_RAYS_CANDIDATES */
+#define PT_QUERY_CHUNK (1u << 20) /* host arrays are staged through two device buffers of this many records (32 MB each) */
+
 /* Counters the measurement contract needs; all totals since pt_reset_stats. */
 typedef struct pt_Stats {
   uint64_t samples;          /* pixel-samples rendered */
@@ -293,6 +316,7 @@ static_assert(sizeof(pt_Tonemapper) == 48, "Tonemapper");
 static_assert(sizeof(pt_SunAndSky) == 96, "SunAndSky");
 static_assert(sizeof(pt_PrimMesh) == 20, "PrimMesh");
 static_assert(sizeof(pt_Node) == 68, "Node");
+static_assert(sizeof(pt_Ray) == 32 && sizeof(pt_RayHit) == 32, "Ray / RayHit");
 #endif
 
 #endif /* PT_TYPES_H */

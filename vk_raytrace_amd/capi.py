@@ -13,6 +13,11 @@ from . import host_device as hd
 
 PT_VARIANT_RAYQUERY, PT_VARIANT_RTX = 0, 1
 PT_ACCEL_FLAT, PT_ACCEL_TWO_LEVEL = 0, 1
+PT_RAYS_CLOSEST, PT_RAYS_OCCLUDED, PT_RAYS_NEAREST, PT_RAYS_CANDIDATES = 0, 1, 2, 3  # pt_trace_rays kinds (include/pt_types.h)
+PT_RAY_HIT, PT_RAY_INVALID = 1, 2  # pt_RayHit.status bits
+PT_RAYS_DEVICE = 1  # pt_trace_rays flag: rays / hits are device pointers
+PT_RAYS_MAX_HITS = 16
+PT_QUERY_CHUNK = 1 << 20  # records per staging buffer of the host-pointer path
 PT_DISPLAY_RING = 8  # images pt_tonemap_begin may have pending (include/pt_api.h)
 PT_FN = {"sin": 0, "cos": 1, "tan": 2, "asin": 3, "acos": 4, "atan2": 5, "exp": 6, "log": 7, "pow": 8}
 PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_ERR_STATE, PT_ERR_OOM, PT_ERR_UNAVAILABLE = 0, -1, -2, -3, -4, -5, -6
@@ -64,6 +69,7 @@ API = [
     ("pt_gather_shards", C.c_int, [_P, _P, C.c_int]),
     ("pt_gather_finish", C.c_int, [_P]),
     ("pt_pick", C.c_int, [_P, C.c_float, C.c_float, _P, _P, C.POINTER(hd.PickResult)]),
+    ("pt_trace_rays", C.c_int, [_P, C.c_int, C.c_uint32, C.c_uint64, _P, _P, C.c_uint32]),
     ("pt_fpmath_eval", C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P]),
     ("pt_measure_peaks", C.c_int, [_P, C.POINTER(hd.Peaks)]),
     ("pt_set_profiling", C.c_int, [_P, C.c_int]),

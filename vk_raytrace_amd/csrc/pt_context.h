@@ -119,6 +119,7 @@ struct pt_context {
   hipEvent_t lastAccum   = nullptr;  // accumDone of the most recent frame (nullptr: none pending)
   DevBuf   dFrame, dSlotTile, dCounters;
   DevBuf   dPick;
+  DevBuf   dQueryRays, dQueryHits;  // pt_trace_rays with host arrays: staging buffers of PT_QUERY_CHUNK records each, allocated on first use
   DevBuf   dRowMajor, dRgba8, dMean, dMips, dGather, dFullTiles, dFullSlotTile, dTileLocalIndex;
   bool     haveFull = false;
   // pipelined display (pt_tonemap_begin / pt_tonemap_end): a ring of pinned host images, each with the event that says its copy has landed

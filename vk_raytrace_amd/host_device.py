@@ -104,6 +104,17 @@ class PickResult(C.Structure):
                 ("instanceID", C.c_uint32), ("instanceCustomIndex", C.c_int32), ("baryCoord", C.c_float * 3)]
 
 
+class Ray(C.Structure):
+    """pt_Ray (pt_trace_rays): tmax bounds every kind but PT_RAYS_CLOSEST; seed is the RNG state before the ray's alpha draws"""
+    _fields_ = [("origin", C.c_float * 3), ("tmax", C.c_float), ("direction", C.c_float * 3), ("seed", C.c_uint32)]
+
+
+class RayHit(C.Structure):
+    """pt_RayHit: ids as in PickResult; a miss is t = u = v = 0, instanceID = 0xffffffff, primitiveID = instanceCustomIndex = -1"""
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("instanceID", C.c_uint32), ("primitiveID", C.c_int32), ("instanceCustomIndex", C.c_int32),
+                ("seed", C.c_uint32), ("status", C.c_uint32)]
+
+
 class Peaks(C.Structure):
     """pt_Peaks (pt_measure_peaks): ceilings measured on the device"""
     _fields_ = [("valuWaveInstrPerSec", C.c_double), ("hbmCopyBytesPerSec", C.c_double), ("hbmReadBytesPerSec", C.c_double), ("computeUnits", C.c_int32),
@@ -130,8 +141,11 @@ class Stats(C.Structure):
 assert C.sizeof(RtxState) == 48 and C.sizeof(SceneCamera) == 140 and C.sizeof(VertexAttributes) == 32
 assert C.sizeof(GltfShadeMaterial) == 216 and C.sizeof(Light) == 64 and C.sizeof(EnvAccel) == 16
 assert C.sizeof(Tonemapper) == 48 and C.sizeof(SunAndSky) == 96 and C.sizeof(PrimMesh) == 20 and C.sizeof(Node) == 68
+assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
 
 vertex_dtype = np.dtype(VertexAttributes)
+ray_dtype = np.dtype(Ray)
+rayhit_dtype = np.dtype(RayHit)
 material_dtype = np.dtype(GltfShadeMaterial)
 light_dtype = np.dtype(Light)
 primmesh_dtype = np.dtype(PrimMesh)

@@ -166,6 +166,33 @@ class HipRenderer(Renderer):
         self._check(self._lib.pt_pick(self._ctx, float(x), float(y), vi, pi, C.byref(out)))
         return out
 
+    def trace_rays(self, kind, origins, directions, tmax=None, seeds=None, hits_per_ray=1):
+        """pt_trace_rays on host arrays: `kind` is capi.PT_RAYS_CLOSEST / OCCLUDED / NEAREST / CANDIDATES; origins, directions: (n, 3); tmax (scalar
+        or (n,), default +inf: unbounded) bounds every kind but CLOSEST; seeds (n,) uint32 (default 0) feed the alpha draws.  Returns a structured
+        array (hd.rayhit_dtype) of shape (n,), or (n, hits_per_ray) for CANDIDATES."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("trace_rays: origins and directions differ in length")
+        rays = np.zeros(len(o), hd.ray_dtype)
+        rays["origin"], rays["direction"] = o, d
+        rays["tmax"] = np.inf if tmax is None else np.asarray(tmax, np.float32)
+        rays["seed"] = 0 if seeds is None else np.asarray(seeds, np.uint32)
+        return self.trace_ray_records(kind, rays, hits_per_ray)
+
+    def trace_ray_records(self, kind, rays, hits_per_ray=1):
+        """pt_trace_rays on an array of hd.ray_dtype records (what trace_rays assembles)"""
+        rays = np.ascontiguousarray(rays, hd.ray_dtype)
+        hits = np.zeros((len(rays), int(hits_per_ray)), hd.rayhit_dtype)
+        self._check(self._lib.pt_trace_rays(self._ctx, int(kind), 0, len(rays), rays.ctypes.data, hits.ctypes.data, int(hits_per_ray)))
+        return hits if int(kind) == capi.PT_RAYS_CANDIDATES else hits[:, 0]
+
+    def trace_rays_device(self, kind, rays_ptr, hits_ptr, n, hits_per_ray=1):
+        """pt_trace_rays with PT_RAYS_DEVICE: rays_ptr / hits_ptr are plain integers, the addresses of n pt_Ray and n * hits_per_ray pt_RayHit records
+        in the memory of the context's GPU (16-byte aligned), e.g. a torch tensor's data_ptr().  The caller owns the memory and keeps it alive;
+        the results are in place when the call returns."""
+        self._check(self._lib.pt_trace_rays(self._ctx, int(kind), capi.PT_RAYS_DEVICE, int(n), C.c_void_p(int(rays_ptr)), C.c_void_p(int(hits_ptr)), int(hits_per_ray)))
+
     def tonemap(self, tm: hd.Tonemapper, display_size=None):
         """RenderOutput::genMipmap + run.  display_size (W, H): the viewport while de-scaling (Tonemapper.zoom = 1 / level)."""
         w, h = display_size or self.size
