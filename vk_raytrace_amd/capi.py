@@ -93,6 +93,7 @@ DEBUG_API = [
     ("pt_debug_texture_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h texture_probe, on the context's scene: (ctx, kind, n, in, in_stride, out, out_stride)
     ("pt_debug_surface_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h surface_probe, on the context's scene: (ctx, kind, n, in, in_stride, out, out_stride); 1: no such data
     ("pt_debug_trace_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h trace_probe, every load inside the row: (ctx, kind, n, in, in_stride, out, out_stride)
+    ("pt_debug_bounce_counts", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[max_bounces][16], max_bounces) -> staged bounces of the newest finished launch sequence
 ]
 
 _lib = None

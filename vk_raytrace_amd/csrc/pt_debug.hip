@@ -318,3 +318,23 @@ extern "C" __attribute__((visibility("default"))) int pt_debug_display_level(pt_
   rc = check_traversal(c);
   return rc != PT_OK ? rc : mv.n;
 }
+// The per-bounce counter block (pt_internal.h CNT_*, CNT_STRIDE words per bounce) of the newest launch sequence that has finished, as it came back for the
+// queue-size feedback: queue sizes, the rays the packet stage handed on (CNT_REDO, CNT_HANDOVER) and the rays sent to the exact loops.  Launches what is
+// pending and waits.  Returns the number of bounces the sequence ran staged (at most max_bounces are copied); 0: no sequence has run.  Not part of the ABI.
+extern "C" __attribute__((visibility("default"))) int pt_debug_bounce_counts(pt_context* c, uint32_t* out, int max_bounces)
+{
+  CTX_CHECK(c);
+  if(!out || max_bounces < 0)
+    return c->fail(PT_ERR_INVALID, "pt_debug_bounce_counts: bad arguments");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_all(c));
+  const pt_context::FrameSlot* newest = nullptr;
+  for(const pt_context::FrameSlot& fs : c->slots)
+    if(fs.hCounts && fs.countsSeq > 0 && (!newest || fs.countsSeq > newest->countsSeq))
+      newest = &fs;
+  if(!newest)
+    return 0;
+  const int n = std::min(newest->countsDepths, PT_MAX_DEPTH);
+  std::copy(newest->hCounts, newest->hCounts + size_t(CNT_STRIDE) * size_t(std::min(n, max_bounces)), out);
+  return n;
+}

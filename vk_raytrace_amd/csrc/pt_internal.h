@@ -91,6 +91,8 @@ struct PtTuning {
   int fuse                 = 1;    // shadow rays of bounce b and closest-hit rays of bounce b + 1 share one persistent launch (k_trace_p): 1 = launch sequences of ONE frame
                                    // (the display loop), 2 = always, 0 = never (the round-4 chain)
   int regen                = 1;    // bounce 0: the packet kernel computes the camera rays itself (k_generate only builds the queue); 0: k_generate writes them
+  int handover             = 1;    // packet stage: a ray that needs the count pass enters it on the trace machine with the packet's pass-A hit, and a ray known to need the exact
+                                   // loop goes straight to it (pt_render.hip k_closest_k); 0: both are redone from the root per lane (the A/B runs and the invariance tests)
   int texGroups            = 1;    // the textures a material samples with one (u, v) are also stored interleaved when they share size and sampler (pt_device.h TexRec::tiled)
   int texTile              = 1;    // RGBA8 images whose size allows it are stored block-linear (8 x 4-texel tiles = one 128-byte line; pt_device.h tex_index)
   int blasWorkers          = 8;    // two-level build: host threads (own stream + arena each) that build the BLASes concurrently
@@ -190,6 +192,7 @@ void pt_launch_shade_tris(hipStream_t stream, uint32_t n, const TriRec* tris, co
 #define CNT_REDO 6           // size of queueR
 #define CNT_CHUNK_REDO 7     // ray-supply chunk counter of k_closest_p on queueR
 #define CNT_NEXT 8                // fused stage (k_trace_p): size of the queue of paths k_shade sent on without a shadow ray
+#define CNT_HANDOVER 9            // entries of queueR the packet kernel handed over with its pass-A hit (QUEUE_HANDOVER); statistics only
 #define CNT_CHUNK_TAIL 10         // path-supply chunk counter of k_tail (the bounce it starts at)
 #define PT_MAX_DEPTH 256
 #define PT_MAX_INFLIGHT 8
@@ -209,7 +212,7 @@ struct RenderBuffersT {
   uint32_t* queueS;    // paths with a shadow ray
   uint32_t* queueX;    // exact-fallback queues (normally empty)
   uint32_t* queueX2;
-  uint32_t* queueR;    // rays the packet kernel could not settle (redone per lane on the trace machine)
+  uint32_t* queueR;    // rays the packet kernel could not settle (the trace machine redoes them per lane, or runs pass B of those marked QUEUE_HANDOVER)
   uint32_t* counts;    // (PT_MAX_DEPTH + 2) x CNT_STRIDE device counters
   uint32_t* countsDone;  // the counter block of the latest finished sample pass (k_accumulate copies it here and clears `counts`)
   float4*   frame;     // accumulation tiles, slot order

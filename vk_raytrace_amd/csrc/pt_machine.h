@@ -316,6 +316,18 @@ PT_DEV void lane_fetch_closest(const DeviceScene& S, const RB& rb, uint32_t pslo
   seed            = __float_as_uint(dw.w);
   lane_begin(L, xyz(rb.ps.rayO[pslot]), xyz(dw), PT_INFINITY, S.numTris == 0);
 }
+// A lane takes over a closest-hit ray whose pass A the packet kernel ran (pt_settle.h store_handover): the ray as above, the certain hit from the hit
+// record and rayO.w, and straight into pass B -- where lane_begin_count would have put the lane after a pass A of its own.  In the two-level form the
+// record names the world triangle, not the leaf slot: bslot then only says "a hit" (nothing of pass B or the settle rule reads more of it).
+template <bool TWO, class RB>
+PT_DEV void lane_fetch_handover(const DeviceScene& S, const RB& rb, uint32_t pslot, TraceLane& L, uint32_t& seed)
+{
+  const float4 dw = rb.ps.rayD[pslot], ow = rb.ps.rayO[pslot], h = rb.ps.hit[pslot];
+  seed            = __float_as_uint(dw.w);
+  lane_begin(L, xyz(ow), xyz(dw), PT_INFINITY, false);
+  L.bt = h.x; L.bu = h.z; L.bv = h.w; L.bslot = __float_as_uint(h.y); L.bw = __float_as_uint(ow.w);
+  lane_begin_count<TWO>(L);
+}
 template <class RB>
 PT_DEV void lane_fetch_shadow(const DeviceScene& S, const RB& rb, uint32_t pslot, TraceLane& L, uint32_t& seed)
 {

@@ -8,9 +8,11 @@
 //   k_generate      seed (pathtrace.comp:97), jitter + camera ray (pathtrace.glsl:348-372)      all paths of the frame batch
 //   per bounce:
 //   k_closest_k     bounce 0: ClosestHit incl. stochastic alpha (traceray_rq.glsl:108-147) as one packet traversal per
-//                   wavefront (pt_packet.h); rays it cannot settle go to queueR                     queue[in] -> queueR
-//   k_closest_p     bounce >= 1 and queueR: the same per lane, persistent wavefronts on the refilling
-//                   trace machine (pt_machine.h)                                                   queue[in] | queueR
+//                   wavefront (pt_packet.h); a ray it cannot settle goes on with what is known of it: its pass-A hit
+//                   (count pass left: queueR, marked), nothing (packet not traversed: queueR), or straight to
+//                   the exact loop (queueX)                                                        queue[in] -> queueR | queueX
+//   k_closest_p     bounce >= 1: the same per lane, persistent wavefronts on the refilling trace machine (pt_machine.h)
+//   k_closest_r     the same body on queueR: marked entries start in pass B with the packet's hit  queue[in] | queueR
 //   k_shade         miss/env, GetShadeState, material, emission, absorption, DirectLight,
 //                   BSDF sample, throughput, next ray (pathtrace.glsl:201-325); Russian roulette
 //                   right away for paths without a shadow ray                                    queue[in] -> queueS | queue[out]
@@ -167,8 +169,10 @@ PT_DEV void wave_add(unsigned long long* ctr, uint32_t v)
 // waits for the next service round instead of dragging ~200 instructions of epilogue into every iteration.
 // HEAT: the heat-map debug mode (shaders/pathtrace.comp:89,108-119 colours a pixel by the real time its invocation took): the instrumented
 // instantiation stamps every ray with the wall-clock time it spent in this kernel (fetch -> settled), added to the path's cost in rayO.w
-template <bool HEAT, bool TWO>
-__global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRACE_WAVES) k_closest_p(DeviceScene S, RenderBuffers rb, const uint32_t* __restrict__ queueIn, int bounce, int minRun, int chunk, int cntIn, int cntChunk)
+// HO: the queue is queueR of a packet stage that hands pass A over -- an entry marked QUEUE_HANDOVER starts in pass B (lane_fetch_handover).  A kernel of
+// its own (k_closest_r) runs that form, so that the kernels every later bounce runs keep their code and their register budget.
+template <bool HEAT, bool TWO, bool HO>
+PT_DEV void closest_machine(const DeviceScene& S, const RenderBuffers& rb, const uint32_t* __restrict__ queueIn, int bounce, int minRun, int chunk, int cntIn, int cntChunk)
 {
   uint32_t heatT0 = 0;
   __shared__ uint32_t stack[STACK_LDS * TRACE_BLOCK];
@@ -217,7 +221,13 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
     if(qi != 0xffffffffu)
     {
       pslot = queueIn[qi];
-      lane_fetch_closest(S, rb, pslot, L, seed);
+      if(HO && (pslot & QUEUE_HANDOVER))
+      {
+        pslot &= ~QUEUE_HANDOVER;
+        lane_fetch_handover<TWO>(S, rb, pslot, L, seed);
+      }
+      else
+        lane_fetch_closest(S, rb, pslot, L, seed);
       alive = true;
       ++nRays;
       if(HEAT)
@@ -231,12 +241,25 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
   wave_add(&rb.counters->closestRays, nRays);
   wave_add(&rb.counters->alphaTests, nAlpha);
 }
+template <bool HEAT, bool TWO>
+__global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRACE_WAVES) k_closest_p(DeviceScene S, RenderBuffers rb, const uint32_t* __restrict__ queueIn, int bounce, int minRun, int chunk, int cntIn, int cntChunk)
+{
+  closest_machine<HEAT, TWO, false>(S, rb, queueIn, bounce, minRun, chunk, cntIn, cntChunk);
+}
+// the same on queueR behind a packet stage that hands pass A over (PT_TUNE handover=1)
+template <bool TWO>
+__global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRACE_WAVES) k_closest_r(DeviceScene S, RenderBuffers rb, int bounce, int minRun, int chunk)
+{
+  closest_machine<false, TWO, true>(S, rb, rb.queueR, bounce, minRun, chunk, CNT_REDO, CNT_CHUNK_REDO);
+}
 
 // Packet kernel for coherent rays (bounce 0, pt_packet.h): persistent wavefronts walk the queue 64 rays (one 8x8 pixel block)
-// at a time with ONE traversal per wave.  Rays it cannot settle on the spot -- packets whose lanes disagree on a direction
-// sign, rays that need pass B or the exact fallback -- are staged in LDS and appended to queueR, which the refilling trace
-// machine (k_closest_p) then redoes per lane.  Keeping those paths out of this kernel keeps it at ~64 VGPRs: the packet
-// traversal is a serial chain of scalar loads, so it lives on resident waves, not on instruction throughput.
+// at a time with ONE traversal per wave.  Rays it cannot settle on the spot are staged in LDS and appended to queueR for the refilling
+// trace machine (k_closest_r): the rays of a packet whose lanes disagree on a direction sign (nothing was traversed: walked per lane from the
+// root) and the rays that need pass B (handed over with this pass A's hit, pt_settle.h store_handover: the lane starts in pass B).  A ray
+// that saw a fractional candidate, or whose draws hit exactly 0.0, goes to the exact loop's queue from here.  `handover` = 0 (PT_TUNE): all of
+// them are redone from the root by k_closest_p.  Keeping those paths out of this kernel keeps it at ~64 VGPRs: the packet traversal is a
+// serial chain of scalar loads, so it lives on resident waves, not on instruction throughput.
 #ifndef PT_PACKET_WAVES
 #define PT_PACKET_WAVES 8
 #endif
@@ -247,11 +270,11 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
 // 32 B per sample less written, 32 B less read; what later stages need is written from here: the direction and RNG state (k_shade), and the whole
 // ray of a path that goes on to the refilling trace machine (queueR).
 template <bool TWO>
-__global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_PACKET_WAVES_TWO : PT_PACKET_WAVES) k_closest_k(DeviceScene S, RenderBuffers rb, FrameParams fp, const uint32_t* __restrict__ queueIn, int bounce)
+__global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_PACKET_WAVES_TWO : PT_PACKET_WAVES) k_closest_k(DeviceScene S, RenderBuffers rb, FrameParams fp, const uint32_t* __restrict__ queueIn, int bounce, int handover)
 {
   __shared__ uint32_t wstack[PACKET_STACK];
   __shared__ uint32_t stage[STAGE_CAP];
-  uint32_t            nStage = 0, nRays = 0, nAlpha = 0;
+  uint32_t            nStage = 0, nRays = 0, nAlpha = 0, nHanded = 0;
   uint32_t*           C     = rb.counts + bounce * CNT_STRIDE;
   const uint32_t      count = C[CNT_IN];
 #pragma unroll 1
@@ -282,12 +305,15 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_PACKET_WAVES_TWO : PT_PA
     }
     RayHit     h;
     const bool packet = TWO ? traverse_packet_two(S, valid, o, d, wstack, h, rb.counters) : traverse_packet_closest(S, valid, o, d, wstack, h, rb.counters);
-    bool       redo   = valid && !packet;
+    bool       redo   = valid && !packet;  // not settled here: the ray goes on with the untouched seed ...
+    bool       handed = false, exact = false;  // ... of which: into pass B with this pass A's hit / straight to the exact loop (PT_TUNE handover)
     uint32_t   seedOut = seed;
     if(valid && packet)
     {
-      redo = (h.flags & TF_SAW_FRAC) != 0 || needs_count_pass(h.flags, 0, h.slot, h.t, h.zeroMaxT, h.zeroMaxT2, h.zeroMaxT3, h.count);
-      if(!redo)
+      const bool frac      = (h.flags & TF_SAW_FRAC) != 0;
+      const bool countPass = needs_count_pass(h.flags, 0, h.slot, h.t, h.zeroMaxT, h.zeroMaxT2, h.zeroMaxT3, h.count);
+      bool       zeroDraw  = false;
+      if(!frac && !countPass)
       {
         uint32_t nDraw, s2;
         if(settle_draws(h.slot, h.w, h.count, seed, nDraw, s2))
@@ -300,20 +326,37 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_PACKET_WAVES_TWO : PT_PA
           ++nRays;
         }
         else
-          redo = true;
+          zeroDraw = true;
       }
+      redo   = frac || countPass || zeroDraw;
+      handed = handover && countPass;
+      exact  = handover && (frac || zeroDraw);
     }
     if(regen && valid)
-    {  // what the next stages read of the ray: k_shade the direction + RNG state; the trace machine (redo) the whole ray with the untouched seed
+    {  // what the next stages read of the ray: k_shade the direction + RNG state; the trace machine and the exact loop (redo) the whole ray with the untouched seed
       rb.ps.rayD[slot] = make_float4(d.x, d.y, d.z, __uint_as_float(redo ? seed : seedOut));
       if(redo)
         rb.ps.rayO[slot] = make_float4(o.x, o.y, o.z, 0.f);
     }
-    stage_push(stage, nStage, redo, slot, rb.queueR, &C[CNT_REDO]);
+    if(handed)
+    {  // the count pass alone is left: the hit is final (the machine counts the ray when it pulls it)
+      store_handover(rb, slot, h, TWO);
+      ++nHanded;
+    }
+    if(exact)
+    {  // a fractional candidate, or a rejected draw of exactly 0.0: what the machine's pass A would only find out again (rare: one atomic per wave that has one)
+      enqueue(rb.queueX, &C[CNT_X_CLOSEST], slot);
+      ++nRays;
+    }
+    stage_push(stage, nStage, redo && !exact, handed ? (slot | QUEUE_HANDOVER) : slot, rb.queueR, &C[CNT_REDO]);
   }
   stage_flush(stage, nStage, rb.queueR, &C[CNT_REDO]);
   wave_add(&rb.counters->closestRays, nRays);
   wave_add(&rb.counters->alphaTests, nAlpha);
+  for(int off = 32; off > 0; off >>= 1)
+    nHanded += __shfl_xor(nHanded, off);
+  if((threadIdx.x & 63) == 0 && nHanded)
+    atomicAdd(&C[CNT_HANDOVER], nHanded);
 }
 
 // Exact fallback: one ray per lane, key-ordered stochastic alpha (trace contract T5).  Runs on the rays the
@@ -1010,6 +1053,7 @@ static void plan_frame(std::vector<PtStep>& steps, hipStream_t stream, const PtT
   // camera rays computed by the packet kernel instead of written by k_generate: one sample per frame (the RNG stream of a second sample continues
   // from the stored state), a packet stage at bounce 0, no heat map (it keeps the path's cost in rayO.w), bounce 0 not already in k_tail
   const int  packetBounces = tune.packetClosestBounces;
+  const int  handover      = tune.handover ? 1 : 0;
   const bool packetStage = !TWO || tune.packetTwo;  // the two-level structure has a packet stage of its own since round 4 (pt_packet.h traverse_packet_two)
   fp.regen = (tune.regen && packetStage && !heat && fp.st.maxSamples == 1 && packetBounces >= 1 && tailFrom > 0 && fp.st.maxDepth > 0) ? 1 : 0;
   for(int s = 0; s < fp.st.maxSamples; ++s)
@@ -1046,8 +1090,11 @@ static void plan_frame(std::vector<PtStep>& steps, hipStream_t stream, const PtT
           {
             const uint32_t kwAll = PT_PACKET_WAVES_LAUNCH;
             const uint32_t kw    = TWO ? kwAll * PT_PACKET_WAVES_TWO / PT_PACKET_WAVES : kwAll;
-            k_closest_k<TWO><<<wavesAll < kw ? wavesAll : kw, TRACE_BLOCK, 0, stream>>>(scene, rb, fp, qIn, depth);
-            k_closest_p<false, TWO><<<gridTrace, TRACE_BLOCK, 0, stream>>>(scene, rb, rb.queueR, depth, PT_REFILL_BELOW_DEFAULT, PT_SUPPLY_CHUNK, CNT_REDO, CNT_CHUNK_REDO);
+            k_closest_k<TWO><<<wavesAll < kw ? wavesAll : kw, TRACE_BLOCK, 0, stream>>>(scene, rb, fp, qIn, depth, handover);
+            if(handover)
+              k_closest_r<TWO><<<gridTrace, TRACE_BLOCK, 0, stream>>>(scene, rb, depth, PT_REFILL_BELOW_DEFAULT, PT_SUPPLY_CHUNK);
+            else
+              k_closest_p<false, TWO><<<gridTrace, TRACE_BLOCK, 0, stream>>>(scene, rb, rb.queueR, depth, PT_REFILL_BELOW_DEFAULT, PT_SUPPLY_CHUNK, CNT_REDO, CNT_CHUNK_REDO);
           }
           else
             k_closest_p<false, TWO><<<gridTrace, TRACE_BLOCK, 0, stream>>>(scene, rb, qIn, depth, PT_REFILL_BELOW_DEFAULT, PT_SUPPLY_CHUNK, CNT_IN, CNT_CHUNK_CLOSEST);

@@ -18,6 +18,19 @@ PT_DEV void store_hit(const RB& rb, uint32_t slot, uint32_t bslot, uint32_t bw, 
     rb.ps.hit[slot] = make_float4(t, __uint_as_float(two ? (bw & TRI_INDEX_MASK) : bslot), u, v);
 }
 
+// Hand-over of a packet's pass A (k_closest_k) to the trace machine: the ray's certain hit is final, only the zero-opacity candidates in front of it
+// have to be counted again (needs_count_pass), so the lane that pulls the ray enters pass B instead of walking pass A a second time
+// (pt_machine.h lane_fetch_handover).  The hit record carries t, u, v and the slot (flat) / the world index (two-level); the triangle's flag bits
+// travel as the whole `w` word in rayO.w, which only the heat-map mode reads -- and that mode has no packet stage.  A miss never needs the count pass
+// (pass_a_settles): a handed-over ray always has a hit.  Bit 31 of the queueR word marks the entry (path slots need 27 bits).
+#define QUEUE_HANDOVER 0x80000000u
+template <class RB>
+PT_DEV void store_handover(const RB& rb, uint32_t slot, const RayHit& h, bool two)
+{
+  store_hit(rb, slot, h.slot, h.w, two, h.t, h.u, h.v);
+  rb.ps.rayO[slot].w = __uint_as_float(h.w);
+}
+
 // The exact key-ordered loops (trace contract T5 / T6; k_closest_x / k_shadow_x / k_trace_x run nothing else): what a ray falls back to when the
 // two-pass scheme cannot settle it -- a candidate of fractional opacity in front of the hit, or a rejected-candidate draw of exactly 0.0.
 // `seed`: the path's RNG state before the ray's first draw; closest: hit record and the state afterwards go to the path state.
