@@ -1,55 +1,31 @@
-// The hand-over of a packet's pass A to the trace machine (csrc/pt_settle.h store_handover, csrc/pt_machine.h lane_fetch_handover) on the CPU.
-// This file adds ONE entry point to the host build of the product's traversal source: everything else -- the scene records, the structures, the
-// include of pt_trace.h / pt_machine.h / pt_settle.h compiled for the host -- is tests/cpp/trace_host.cpp, included as it is.
+// The hand-over of a packet's pass A to the trace machine (csrc/pt_settle.h store_handover, csrc/pt_machine.h lane_fetch_handover) on the CPU:
+// one entry point of the host harness (tests/host_harness.py), on the scenes th_create_scene makes, with the machine leg of th_walk.h.
 //
 // For every ray two routes are run on the same scene and the same seed:
-//   (a) the lane starts at the root (lane_fetch_closest) and is driven through the service round of k_closest_p to its end;
+//   (a) the lane starts at the root (lane_fetch_closest) and is driven through the service round of k_closest_p to its end (drive_lane);
 //   (b) pass A comes from traverse<TM_CLOSEST> (what the packet kernel holds per lane when its traversal ends), k_closest_k's decision is taken
-//       on it, and a ray that needs the count pass is stored with store_handover and begun with lane_fetch_handover.
+//       on it, and a ray that needs the count pass is stored with store_handover, begun with lane_fetch_handover and driven by the same drive_lane.
 // A ray either route cannot settle goes through settle_closest_exact, like k_closest_x.  tests/test_handover_host.py requires both routes to
 // leave the same hit record, the same RNG state, the same number of draws and to have taken the same way (settled / exact loop).
-#include "trace_host.cpp"
+#include "th_walk.h"
 
 namespace {
 struct RouteOut {
   uint32_t hit[4], seed, draws, exact;
 };
-// the run loop and the service round of k_closest_p for one lane that has been begun (pt_render.hip closest_machine); the verdict goes to `out`
+// the lane's verdict as k_closest_p acts on it (pt_render.hip closest_machine): the hit record and the seed go to the path state
 template <bool TWO>
-void drive_lane(const DeviceScene& S, const RenderBuffers& rb, uint32_t r, TraceLane& L, uint32_t seed, uint32_t* stack, uint32_t* spill, RouteOut& out)
+void drive_and_store(const DeviceScene& S, TraceLane& L, uint32_t seed, WalkCtx& c, RouteOut& out)
 {
-  bool fallback = false;
-  for(;;)
+  const LaneVerdict v = drive_lane<TWO>(S, L, seed, c);
+  if(v.settled)
   {
-    while(!L.done)
-    {
-      if(!(L.cur & BVH_LEAF))
-        lane_inner<false, TWO>(S, L, stack, spill, rb.counters);
-      if(!L.done && (L.cur & BVH_LEAF))
-        lane_leaf<false, TWO>(S, L, stack, spill);
-    }
-    fallback = (L.flags & TF_SAW_FRAC) != 0;
-    if(needs_count_pass(L.flags, L.pass, L.bslot, L.bt, L.zeroMaxT, L.zeroMaxT2, L.zeroMaxT3, L.cnt))
-    {
-      lane_begin_count<TWO>(L);
-      continue;
-    }
-    if(!fallback)
-    {
-      uint32_t nDraw, s2;
-      if(settle_draws(L.bslot, L.bw, L.cnt, seed, nDraw, s2))
-      {
-        store_hit(rb, r, L.bslot, L.bw, TWO, L.bt, L.bu, L.bv);
-        if(nDraw)
-          rb.ps.rayD[r].w = __uint_as_float(s2);
-        out.draws = nDraw;
-      }
-      else
-        fallback = true;
-    }
-    break;
+    store_hit(c.rb, 0u, L.bslot, L.bw, TWO, L.bt, L.bu, L.bv);
+    if(v.nDraw)
+      c.rb.ps.rayD[0].w = __uint_as_float(v.s2);
+    out.draws = v.nDraw;
   }
-  out.exact = fallback ? 1u : 0u;
+  out.exact = v.settled ? 0u : 1u;
 }
 template <bool TWO>
 void finish(const DeviceScene& S, const RenderBuffers& rb, uint32_t r, f3 o, f3 d, uint32_t seed0, uint32_t* stack, RouteOut& out)
@@ -65,18 +41,18 @@ void finish(const DeviceScene& S, const RenderBuffers& rb, uint32_t r, f3 o, f3 
   out.seed   = __float_as_uint(rb.ps.rayD[r].w);
 }
 
+
 template <bool TWO>
 uint32_t handover_rays(Scene* s, uint32_t nrays, const float* org, const float* dir, const uint32_t* seeds, uint32_t* outA, uint32_t* outB, uint32_t* info)
 {
   const DeviceScene&    S = TWO ? s->dsTwo : s->dsFlat;
-  std::vector<float4>   rayO(1), rayD(1), hit(1);
-  std::vector<uint32_t> stack(size_t(STACK_LDS) * TRACE_BLOCK), spill(STACK_SPILL);
-  Counters              cnt;
-  std::memset(&cnt, 0, sizeof(cnt));
-  RenderBuffers rb;
-  std::memset(&rb, 0, sizeof(rb));
-  rb.ps.rayO.p = rayO.data(); rb.ps.rayD.p = rayD.data(); rb.ps.hit.p = hit.data();
-  rb.counters = &cnt;
+  std::vector<float4>   rayO(1), rayD(1), hit(1);  // one path slot, used by every ray in turn
+  RenderBuffers         proto;
+  std::memset(&proto, 0, sizeof(proto));
+  proto.ps.rayO.p = rayO.data(); proto.ps.rayD.p = rayD.data(); proto.ps.hit.p = hit.data();
+  WalkCtx              ctx(&proto);
+  const RenderBuffers& rb    = ctx.rb;
+  uint32_t* const      stack = ctx.stack.data();
   for(uint32_t r = 0; r < nrays; ++r)
   {
     const f3 o = f3{org[3 * r], org[3 * r + 1], org[3 * r + 2]}, d = f3{dir[3 * r], dir[3 * r + 1], dir[3 * r + 2]};
@@ -92,8 +68,8 @@ uint32_t handover_rays(Scene* s, uint32_t nrays, const float* org, const float* 
       TraceLane L;
       uint32_t  seed = 0;
       lane_fetch_closest(S, rb, 0u, L, seed);
-      drive_lane<TWO>(S, rb, 0u, L, seed, stack.data(), spill.data(), a);
-      finish<TWO>(S, rb, 0u, o, d, seeds[r], stack.data(), a);
+      drive_and_store<TWO>(S, L, seed, ctx, a);
+      finish<TWO>(S, rb, 0u, o, d, seeds[r], stack, a);
     }
     // ---- (b) pass A as the packet kernel holds it, k_closest_k's decision, the hand-over
     RouteOut b{};
@@ -101,7 +77,7 @@ uint32_t handover_rays(Scene* s, uint32_t nrays, const float* org, const float* 
     bool     dummy, handed = false;
     {
       reset();
-      traverse<TM_CLOSEST, TWO>(S, o, d, PT_INFINITY, 0.0f, 0xffffffffu, 0u, stack.data(), h, dummy, &cnt);
+      traverse<TM_CLOSEST, TWO>(S, o, d, PT_INFINITY, 0.0f, 0xffffffffu, 0u, stack, h, dummy, &ctx.cnt);
       uint32_t   count     = h.count;
       const bool frac      = (h.flags & TF_SAW_FRAC) != 0;
       const bool countPass = needs_count_pass(h.flags, 0, h.slot, h.t, h.zeroMaxT, h.zeroMaxT2, h.zeroMaxT3, count);
@@ -125,22 +101,22 @@ uint32_t handover_rays(Scene* s, uint32_t nrays, const float* org, const float* 
         TraceLane L;
         uint32_t  seed = 0;
         lane_fetch_handover<TWO>(S, rb, 0u, L, seed);
-        drive_lane<TWO>(S, rb, 0u, L, seed, stack.data(), spill.data(), b);
+        drive_and_store<TWO>(S, L, seed, ctx, b);
       }
       else
         b.exact = 1u;
-      finish<TWO>(S, rb, 0u, o, d, seeds[r], stack.data(), b);
+      finish<TWO>(S, rb, 0u, o, d, seeds[r], stack, b);
     }
     // ---- what the fixture holds: pass A's view of the ray, and the count pass in front of its hit run for every ray
     RayHit c;
-    traverse<TM_COUNT, TWO>(S, o, d, h.slot == BVH_NONE ? PT_INFINITY : h.t, 0.0f, 0xffffffffu, h.slot == BVH_NONE ? 0u : (h.w & TRI_INDEX_MASK), stack.data(), c, dummy, &cnt);
+    traverse<TM_COUNT, TWO>(S, o, d, h.slot == BVH_NONE ? PT_INFINITY : h.t, 0.0f, 0xffffffffu, h.slot == BVH_NONE ? 0u : (h.w & TRI_INDEX_MASK), stack, c, dummy, &ctx.cnt);
     std::memcpy(outA + 7 * size_t(r), &a, sizeof(a));
     std::memcpy(outB + 7 * size_t(r), &b, sizeof(b));
     uint32_t* I = info + 9 * size_t(r);
     I[0] = h.flags; I[1] = h.count; I[2] = __float_as_uint(h.zeroMaxT); I[3] = __float_as_uint(h.zeroMaxT2); I[4] = __float_as_uint(h.zeroMaxT3);
     I[5] = __float_as_uint(h.t); I[6] = h.slot == BVH_NONE ? 0xffffffffu : (h.w >> 29); I[7] = c.flags; I[8] = handed ? 1u : 0u;
   }
-  return cnt.stackOverflow;
+  return ctx.cnt.stackOverflow;
 }
 }  // namespace
 

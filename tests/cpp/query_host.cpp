@@ -1,8 +1,7 @@
-// CPU harness around the product's ray-query body (test infrastructure; built and used by tests/test_query_host.py and, as the reference of the
-// device runs, by tests/test_query_gpu.py).  vk_raytrace_amd/csrc/pt_query.h -- query_ray<TWO>, what pt_trace_rays' kernel runs per lane -- is
-// compiled for the host next to the harness of the traversal source (trace_host.cpp: its Scene, th_create*, th_candidates, th_settle), on the
-// structures that harness assembles.
-#include "trace_host.cpp"
+// The product's ray-query body on the host (unit of the host harness, tests/host_harness.py; the reference of tests/test_query_host.py and, for the
+// device runs, of tests/test_query_gpu.py).  vk_raytrace_amd/csrc/pt_query.h -- query_ray<TWO>, what pt_trace_rays' kernel runs per lane -- on the
+// structures th_scene.h assembles.
+#include "th_walk.h"
 #include "pt_query.h"
 
 // n rays of `kind` on the flat (two = 0) or the two-level structure; hits: n x hitsPerRay records.  Returns the traversal-stack overflows counted.
@@ -10,22 +9,10 @@ extern "C" uint32_t qh_query(void* p, int two, int kind, int variant, uint64_t n
 {
   Scene*             s = static_cast<Scene*>(p);
   const DeviceScene& S = two ? s->dsTwo : s->dsFlat;
-  uint32_t           overflow = 0;
-#pragma omp parallel
-  {
-    std::vector<uint32_t> stack(size_t(STACK_LDS) * TRACE_BLOCK);
-    Counters              cnt;
-    std::memset(&cnt, 0, sizeof(cnt));
-#pragma omp for schedule(dynamic, 64)
-    for(long long r = 0; r < (long long)n; ++r)
-    {
-      if(two)
-        query_ray<true>(S, kind, variant, rays[r], hitsPerRay, stack.data(), &cnt, hits + size_t(r) * hitsPerRay);
-      else
-        query_ray<false>(S, kind, variant, rays[r], hitsPerRay, stack.data(), &cnt, hits + size_t(r) * hitsPerRay);
-    }
-#pragma omp critical
-    overflow += cnt.stackOverflow;
-  }
-  return overflow;
+  return for_each_ray((long long)n, 64, nullptr, [&](WalkCtx& c, long long r) {
+    if(two)
+      query_ray<true>(S, kind, variant, rays[r], hitsPerRay, c.stack.data(), &c.cnt, hits + size_t(r) * hitsPerRay);
+    else
+      query_ray<false>(S, kind, variant, rays[r], hitsPerRay, c.stack.data(), &c.cnt, hits + size_t(r) * hitsPerRay);
+  });
 }

@@ -44,7 +44,7 @@ def load():
 
 
 def probe(fn_ptr, fn, rows, out_words, ctx=None):
-    """rows (n, w) float32 through one call of a probe (signatures: tests/orc.py, tests/ref.py, tests/test_trace_host.py harness(), vk_raytrace_amd/capi.py
+    """rows (n, w) float32 through one call of a probe (signatures: tests/orc.py, tests/ref.py, tests/host_harness.py, vk_raytrace_amd/capi.py
     DEBUG_API); returns (n, out_words) float32, or None where that side answers -1 (no such function)"""
     rows = np.ascontiguousarray(rows, np.float32)
     out = np.zeros((len(rows), out_words), np.float32)

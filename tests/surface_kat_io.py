@@ -2,7 +2,6 @@
 the surface probes (vk_raytrace_amd/csrc/pt_probe.h surface_probe: th_surface_probe on the host build, pt_debug_surface_probe on the device,
 orc_surface_probe on the oracle, ref_surface_probe on the compiled reference).  A probe takes rows of IN words and fills rows of OUT words; integers
 travel as bit patterns; rows a probe refuses keep the caller's fill."""
-import ctypes as C
 import importlib.util
 import os
 
@@ -71,9 +70,6 @@ class HostScene:
     def __init__(self, scene, tune=None):
         from tests import tex_kat_io
         self.hs = tex_kat_io.HostScene(scene, tune)
-        L = self.hs.L
-        L.th_surface_probe.restype = C.c_int
-        L.th_surface_probe.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
 
     def probe(self, kind, r, fill=np.nan):
         out, rc = call(self.hs.L.th_surface_probe, (self.hs.h,), kind, r, fill)

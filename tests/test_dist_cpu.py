@@ -3,7 +3,7 @@
 bit-identical to a single-process render: seeds depend on the global pixel index only
 (shaders/pathtrace.comp:97).  Two flavours of "render": the oracle standing in for the HIP path, and the
 PRODUCT's own source -- the per-path functions the HIP kernels are made of, compiled for the host
-(tests/test_trace_host.py host_render) with the device's tile / slot layout of the rank's shard."""
+(tests/host_harness.py host_render) with the device's tile / slot layout of the rank's shard."""
 import os
 import socket
 import sys
@@ -73,7 +73,7 @@ def _worker_product(rank, world, port, out_path):
     import torch
     import torch.distributed as dist
     from tests.common import Config, render_oracle
-    from tests.test_trace_host import host_render
+    from tests.host_harness import host_render
     from vk_raytrace_amd import synth, shard
     dist.init_process_group("gloo", rank=rank, world_size=world)
     W, H = 100, 70   # not a multiple of the tile size: partial edge tiles
@@ -94,8 +94,8 @@ def _worker_product(rank, world, port, out_path):
 
 def test_two_rank_sharding_of_the_products_host_build(tmp_path):
     import torch.multiprocessing as mp
-    from tests.test_trace_host import harness
-    harness()   # build once, before the ranks race for it
+    from tests import host_harness
+    host_harness.build()   # once, so that the ranks do not both compile it
     out = str(tmp_path / "res.npy")
     mp.spawn(_worker_product, args=(2, _free_port(), out), nprocs=2, join=True)
     full, ref, foreign = np.load(out)

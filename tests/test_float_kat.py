@@ -105,8 +105,8 @@ def tol():
 
 
 def host_probe():
-    from tests.test_trace_host import harness
-    return harness().th_shading_probe
+    from tests import host_harness
+    return host_harness.lib().th_shading_probe
 
 
 def sky_rows(kat):

@@ -1,45 +1,18 @@
 """The hand-over of the packet stage's pass A to the trace machine, on the CPU (tests/cpp/handover_host.cpp: the product's pt_trace.h,
-pt_machine.h and pt_settle.h compiled for the host, one entry point on top of tests/cpp/trace_host.cpp).
+pt_machine.h and pt_settle.h compiled for the host, the th_handover entry point of the host harness, tests/host_harness.py).
 
 Claim under test: a ray whose pass A cannot stand may enter pass B with the pass-A hit somebody else computed -- stored
 by store_handover, restored by lane_fetch_handover -- and nothing observable changes: the hit record, the RNG state afterwards, the number of
 draws and the way the ray took (settled by the two passes / by the exact key-ordered loop) are those of a lane that started at the root.  Rays
 known to need the exact loop after pass A go straight to it; they must arrive at the same record too.  Every case the rule distinguishes is
 asserted to occur in the fixture, on the flat and on the two-level structure."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from tests.handover_scene import handover_scene, EYE
-from vk_raytrace_amd import capi
+from tests.host_harness import NONE, TracedScene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "handover_host.cpp")
-OUT = os.path.join(ROOT, "tests", "cpp", "_build", "libhandoverhost.so")
-NONE = 0xFFFFFFFF
 TF_SAW_ZERO, TF_SAW_FRAC, TRI_OPAQUE = 1, 2, 1
-
-
-def harness():
-    capi.lib()  # libptmi.so must exist: the harness links its host-side test hooks (scene records, builder emulation)
-    csrc = os.path.join(ROOT, "vk_raytrace_amd", "csrc")
-    deps = [SRC, os.path.join(ROOT, "tests", "cpp", "trace_host.cpp"), capi.LIB_PATH] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        lib_dir = os.path.dirname(capi.LIB_PATH)
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fopenmp", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-DSTACK_LDS=24", "-Wno-attributes",
-                               "-I/opt/rocm/include", "-I" + csrc, "-I" + os.path.join(ROOT, "include"), SRC,
-                               "-L" + lib_dir, "-l:libptmi.so", "-Wl,-rpath," + lib_dir, "-Wl,-rpath,/opt/rocm/lib", "-o", OUT])
-    L = C.CDLL(OUT)
-    L.th_create_scene.restype = C.c_void_p
-    L.th_create_scene.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    L.th_destroy.argtypes = [C.c_void_p]
-    L.th_handover.restype = C.c_uint32
-    L.th_handover.argtypes = [C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 6
-    return L
 
 
 def fixed_rays(n_side=72):
@@ -57,23 +30,18 @@ def fixed_rays(n_side=72):
 @pytest.fixture(scope="module")
 def routes():
     """both routes for every ray, flat and two-level: computed once"""
-    L = harness()
     sc = handover_scene()
-    sc.finalize(capi.pack_vertices)
-    d, keep = sc.desc()
-    err = C.create_string_buffer(256)
-    h = L.th_create_scene(C.byref(d), err, 256)
-    assert h, err.value
+    tr = TracedScene(sc)
     org, dirs, seeds = fixed_rays()
     out = {}
     try:
         for two in (0, 1):
             a, b, info = np.zeros((len(org), 7), np.uint32), np.zeros((len(org), 7), np.uint32), np.zeros((len(org), 9), np.uint32)
-            over = L.th_handover(h, two, len(org), org.ctypes.data, dirs.ctypes.data, seeds.ctypes.data, a.ctypes.data, b.ctypes.data, info.ctypes.data)
+            over = tr.L.th_handover(tr.h, two, len(org), org.ctypes.data, dirs.ctypes.data, seeds.ctypes.data, a.ctypes.data, b.ctypes.data, info.ctypes.data)
             assert over == 0, "traversal stack overflow"
             out[two] = (a, b, info)
     finally:
-        L.th_destroy(h)
+        tr.close()
     assert sc.num_triangles < 1000
     return out, seeds
 

@@ -12,11 +12,10 @@ import sys
 import numpy as np
 import pytest
 
-from tests import test_trace_host as tth
 from tests.common import Config
+from tests.host_harness import NONE, TracedScene, alpha_scenes, deep_rays, ill_conditioned, instanced_scene, rays_for
 from tests.test_query_host import (ALL_KINDS, CANDIDATES, CLOSEST, DEGENERATE_DIR, DEGENERATE_ORG, HIT, INF, INVALID, NEAREST, OCCLUDED, alpha_inputs, bits, empty_scenes,
-                                   host_query, invalid_ray_batch, make_rays, one_triangle_scene, records_equal, three_layer_scene, traced, world_index)
-from tests.test_trace_host import NONE, TracedScene, ill_conditioned, instanced_scene, rays_for
+                                   host_query, invalid_ray_batch, make_rays, one_triangle_scene, records_equal, three_layer_scene, world_index)
 from vk_raytrace_amd import capi, host_device as hd, synth
 from vk_raytrace_amd.renderer import HipRenderer
 
@@ -87,10 +86,10 @@ def check_all_kinds(r, tr, scene, accel, org, dirs, seeds, tmax, what, variants=
 
 # ---- device against host, bit for bit -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("accel", ACCELS, ids=ACCEL_IDS)
-@pytest.mark.parametrize("name,scene,eye,spread", list(tth._alpha_scenes()), ids=lambda x: x if isinstance(x, str) else None)
+@pytest.mark.parametrize("name,scene,eye,spread", list(alpha_scenes()), ids=lambda x: x if isinstance(x, str) else None)
 def test_device_equals_host_on_the_alpha_scenes(name, scene, eye, spread, accel):
     """the inputs of test_closest_and_occluded_equal_the_key_ordered_loop: 6000 rays and seeds, every kind, both variants of the shadow ray"""
-    tr = traced(TracedScene, scene)
+    tr = TracedScene(scene)
     r = renderer(scene, accel)
     org, dirs, seeds, tmax = alpha_inputs(tr, eye, spread)
     check_all_kinds(r, tr, scene, accel, org, dirs, seeds, tmax, f"{name} {ACCEL_IDS[two_of(accel)]}", variants=(capi.PT_VARIANT_RAYQUERY, capi.PT_VARIANT_RTX))
@@ -107,7 +106,7 @@ def test_device_equals_host_on_the_alpha_scenes(name, scene, eye, spread, accel)
 def test_device_equals_host_on_the_instanced_scenes(seed, accel):
     """scaled / rotated / mirrored / coincident instances, camera-like, surface-to-surface, axis-parallel and far-origin rays (rays_for)"""
     sc, _, off = instanced_scene(seed)
-    tr = traced(TracedScene, sc)   # the instance flags are the product's own here (from the materials), as on the device
+    tr = TracedScene(sc)   # the instance flags are the product's own here (from the materials), as on the device
     r = renderer(sc, accel)
     org, dirs = rays_for(tr, np.random.default_rng(100 + seed), off, 6000)
     tmax = np.where(np.arange(len(org)) % 3 == 0, INF, np.float32(9.0)).astype(np.float32)
@@ -120,7 +119,7 @@ def test_edges_on_the_device(accel):
     """degenerate scenes, the exclusive upper bound, empty ranges, one invalid ray per rule among valid neighbours, 16 results for 3 candidates"""
     two = two_of(accel)
     sc, _ = one_triangle_scene()
-    tr, r = traced(TracedScene, sc), renderer(sc, accel)
+    tr, r = TracedScene(sc), renderer(sc, accel)
     t_hit = host_query(tr, two, NEAREST, make_rays(DEGENERATE_ORG[:1], DEGENERATE_DIR[:1]))["t"][0]
     assert t_hit > 0
     tm = np.array([t_hit, np.nextafter(t_hit, np.float32(np.inf)), 0.0, -1.0, -np.inf, np.inf], np.float32)
@@ -138,13 +137,13 @@ def test_edges_on_the_device(accel):
         assert (dev["status"][bad] == INVALID).all() and (dev["seed"][bad] == invalid["seed"][bad][:, None]).all() and (np.delete(dev["status"][:, 0], bad) & INVALID == 0).all()
     r.destroy(); tr.close()
     for sc, _ in empty_scenes():
-        tr, r = traced(TracedScene, sc), renderer(sc, accel)
+        tr, r = TracedScene(sc), renderer(sc, accel)
         for kind in ALL_KINDS:
             dev = r.trace_ray_records(kind, invalid)
             assert records_equal(dev, host_query(tr, two, kind, invalid)) and ((dev["status"] & HIT) == 0).all()
         r.destroy(); tr.close()
     sc, _ = three_layer_scene()
-    tr, r = traced(TracedScene, sc), renderer(sc, accel)
+    tr, r = TracedScene(sc), renderer(sc, accel)
     rays = make_rays([[0, -0.2, 5]], [[0, 0, -1]], seeds=9)   # (seen from +z the three layers face the ray, whatever the material's sidedness)
     dev = r.trace_ray_records(CANDIDATES, rays, 16)
     assert records_equal(dev, host_query(tr, two, CANDIDATES, rays, hits_per_ray=16))
@@ -156,7 +155,7 @@ def test_edges_on_the_device(accel):
 @pytest.mark.parametrize("accel", ACCELS, ids=ACCEL_IDS)
 def test_wave_edges(accel):
     scene = synth.fuzz_scene(0)
-    tr, r = traced(TracedScene, scene), renderer(scene, accel)
+    tr, r = TracedScene(scene), renderer(scene, accel)
     org, dirs, seeds, tmax = alpha_inputs(tr, (0, 0, 6), 3.0, n=4097)
     rays = make_rays(org, dirs, tmax=tmax, seeds=seeds)
     for kind, hpr in ((CLOSEST, 1), (OCCLUDED, 1), (CANDIDATES, 3)):
@@ -171,7 +170,7 @@ def test_host_arrays_cross_the_staging_chunk():
     """n = 2^20 + 65 on the one-triangle scene: two chunks through the staging buffers.  Equal to the same rays sent as two smaller calls, and 4096 rays
     on both sides of the boundary equal the host harness."""
     sc, _ = one_triangle_scene()
-    tr, r = traced(TracedScene, sc), renderer(sc, capi.PT_ACCEL_FLAT)
+    tr, r = TracedScene(sc), renderer(sc, capi.PT_ACCEL_FLAT)
     n = capi.PT_QUERY_CHUNK + 65
     rng = np.random.default_rng(5)
     org = np.concatenate([rng.uniform(-1.5, 1.5, (n, 2)), np.full((n, 1), 3.0)], 1).astype(np.float32)
@@ -270,9 +269,9 @@ def test_stack_limit(accel):
     two = two_of(accel)
     env = synth.procedural_sky(64, 32)
     cfg = Config(synth.deep_chain(synth.DEEP_SPILL_LEVELS), env, 64, 48)
-    o, d = tth._deep_rays(cfg)
+    o, d = deep_rays(cfg)
     rays = make_rays(o, d, seeds=np.arange(len(o), dtype=np.uint32))
-    tr, r = traced(TracedScene, cfg.scene), renderer(cfg.scene, accel)
+    tr, r = TracedScene(cfg.scene), renderer(cfg.scene, accel)
     for kind in (CLOSEST, NEAREST):
         dev = r.trace_ray_records(kind, rays)   # PT_OK
         assert ((dev["status"] & HIT) != 0).mean() > 0.5
@@ -280,7 +279,7 @@ def test_stack_limit(accel):
     r.destroy(); tr.close()
     deep = Config(synth.deep_chain(synth.DEEP_OVERFLOW_LEVELS), env, 64, 48)
     r = renderer(deep.scene, accel)
-    tr = traced(TracedScene, deep.scene)
+    tr = TracedScene(deep.scene)
     away = make_rays([[0, 0, -1e4]], [[0, 0, -1]])   # from behind the camera, away from the chain (which runs along +z for thousands of units): a miss without a walk
     want, over = host_query(tr, two, CLOSEST, away, overflow=True)
     assert over == 0 and want["status"][0] == 0

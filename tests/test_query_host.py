@@ -1,56 +1,28 @@
 """pt_trace_rays' per-ray body on the CPU: vk_raytrace_amd/csrc/pt_query.h (query_ray<TWO>, what the query kernel runs per lane) compiled for the
-host by tests/cpp/query_host.cpp next to the harness of the traversal source, and held ray by ray to the definitions that harness already has:
+host by tests/cpp/query_host.cpp, a unit of the host harness (tests/host_harness.py: qh_query), and held ray by ray to the definitions that harness
+already has:
 
   PT_RAYS_CLOSEST / PT_RAYS_OCCLUDED  th_settle's exact key-ordered loop (trace contract T5 / T6): hit, barycentrics AND the RNG state afterwards
-  PT_RAYS_CANDIDATES                  th_candidates mode 0, brute force over every world triangle, by compare()'s rule of tests/test_trace_host.py
+  PT_RAYS_CANDIDATES                  th_candidates mode 0, brute force over every world triangle, by compare()'s rule of tests/host_harness.py
   PT_RAYS_NEAREST                     the same brute force with TRI_NOCULL forced on every instance (the picker's flag-less ray)
 
-Scenes, rays and rules are test_trace_host's.  tests/test_query_gpu.py runs the same rays through the C ABI on the device and compares them, record
+Scenes, rays and rules are the harness's, the ones tests/test_trace_host.py uses.  tests/test_query_gpu.py runs the same rays through the C ABI on the device and compares them, record
 by record, with what this harness returns (the helpers below are shared with it)."""
-import contextlib
-import ctypes as C
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests import test_trace_host as tth
-from tests.test_trace_host import NONE, NOCULL, OPAQUE, Traced, TracedScene, ill_conditioned, instanced_scene, rays_for, scene_rays
+from tests.host_harness import NONE, NOCULL, OPAQUE, Traced, TracedScene, accidental_differences, alpha_scenes, instanced_scene, rays_for, scene_rays
 from vk_raytrace_amd import capi, host_device as hd
 from vk_raytrace_amd.scene import Scene, translate, rotate_y
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-QSRC = os.path.join(ROOT, "tests", "cpp", "query_host.cpp")
 CLOSEST, OCCLUDED, NEAREST, CANDIDATES = capi.PT_RAYS_CLOSEST, capi.PT_RAYS_OCCLUDED, capi.PT_RAYS_NEAREST, capi.PT_RAYS_CANDIDATES
 HIT, INVALID = capi.PT_RAY_HIT, capi.PT_RAY_INVALID
 INF = np.float32(1e32)  # PT_INFINITY: what th_candidates / th_settle take for "unbounded"
 ACCIDENTAL_CAP = 12     # test_walks_report_brute_force_candidates gives this cap to the host walks on the same rays (see test_candidates_equal_brute_force for what it sees)
-
-
-@contextlib.contextmanager
-def _query_build():
-    """harness() of tests/test_trace_host.py, with its flags, on query_host.cpp (which includes trace_host.cpp): a build flavour of its own"""
-    saved = tth.SRC, tth.FLAVOUR
-    tth.FLAVOURS.setdefault("query", [])
-    tth.SRC, tth.FLAVOUR = QSRC, "query"
-    out = os.path.join(ROOT, "tests", "cpp", "_build", "libtracehost_query.so")
-    extra = [os.path.join(ROOT, "vk_raytrace_amd", "csrc", "pt_query.h"), os.path.join(ROOT, "tests", "cpp", "trace_host.cpp"), os.path.join(ROOT, "include", "pt_types.h")]
-    if os.path.exists(out) and any(os.path.getmtime(d) > os.path.getmtime(out) for d in extra):
-        os.remove(out)
-    try:
-        yield
-    finally:
-        tth.SRC, tth.FLAVOUR = saved
-
-
-def traced(cls, *args, **kw):
-    """a Traced / TracedScene of test_trace_host on the query flavour of the harness: th_* as always, plus qh_query"""
-    with _query_build():
-        tr = cls(*args, **kw)
-    tr.L.qh_query.restype = C.c_uint32
-    tr.L.qh_query.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]
-    return tr
 
 
 def make_rays(org, dirs, tmax=None, seeds=None):
@@ -99,18 +71,6 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def accidental_differences(tr, org, dirs, ref_w, ref_t, w, t, what):
-    """compare()'s rule of tests/test_trace_host.py on candidate lists (n, k): a ray that differs is accepted only when fp32's verdict on one of the
-    two triangles at the first differing position is an artefact (ill_conditioned).  Returns how many rays were accepted that way."""
-    bad = np.nonzero(((w != ref_w) | (bits(t) != bits(ref_t))).any(1))[0]
-    for r in bad:
-        c = int(np.nonzero((w[r] != ref_w[r]) | (bits(t[r]) != bits(ref_t[r])))[0][0])
-        involved = [(ref_w[r, c], ref_t[r, c]), (w[r, c], t[r, c])]
-        assert any(x != NONE and ill_conditioned(tr.world_tri(x), org[r], dirs[r], tx) for x, tx in involved), \
-            f"{what}: ray {r} candidate {c}: reference {ref_w[r]} {ref_t[r]} vs query {w[r]} {t[r]}"
-    return len(bad)
-
-
 def records_equal(a, b):
     """every field of every record, floats by their bits"""
     return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
@@ -126,11 +86,11 @@ def alpha_inputs(tr, eye, spread, n=6000):
 
 
 # ---- alpha scenes: CLOSEST and OCCLUDED against the definition --------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,scene,eye,spread", list(tth._alpha_scenes()), ids=lambda x: x if isinstance(x, str) else None)
+@pytest.mark.parametrize("name,scene,eye,spread", list(alpha_scenes()), ids=lambda x: x if isinstance(x, str) else None)
 def test_closest_and_occluded_equal_the_key_ordered_loop(name, scene, eye, spread):
     """On exactly the inputs on which the existing test finds zero differences among the host legs: every ray's t, u, v (bits), world triangle and
     seed equal th_settle(exact = 1) on the flat structure -- for both structures; the shadow verdict and seed for both variants."""
-    tr = traced(TracedScene, scene)
+    tr = TracedScene(scene)
     org, dirs, seeds, tmax = alpha_inputs(tr, eye, spread)
     ref_w, ref_tuv, ref_seed, ref_draws = tr.settle(0, 0, 1, org, dirs, seeds)
     assert (ref_w != NONE).mean() > 0.5 and ref_draws.sum() > len(org) // 20 and (ref_seed != seeds).any(), "the scene must exercise hits and alpha draws"
@@ -166,7 +126,7 @@ def test_candidates_equal_brute_force(seed):
     measured when this test was written): scene 0: none on either structure; scene 3: 2 rays on the flat and 2 on the two-level structure, 4 in its
     count.  The cap is that test's: 12 -- here per structure."""
     sc, flags, off = instanced_scene(seed)
-    tr = traced(Traced, sc, flags)
+    tr = Traced(sc, flags)
     org, dirs = rays_for(tr, np.random.default_rng(100 + seed), off, 6000)
     ref_w, ref_t = tr.candidates(0, org, dirs, max_cand=6)
     assert (ref_w != NONE).sum() > 8000
@@ -186,8 +146,8 @@ def test_nearest_ignores_culling(seed):
     geometry with TRI_NOCULL forced on every instance, nearest key inside (0, tmax), unbounded and bounded"""
     sc, flags, off = instanced_scene(seed)
     assert (flags & NOCULL).any() and not (flags & NOCULL).all()
-    tr = traced(Traced, sc, flags)
-    brute = traced(Traced, sc, flags | NOCULL)
+    tr = Traced(sc, flags)
+    brute = Traced(sc, flags | NOCULL)
     org, dirs = rays_for(tr, np.random.default_rng(100 + seed), off, 6000)
     culled_w, _ = tr.candidates(0, org, dirs, max_cand=1)
     for tmax in (INF, np.float32(9.0)):
@@ -237,7 +197,7 @@ ALL_KINDS = (CLOSEST, OCCLUDED, NEAREST, CANDIDATES)
 
 def test_degenerate_scenes():
     sc, flags = one_triangle_scene()
-    tr = traced(Traced, sc, flags)
+    tr = Traced(sc, flags)
     ref_w, ref_t = tr.candidates(0, DEGENERATE_ORG, DEGENERATE_DIR, max_cand=1)
     assert (ref_w[:2, 0] == 0).all() and ref_w[2, 0] == NONE
     rays = make_rays(DEGENERATE_ORG, DEGENERATE_DIR, seeds=[5, 6, 7])
@@ -250,7 +210,7 @@ def test_degenerate_scenes():
         assert np.array_equal(got["status"], [HIT, HIT, 0]) and (world_index(sc, got[2:]) == NONE).all() and (got["instanceID"] == NONE).all()
     tr.close()
     for sc, flags in empty_scenes():
-        tr = traced(Traced, sc, flags)
+        tr = Traced(sc, flags)
         for two in (0, 1):
             for kind in ALL_KINDS:
                 got = host_query(tr, two, kind, rays)
@@ -260,7 +220,7 @@ def test_degenerate_scenes():
 
 def test_the_upper_bound_is_exclusive_and_an_empty_range_is_a_miss():
     sc, flags = one_triangle_scene()
-    tr = traced(Traced, sc, flags)
+    tr = Traced(sc, flags)
     t_hit = tr.candidates(0, DEGENERATE_ORG[:1], DEGENERATE_DIR[:1], max_cand=1)[1][0, 0]
     assert t_hit > 0
     tm = np.array([t_hit, np.nextafter(t_hit, np.float32(np.inf)), 0.0, -1.0, -np.inf, np.inf], np.float32)
@@ -301,7 +261,7 @@ def invalid_ray_batch():
 
 def test_invalid_rays_are_reported_per_ray():
     sc, flags = one_triangle_scene()
-    tr = traced(Traced, sc, flags)
+    tr = Traced(sc, flags)
     rays, where = invalid_ray_batch()
     for two in (0, 1):
         for kind in ALL_KINDS:
@@ -319,7 +279,7 @@ def test_invalid_rays_are_reported_per_ray():
 
 def test_sixteen_results_for_a_ray_with_three_candidates():
     sc, flags = three_layer_scene()
-    tr = traced(Traced, sc, flags)
+    tr = Traced(sc, flags)
     rays = make_rays([[0, -0.2, 5]], [[0, 0, -1]], seeds=9)
     for two in (0, 1):
         got = host_query(tr, two, CANDIDATES, rays, hits_per_ray=16)[0]

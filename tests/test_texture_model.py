@@ -551,7 +551,6 @@ def test_opacity_maps_never_change_a_result(gen):
     mats, taps = alpha_materials(), alpha_taps()
     assert len(taps) >= 16 * 16 * 64 * len(WINDOWS)
     hs = io.HostScene(sc)
-    hs.L.th_clear_fast_tap.argtypes = [C.c_void_p]
     answered, poked, clears, results = 0, 0, [], []
     for m, (mode, cutoff, factor, tex) in enumerate(mats):
         am = hs.alpha_mats[m]

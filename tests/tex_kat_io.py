@@ -95,18 +95,12 @@ class HostScene:
     """the product's records, lines, maps and pool for a scene (tests/cpp/trace_host.cpp th_create_scene) under one PT_TUNE setting"""
 
     def __init__(self, scene, tune=None, expect_error=False):
-        from tests.test_trace_host import harness
-        L = self.L = harness()
-        L.th_create_scene.restype = C.c_void_p
-        L.th_create_scene.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-        L.th_texture_probe.restype = C.c_int
-        L.th_texture_probe.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.th_texture_records.argtypes = [C.c_void_p] * 7
-        L.th_set_env.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        from tests import host_harness
+        L = self.L = host_harness.lib()
         d, self.keep = scene.desc()
         err = C.create_string_buffer(256)
         with tuned(tune):
-            self.h = L.th_create_scene(C.byref(d), err, 256)
+            self.h = L.th_create_scene(C.byref(d), err, 256, host_harness.MERGE_SINGLES)
         self.error = err.value.decode()
         if expect_error:
             return

@@ -2,7 +2,6 @@
 (vk_raytrace_amd/csrc/pt_probe.h trace_probe) and the assertions, written once so that the host build, the oracle and the device are held to the same ones.
 Every probe -- th_trace_probe, orc_trace_probe, pt_debug_trace_probe -- takes (kind, n, in, in_stride, out, out_stride); integers travel as bit patterns.
 The derivations behind the numbers used here (the T2 bound, the margins of the box tests, the order rule) are in the generator's docstring."""
-import ctypes as C
 import importlib.util
 import os
 
@@ -43,10 +42,8 @@ def probe(fn, kind, rows, ctx=None):
 
 
 def host_fn():
-    from tests.test_trace_host import harness
-    L = harness()
-    L.th_trace_probe.restype, L.th_trace_probe.argtypes = C.c_int, [C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    return L.th_trace_probe
+    from tests import host_harness
+    return host_harness.lib().th_trace_probe
 
 
 def orc_fn():

@@ -25,7 +25,7 @@ KINDS = (("CLOSEST", capi.PT_RAYS_CLOSEST, 1), ("OCCLUDED", capi.PT_RAYS_OCCLUDE
 
 
 def primary_rays(cam, width, height):
-    """camera rays through the pixel centres (pinhole): the formula of tests/test_trace_host.py _deep_rays"""
+    """camera rays through the pixel centres (pinhole): the formula of tests/host_harness.py deep_rays"""
     t = np.tan(np.radians(cam.fov) / 2)
     ys, xs = np.mgrid[0:height, 0:width]
     d = np.stack([(2 * (xs + 0.5) / width - 1) * t * width / height, (1 - 2 * (ys + 0.5) / height) * t, np.ones(xs.shape)], -1).reshape(-1, 3)

@@ -1,9 +1,8 @@
 """CPU experiment (no GPU): how deep does the traversal stack of the persistent trace kernels get?  The product's lane machine (pt_machine.h, compiled
-for the host by tests/cpp/trace_host.cpp) walks camera, bounce and shadow rays over the C3 stand-in's flat structure; per ray the deepest stack level
+for the host by the host harness, tests/host_harness.py) walks camera, bounce and shadow rays over the C3 stand-in's flat structure; per ray the deepest stack level
 used.  The kernels keep the first STACK_LDS = 24 levels in LDS and the rest in a private array (the 160 B of "scratch" in profiles/*_kernel_usage.txt):
 this says how often that array is touched at all.
    python tools/stack_depth_experiment.py [rays] [c3|c5]"""
-import ctypes as C
 import os
 import sys
 
@@ -11,27 +10,15 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import tests.test_trace_host as T  # noqa: E402
+import tests.host_harness as T  # noqa: E402
 from vk_raytrace_amd import workloads  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 200000
 which = sys.argv[2] if len(sys.argv) > 2 else "c3"
 wl = workloads.c3_sponza(tex_size=64) if which == "c3" else workloads.c5_bistro(tex_size=32)
 tr = T.TracedScene(wl.scene)
-L = tr.L
-L.th_take_sp_hist.argtypes = [C.c_void_p]
 rng = np.random.default_rng(1)
-cam = wl.scene.camera
-eye = np.array(cam.eye, np.float64)
-fwd = np.array(cam.center, np.float64) - eye
-fwd /= np.linalg.norm(fwd)
-right = np.cross(fwd, np.array(cam.up, np.float64)); right /= np.linalg.norm(right)
-up = np.cross(right, fwd)
-th = np.tan(np.radians(cam.fov) / 2)
-px = rng.uniform(-1, 1, (n, 2)) * (th * 16 / 9, th)
-d0 = fwd + px[:, :1] * right + px[:, 1:] * up
-d0 /= np.linalg.norm(d0, axis=1, keepdims=True)
-o0 = np.repeat(eye[None], n, 0)
+o0, d0 = T.camera_rays(wl.scene.camera, rng, n)
 seeds = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
 w, tuv, _, _ = tr.settle(0, 0, 0, o0, d0, seeds)
 hit = w != T.NONE
@@ -44,10 +31,7 @@ tmax = np.full(len(p1), 1e32, np.float32)
 print(f"{which} stand-in, {tr.n} triangles; per ray the deepest level of the traversal stack (entries = 32-bit child references: leaf bit + alpha bit + up to 22 bits of slot)")
 for name, kind, o, d, tm in (("camera rays", 0, o0, d0, None), ("bounce rays (random direction from a surface point)", 0, o1, d1, None), ("shadow rays (upper hemisphere, unbounded)", 1, os_, ds, tmax)):
     o32, d32 = np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d, np.float32)
-    hist = np.zeros(65, np.uint64)
-    L.th_take_sp_hist(hist.ctypes.data)
-    tr.settle(kind, 0, 2, o32, d32, seeds[:len(o32)], tm)
-    L.th_take_sp_hist(hist.ctypes.data)
+    hist = tr.settle(kind, 0, 2, o32, d32, seeds[:len(o32)], tm, sp_hist=True)[4]
     tot = hist.sum()
     cum = np.cumsum(hist) / tot
     deepest = int(np.nonzero(hist)[0].max())

@@ -1,9 +1,8 @@
 """CPU experiment (no GPU): dependent memory round trips per ray of a closest-hit walk over the C3 stand-in's flat structure -- the quantity that
 bounds the trace stages (a stage lasts as long as its slowest ray, a chain of node / triangle fetches) -- for the product's
 4-wide nodes with one triangle per step (what the kernels do today), with the hit leaf children of a node fetched together, and for 8-wide nodes.
-Uses the binary tree the device builder produces (host emulation) and the test harness tests/cpp/trace_host.cpp (th_step_model).
+Uses the binary tree the device builder produces (host emulation) and the "steps" flavour of the host harness (tests/cpp/experiments/step_model.cpp).
    python tools/steps_experiment.py [rays]"""
-import ctypes as C
 import os
 import sys
 
@@ -11,26 +10,15 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import tests.test_trace_host as T  # noqa: E402
+import tests.host_harness as T  # noqa: E402
 from vk_raytrace_amd import workloads  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 40000
 wl = workloads.c3_sponza(tex_size=64)
-tr = T.TracedScene(wl.scene)
+tr = T.TracedScene(wl.scene, flavour="steps")
 L = tr.L
-L.th_step_model.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 rng = np.random.default_rng(1)
-cam = wl.scene.camera
-eye = np.array(cam.eye, np.float64)
-fwd = np.array(cam.center, np.float64) - eye
-fwd /= np.linalg.norm(fwd)
-right = np.cross(fwd, np.array(cam.up, np.float64)); right /= np.linalg.norm(right)
-up = np.cross(right, fwd)
-th = np.tan(np.radians(cam.fov) / 2)
-px = rng.uniform(-1, 1, (n, 2)) * (th * 16 / 9, th)
-d0 = fwd + px[:, :1] * right + px[:, 1:] * up
-d0 /= np.linalg.norm(d0, axis=1, keepdims=True)
-o0 = np.repeat(eye[None], n, 0)
+o0, d0 = T.camera_rays(wl.scene.camera, rng, n)
 seeds = np.zeros(n, np.uint32)
 w, tuv, _, _ = tr.settle(0, 0, 0, o0, d0, seeds)
 hit = w != T.NONE
