@@ -14,8 +14,8 @@
  *    pt_get_stats and pt_synchronize wait for it.
  *  - Traversal-stack overflow: a ray whose walk needs more than 64 stack entries drops a subtree, so the image misses geometry.  Once
  *    such an overflow has been counted, every call that hands out results returns PT_ERR_STATE ("BVH traversal stack overflowed ...")
- *    instead of PT_OK: pt_synchronize, pt_read_accum, pt_tonemap, pt_tonemap_zoom, pt_tonemap_end, pt_pick, pt_trace_rays, pt_local_shard,
- *    pt_gather_shards and pt_get_stats, and pt_tonemap_begin once the overflow is known (it then enqueues nothing).  The state stays
+ *    instead of PT_OK: pt_synchronize, pt_read_accum, pt_tonemap, pt_tonemap_zoom, pt_tonemap_end, pt_denoise, pt_tonemap_denoised, pt_pick,
+ *    pt_trace_rays, pt_local_shard, pt_gather_shards and pt_get_stats, and pt_tonemap_begin once the overflow is known (it then enqueues nothing).  The state stays
  *    until pt_reset_stats or the next pt_build_accel (a new scene) clears it; images begun before the clear no longer report it.
  *  - there is no CPU fallback: without a gfx950 device pt_create fails with PT_ERR_NO_DEVICE.
  */
@@ -177,6 +177,31 @@ int pt_tonemap_zoom(pt_context* ctx, const pt_Tonemapper* tm, int disp_width, in
 int pt_tonemap_begin(pt_context* ctx, const pt_Tonemapper* tm, int disp_width, int disp_height);
 int pt_tonemap_end(pt_context* ctx, uint8_t* rgba8_out);
 int pt_tonemap_pending(pt_context* ctx);
+
+/* ---- denoiser (no reference counterpart: the reference displays its accumulation image unfiltered) -------------------------------------------
+ * An edge-avoiding a-trous filter (Dammertz et al. 2010) as a stage of its own between the accumulation image and the display pass; DESIGN.md
+ * "Denoiser" has the definition, csrc/pt_denoise.h the one fp32 operation sequence host and device share.  The stage reads the row-major image
+ * pt_read_accum returns and guide planes the CALLER supplies -- typically frame-0 debug frames (base colour, normal) and pt_trace_rays depths, all
+ * obtained through entry points that exist already; no render kernel captures anything for it. */
+
+/* No reference counterpart.  Installs the guide planes: planes[j] is NULL (plane j unset) or a row-major image of width * height * 4 floats whose
+ * .xyz are read; copied before the call returns.  Guides must be finite (the filter's result is unspecified otherwise; its reads stay in bounds).
+ * PT_ERR_STATE before pt_resize; a pt_resize to another size drops every plane, because its size no longer fits.  planes == NULL: PT_ERR_INVALID. */
+int pt_set_denoise_guides(pt_context* ctx, const float* const planes[PT_DENOISE_GUIDES]);
+
+/* No reference counterpart.  The image pt_read_accum would return, filtered: row-major width * height * 4 floats, alpha copied.  Synchronous like
+ * pt_read_accum: waits for the frames in flight and reports their traversal-stack overflow with PT_ERR_STATE.  Read-only with respect to rendering:
+ * the accumulation tiles, the path state, the frame slots and every pt_Stats field stay as they are, and a frame rendered afterwards continues the
+ * running mean as if the call had not happened.  PT_ERR_STATE: before pt_resize; PT_DENOISE_DEMODULATE without guide plane 0; nranks > 1 without a
+ * gathered image (a filter over the zero-filled tiles of other ranks means nothing).  PT_ERR_INVALID, with nothing launched: null arguments,
+ * iterations outside 1 .. 8, sigmaColor negative or NaN, sigmaGuide of an installed plane not positive and finite, a sigma so small that 1 / sigma^2
+ * overflows, unknown flag bits. */
+int pt_denoise(pt_context* ctx, const pt_DenoiseParams* params, float* rgba32f_out);
+
+/* No reference counterpart.  pt_tonemap (viewport = accumulation size) with the denoised image as level 0 of the offscreen image: the bytes are those
+ * of pt_tonemap on a context whose accumulation image was replaced by pt_denoise's output with pt_write_accum.  Synchronous; errors as pt_denoise
+ * and pt_tonemap.  (Not provided: the pt_tonemap_begin / pt_tonemap_end form and pt_tonemap_zoom of a denoised image.) */
+int pt_tonemap_denoised(pt_context* ctx, const pt_DenoiseParams* params, const pt_Tonemapper* tm, uint8_t* rgba8_out);
 
 /* Test access to the image the display pass samples: builds the offscreen image of a disp_width x disp_height viewport and its full mip chain exactly
  * as pt_tonemap_zoom does with auto-exposure on, and copies level `level` (RGBA32F, row-major) to rgba32f_out, its extent to *width / *height (each may

@@ -118,6 +118,15 @@ public:
   void tonemapBegin(const pt_Tonemapper& tm, int dispW, int dispH) { check(pt_tonemap_begin(m_ctx, &tm, dispW, dispH)); }
   void tonemapEnd(uint8_t* rgba8) { check(pt_tonemap_end(m_ctx, rgba8)); }
   int  tonemapPending() const { return pt_tonemap_pending(m_ctx); }
+  // the edge-avoiding a-trous denoiser between the accumulation image and the display pass (no reference counterpart): guide planes from the caller
+  // (each NULL or width * height * 4 floats: albedo, normal, depth), the filtered accumulation image, and the display pass of it
+  bool setDenoiseGuides(const float* albedo, const float* normal, const float* depth)
+  {
+    const float* const planes[PT_DENOISE_GUIDES] = {albedo, normal, depth};
+    return check(pt_set_denoise_guides(m_ctx, planes));
+  }
+  bool denoise(const pt_DenoiseParams& p, float* rgba32f) { return check(pt_denoise(m_ctx, &p, rgba32f)); }
+  bool tonemapDenoised(const pt_DenoiseParams& p, const pt_Tonemapper& tm, uint8_t* rgba8) { return check(pt_tonemap_denoised(m_ctx, &p, &tm, rgba8)); }
 
   bool               ok() const { return m_status == PT_OK; }
   int                status() const { return m_status; }

@@ -255,6 +255,18 @@ enum { PT_RAYS_CLOSEST = 0, PT_RAYS_OCCLUDED = 1, PT_RAYS_NEAREST = 2, PT_RAYS_C
 #define PT_RAYS_MAX_HITS 16u   /* largest hits_per_ray of PT_RAYS_CANDIDATES */
 #define PT_QUERY_CHUNK (1u << 20) /* host arrays are staged through two device buffers of this many records (32 MB each) */
 
+/* pt_denoise / pt_tonemap_denoised: the edge-avoiding a-trous filter between the accumulation image and the display pass (no reference counterpart;
+ * defined in DESIGN.md "Denoiser" and stated once in csrc/pt_denoise.h).  Guide planes are row-major RGBA32F images of the accumulation size whose
+ * .xyz steer the weights; by convention plane 0 is the albedo (the only one PT_DENOISE_DEMODULATE reads), 1 the normal, 2 the depth in .x. */
+#define PT_DENOISE_GUIDES 3
+#define PT_DENOISE_DEMODULATE 1u /* pt_DenoiseParams::flags bit 0: filter colour / max(albedo, 0.001) and multiply the albedo back afterwards */
+typedef struct pt_DenoiseParams {
+  int32_t  iterations;                    /* 1 .. 8; iteration i taps at distance 2^i */
+  float    sigmaColor;                    /* standard deviation of the colour term at iteration 0, halved every iteration; 0: no colour term */
+  float    sigmaGuide[PT_DENOISE_GUIDES]; /* of the term of guide plane j; read only for the planes that are installed */
+  uint32_t flags;                         /* PT_DENOISE_DEMODULATE */
+} pt_DenoiseParams;
+
 /* Counters the measurement contract needs; all totals since pt_reset_stats. */
 typedef struct pt_Stats {
   uint64_t samples;          /* pixel-samples rendered */
@@ -317,6 +329,7 @@ static_assert(sizeof(pt_SunAndSky) == 96, "SunAndSky");
 static_assert(sizeof(pt_PrimMesh) == 20, "PrimMesh");
 static_assert(sizeof(pt_Node) == 68, "Node");
 static_assert(sizeof(pt_Ray) == 32 && sizeof(pt_RayHit) == 32, "Ray / RayHit");
+static_assert(sizeof(pt_DenoiseParams) == 24, "DenoiseParams");
 #endif
 
 #endif /* PT_TYPES_H */

@@ -18,6 +18,8 @@ PT_RAY_HIT, PT_RAY_INVALID = 1, 2  # pt_RayHit.status bits
 PT_RAYS_DEVICE = 1  # pt_trace_rays flag: rays / hits are device pointers
 PT_RAYS_MAX_HITS = 16
 PT_QUERY_CHUNK = 1 << 20  # records per staging buffer of the host-pointer path
+PT_DENOISE_GUIDES = 3  # guide planes of the denoiser (include/pt_types.h)
+PT_DENOISE_DEMODULATE = 1  # pt_DenoiseParams.flags
 PT_DISPLAY_RING = 8  # images pt_tonemap_begin may have pending (include/pt_api.h)
 PT_FN = {"sin": 0, "cos": 1, "tan": 2, "asin": 3, "acos": 4, "atan2": 5, "exp": 6, "log": 7, "pow": 8}
 PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_ERR_STATE, PT_ERR_OOM, PT_ERR_UNAVAILABLE = 0, -1, -2, -3, -4, -5, -6
@@ -54,6 +56,9 @@ API = [
     ("pt_tonemap_begin", C.c_int, [_P, C.POINTER(hd.Tonemapper), C.c_int, C.c_int]),
     ("pt_tonemap_end", C.c_int, [_P, _P]),
     ("pt_tonemap_pending", C.c_int, [_P]),
+    ("pt_set_denoise_guides", C.c_int, [_P, C.POINTER(_P)]),
+    ("pt_denoise", C.c_int, [_P, C.POINTER(hd.DenoiseParams), _P]),
+    ("pt_tonemap_denoised", C.c_int, [_P, C.POINTER(hd.DenoiseParams), C.POINTER(hd.Tonemapper), _P]),
     ("pt_debug_display_level", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_local_shard", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_scatter_shards", C.c_int, [_P, _P, C.c_int]),
@@ -93,6 +98,8 @@ DEBUG_API = [
     ("pt_debug_texture_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h texture_probe, on the context's scene: (ctx, kind, n, in, in_stride, out, out_stride)
     ("pt_debug_surface_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h surface_probe, on the context's scene: (ctx, kind, n, in, in_stride, out, out_stride); 1: no such data
     ("pt_debug_trace_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h trace_probe, every load inside the row: (ctx, kind, n, in, in_stride, out, out_stride)
+    ("pt_debug_denoise_lds", C.c_int, [_P, C.c_int]),  # csrc/pt_denoise.hip: (ctx, largest step staged in LDS; negative: the default) -> the value in force
+    ("pt_debug_denoise_time", C.c_int, [_P, C.POINTER(hd.DenoiseParams), C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_denoise.hip: (ctx, params, reps, ms per run out): the filter alone, device events
     ("pt_debug_bounce_counts", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[max_bounces][16], max_bounces) -> staged bounces of the newest finished launch sequence
 ]
 

@@ -333,6 +333,7 @@ int pt_destroy(pt_context* c)
                    &c->dMean, &c->dMips, &c->dGather, &c->dFullTiles, &c->dFullSlotTile, &c->dTileLocalIndex};
   for(DevBuf* b : all)
     dev_free(*b);
+  denoise_release(c);
   for(auto& fs : c->slots)
   {
     fs.release_paths();
@@ -638,6 +639,7 @@ int pt_resize(pt_context* c, int width, int height)
     return PT_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_all(c));
+  denoise_release(c);  // the denoiser's buffers and the guide planes were sized for the old image
   c->tilesX = (width + PT_TILE - 1) / PT_TILE;
   c->tilesY = (height + PT_TILE - 1) / PT_TILE;
   std::vector<uint32_t> local;
@@ -934,7 +936,10 @@ int pt_synchronize(pt_context* c)
   return check_traversal(c);
 }
 
-static int untile_to_rowmajor(pt_context* c)
+}  // extern "C"
+// The row-major accumulation image (dRowMajor), enqueued on the context's stream behind the frames rendered so far: what pt_read_accum copies out and
+// what the display pass and the denoiser (pt_denoise.hip) read
+int untile_to_rowmajor(pt_context* c)
 {
   int rc = flush_pending(c);
   if(rc != PT_OK)
@@ -950,6 +955,7 @@ static int untile_to_rowmajor(pt_context* c)
   HIP_TRY(c, hipGetLastError());
   return PT_OK;
 }
+extern "C" {
 
 int pt_read_accum(pt_context* c, float* out)
 {
@@ -1010,6 +1016,8 @@ int pt_pick(pt_context* c, float pick_x, float pick_y, const float* view_inverse
 // the accumulation image itself, or a viewport-sized image with it in the top-left corner (texels outside: zero); levels 1.. only with `chain`
 // (src/sample_example.cpp:423-427 generates the chain only with auto-exposure): extent max(1, e / 2), floor(log2(max(w, h))) + 1 levels.
 // readDone (may be null): recorded once the accumulation image has been read, and made the event the next frame's accumulate step waits for.
+// display_chain chooses level 0 -- the accumulation image; display_levels is everything after that choice, shared with the denoised pass
+// (pt_denoise.hip), whose level 0 is the filtered image.
 int display_chain(pt_context* c, int dispW, int dispH, bool chain, hipEvent_t readDone, MipView& mv)
 {
   if(c->width == 0)
@@ -1025,6 +1033,11 @@ int display_chain(pt_context* c, int dispW, int dispH, bool chain, hipEvent_t re
     HIP_TRY(c, hipEventRecord(readDone, c->stream));
     c->lastAccum = readDone;
   }
+  return display_levels(c, (const float4*)c->dRowMajor.p, dispW, dispH, chain, mv);
+}
+int display_levels(pt_context* c, const float4* image, int dispW, int dispH, bool chain, MipView& mv)
+{
+  int        rc;
   const bool padded = dispW != c->width || dispH != c->height;
   size_t     texels = padded ? size_t(dispW) * dispH : 0, offset = texels;
   int        lw = dispW, lh = dispH, levels = 1;
@@ -1040,8 +1053,8 @@ int display_chain(pt_context* c, int dispW, int dispH, bool chain, hipEvent_t re
     return rc;
   float4* pool = (float4*)c->dMips.p;
   if(padded)
-    pt_launch_pad_corner(c->stream, (const float4*)c->dRowMajor.p, c->width, c->height, pool, dispW, dispH);
-  mv.level[0] = padded ? pool : (const float4*)c->dRowMajor.p;
+    pt_launch_pad_corner(c->stream, image, c->width, c->height, pool, dispW, dispH);
+  mv.level[0] = padded ? pool : image;
   mv.w[0] = dispW; mv.h[0] = dispH; mv.n = levels;
   for(int i = 1; i < levels; ++i)
   {
@@ -1078,6 +1091,12 @@ static int enqueue_tonemap(pt_context* c, const pt_Tonemapper* tm, int dispW, in
   MipView mv{};
   if((rc = display_chain(c, dispW, dispH, (tm->autoExposure & 1) != 0, readDone, mv)) != PT_OK)
     return rc;
+  return display_finish(c, tm, mv, dispW, dispH, out);
+}
+// ... from the offscreen image on: the tonemap kernel and the copy
+int display_finish(pt_context* c, const pt_Tonemapper* tm, MipView& mv, int dispW, int dispH, uint8_t* out)
+{
+  int rc;
   select_levels(mv, tm->zoom);
   if((rc = dev_alloc(c, c->dRgba8, 4 * size_t(dispW) * dispH)) != PT_OK)
     return rc;

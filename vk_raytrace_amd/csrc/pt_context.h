@@ -121,6 +121,9 @@ struct pt_context {
   DevBuf   dPick;
   DevBuf   dQueryRays, dQueryHits;  // pt_trace_rays with host arrays: staging buffers of PT_QUERY_CHUNK records each, allocated on first use
   DevBuf   dRowMajor, dRgba8, dMean, dMips, dGather, dFullTiles, dFullSlotTile, dTileLocalIndex;
+  // denoiser (pt_denoise.hip): the two ping-pong images, allocated on first use, and the caller's guide planes; pt_resize and pt_destroy free them
+  DevBuf   dDenoise[2], dGuide[PT_DENOISE_GUIDES];
+  int      denoiseLdsMaxStep = -1;  // largest step whose iteration stages its tile in LDS (-1: the measured default; pt_debug_denoise_lds)
   bool     haveFull = false;
   // pipelined display (pt_tonemap_begin / pt_tonemap_end): a ring of pinned host images, each with the event that says its copy has landed
   // and the event after which the accumulation image may be written again (the untile pass has read it)
@@ -168,7 +171,11 @@ int        flush_pending(pt_context* c);    // launches the frames handed to pt_
 hipError_t sync_all(pt_context* c);         // flush_pending, then waits for every stream of the context
 int        check_traversal(pt_context* c);  // after a synchronisation: PT_ERR_STATE once a traversal ran out of stack
 void       clear_overflow(pt_context* c);
+int        untile_to_rowmajor(pt_context* c);  // the row-major accumulation image in dRowMajor, enqueued behind the frames rendered so far
 int        display_chain(pt_context* c, int dispW, int dispH, bool chain, hipEvent_t readDone, MipView& mv);  // the display pass's offscreen image and its mip chain, enqueued
+int        display_levels(pt_context* c, const float4* image, int dispW, int dispH, bool chain, MipView& mv);  // ... the part after level 0 (`image`, accumulation size) is chosen
+int        display_finish(pt_context* c, const pt_Tonemapper* tm, MipView& mv, int dispW, int dispH, uint8_t* out);  // ... the tonemap kernel and the copy to `out` (host), enqueued
+void       denoise_release(pt_context* c);  // pt_denoise.hip: frees the denoiser's images and drops the guide planes
 void       refresh_scene_ptrs(pt_context* c);
 int        upload_instances(pt_context* c);
 std::vector<InstanceRec> effective_instances(const pt_context* c);  // the instance records as the kernels see them

@@ -115,6 +115,11 @@ class RayHit(C.Structure):
                 ("seed", C.c_uint32), ("status", C.c_uint32)]
 
 
+class DenoiseParams(C.Structure):
+    """pt_DenoiseParams (pt_denoise, pt_tonemap_denoised): sigmaColor 0 switches the colour term off; sigmaGuide[j] is read for installed planes only"""
+    _fields_ = [("iterations", C.c_int32), ("sigmaColor", C.c_float), ("sigmaGuide", C.c_float * 3), ("flags", C.c_uint32)]
+
+
 class Peaks(C.Structure):
     """pt_Peaks (pt_measure_peaks): ceilings measured on the device"""
     _fields_ = [("valuWaveInstrPerSec", C.c_double), ("hbmCopyBytesPerSec", C.c_double), ("hbmReadBytesPerSec", C.c_double), ("computeUnits", C.c_int32),
@@ -141,7 +146,7 @@ class Stats(C.Structure):
 assert C.sizeof(RtxState) == 48 and C.sizeof(SceneCamera) == 140 and C.sizeof(VertexAttributes) == 32
 assert C.sizeof(GltfShadeMaterial) == 216 and C.sizeof(Light) == 64 and C.sizeof(EnvAccel) == 16
 assert C.sizeof(Tonemapper) == 48 and C.sizeof(SunAndSky) == 96 and C.sizeof(PrimMesh) == 20 and C.sizeof(Node) == 68
-assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
+assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32 and C.sizeof(DenoiseParams) == 24
 
 vertex_dtype = np.dtype(VertexAttributes)
 ray_dtype = np.dtype(Ray)

@@ -44,6 +44,21 @@ class Renderer:
         self.m_state = state
 
 
+def pixel_centre_rays(cam: hd.SceneCamera, width, height):
+    """The pinhole camera rays through the pixel centres, built the way pt_pick builds its ray from a window position:
+    origin = viewInverse * (0, 0, 0, 1), direction = viewInverse * (normalize((projInverse * (d, 1, 1)).xyz), 0) with d = 2 * (pixel + 0.5) / size - 1.
+    Returns (origins, directions), float32 arrays of shape (height * width, 3) in row-major pixel order."""
+    vi = np.array(cam.viewInverse, np.float64).reshape(4, 4).T  # column-major storage
+    pi = np.array(cam.projInverse, np.float64).reshape(4, 4).T
+    ys, xs = np.mgrid[0:height, 0:width]
+    d = np.stack([2 * (xs + 0.5) / width - 1, 2 * (ys + 0.5) / height - 1, np.ones(xs.shape), np.ones(xs.shape)], -1).reshape(-1, 4)
+    target = d @ pi.T
+    t3 = target[:, :3] / np.linalg.norm(target[:, :3], axis=1, keepdims=True)
+    directions = t3 @ vi[:3, :3].T
+    origins = np.broadcast_to(vi[:3, 3], directions.shape)
+    return np.ascontiguousarray(origins, np.float32), np.ascontiguousarray(directions, np.float32)
+
+
 class HipRenderer(Renderer):
     """libptmi.so behind the reference's Renderer interface."""
 
@@ -53,6 +68,7 @@ class HipRenderer(Renderer):
         self._ctx = None
         self._display_sizes = []  # viewports of the images begun with tonemap_begin and not collected yet
         self._keep = None
+        self._camera = None
         self.size = (0, 0)
         self.env_integral = 1.0
         self.env_average = 1.0
@@ -116,6 +132,7 @@ class HipRenderer(Renderer):
 
     def set_camera(self, cam: hd.SceneCamera):
         self._check(self._lib.pt_set_camera(self._ctx, C.byref(cam)))
+        self._camera = hd.SceneCamera.from_buffer_copy(cam)  # render_guides shoots its depth rays through it
 
     def set_sunsky(self, ss: hd.SunAndSky):
         self._check(self._lib.pt_set_sunsky(self._ctx, C.byref(ss)))
@@ -202,6 +219,54 @@ class HipRenderer(Renderer):
         else:
             self._check(self._lib.pt_tonemap_zoom(self._ctx, C.byref(tm), w, h, out.ctypes.data))
         return out
+
+    # -- denoiser (no reference counterpart) ----------------------------------------------------------
+    def set_denoise_guides(self, albedo=None, normal=None, depth=None):
+        """pt_set_denoise_guides: each plane is None (unset) or an (H, W, 4) float32 image whose .xyz steer the filter's weights"""
+        w, h = self.size
+        planes = [None if p is None else np.ascontiguousarray(p, np.float32) for p in (albedo, normal, depth)]
+        for p in planes:
+            if p is not None and p.shape != (h, w, 4):
+                raise ValueError(f"set_denoise_guides: a plane of shape {p.shape}, the image is {(h, w, 4)}")
+        ptrs = (C.c_void_p * capi.PT_DENOISE_GUIDES)(*[None if p is None else p.ctypes.data for p in planes])
+        self._check(self._lib.pt_set_denoise_guides(self._ctx, ptrs))
+
+    def denoise(self, params: hd.DenoiseParams):
+        """pt_denoise: the image read_accum() would return, filtered ((H, W, 4) float32)"""
+        w, h = self.size
+        out = np.empty((h, w, 4), np.float32)
+        self._check(self._lib.pt_denoise(self._ctx, C.byref(params), out.ctypes.data))
+        return out
+
+    def tonemap_denoised(self, params: hd.DenoiseParams, tm: hd.Tonemapper):
+        """pt_tonemap_denoised: tonemap() of the denoised image"""
+        w, h = self.size
+        out = np.empty((h, w, 4), np.uint8)
+        self._check(self._lib.pt_tonemap_denoised(self._ctx, C.byref(params), C.byref(tm), out.ctypes.data))
+        return out
+
+    def render_guides(self, state: hd.RtxState, miss_depth=1.0e30):
+        """Guide planes for the current camera, from entry points that exist for other purposes: one frame-0 debug frame each for base colour and
+        normal, and the closest-hit distance of the pixel-centre camera rays (`t` in .x; `miss_depth` where nothing is hit).  Installs all three
+        and returns them.  To be called right after a camera change, before frame 0 of the real accumulation: frame 0 overwrites the accumulation
+        image, so nothing needs saving.  `state`: the push constants of the frames to come (not modified); the camera is what set_camera was given."""
+        if self._camera is None:
+            raise capi.PtError(capi.PT_ERR_STATE, "render_guides before set_camera")
+        w, h = self.size
+        st = hd.RtxState.from_buffer_copy(state)
+        st.frame, st.size[0], st.size[1] = 0, w, h
+        planes = []
+        for mode in (hd.eBaseColor, hd.eNormal):
+            st.debugging_mode = mode
+            self._check(self._lib.pt_render_frame(self._ctx, C.byref(st)))
+            planes.append(self.read_accum())
+        origins, directions = pixel_centre_rays(self._camera, w, h)
+        hits = self.trace_rays(capi.PT_RAYS_CLOSEST, origins, directions)
+        depth = np.zeros((h, w, 4), np.float32)
+        depth[..., 0] = np.where(hits["status"] & capi.PT_RAY_HIT, hits["t"], np.float32(miss_depth)).reshape(h, w)
+        planes.append(depth)
+        self.set_denoise_guides(*planes)
+        return tuple(planes)
 
     def tonemap_begin(self, tm: hd.Tonemapper, display_size=None):
         """pt_tonemap_begin: the display pass enqueued behind the frames rendered so far; later frames overlap it.  tonemap_end() returns the
