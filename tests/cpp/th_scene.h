@@ -3,8 +3,9 @@
 //
 // Topology comes from the product's device builder run through its host emulation (pt_debug_sahdev_topology in libptmi.so); boxes, the 4-wide
 // collapse, the vertex form of BLAS leaves and the TLAS proxies restate pt_accel.hip (k_gather's tri_box, k_collapse, k_blas_vertex_form,
-// k_instance_proxies) -- they only have to be valid structures of that format, the code under test is the walk.  build_structures at the end
-// of this file spells out the stages.
+// k_instance_proxies).  The restated stages are held, node by node, to the same auditor as the device's own arrays (tests/accel_audit.py through
+// th_accel_read; tests/test_accel_audit.py), so a walk test that passes here passes on a structure with the invariants DESIGN.md "What the build
+// guarantees" lists.  build_structures at the end of this file spells out the stages.
 #pragma once
 #include "th_shims.h"
 #include "pt_shade.h"    // pt_settle.h (pt_trace.h + the per-ray settle functions k_tail runs) + the shading steps of a path (generate_ray, shade_path, ...)
@@ -208,6 +209,10 @@ struct Scene {
   std::vector<uint32_t>    instBlock;  // DeviceScene::instBlock (pt_capi_accel.hip build_tlas)
   std::vector<CompactNode> flatCNodes, blasCNodes, tlasCNodes;  // TH_COMPACT_NODES: the nodes in the compact form (read by lane_inner only)
   bool                     compactOk = false;  // ... and every node of the three structures could be encoded
+  // what th_accel_info / th_accel_read report of the two-level build (pt_accel_dump.h)
+  std::vector<uint32_t>    instNodeBase, blasRanges, mergedList;
+  uint32_t                 mergedTris = 0, mergedWide = 0, numActive = 0;
+  float                    mergedBox[6] = {0, 0, 0, 0, 0, 0};
   std::vector<AlphaMat>    alphaMats;   // th_create_scene: the product's own records (pt_debug_scene_records)
   std::vector<uint32_t>    alphaMaps, texels;
   std::vector<TexRec>      texRecs;
@@ -383,9 +388,12 @@ inline void build_tlas(Scene* s, const TwoLevelPlan& plan)
     prox.push_back(r);
   }
   if(plan.haveMerged)
-  {  // the merged structure's proxy (pt_tlas_build): its root box
+  {  // the merged structure's proxy (pt_tlas_build): its root box, opaque when every merged triangle is
+    bool opaque = true;
+    for(uint32_t i = 0; i < uint32_t(s->inst.size()); ++i)
+      opaque = opaque && (!plan.isMerged[i] || (s->inst[i].flags & TRI_OPAQUE));
     TriRec r;
-    r.p0w = make_float4(plan.mlo[0], plan.mlo[1], plan.mlo[2], __uint_as_float(TRI_INDEX_MASK));
+    r.p0w = make_float4(plan.mlo[0], plan.mlo[1], plan.mlo[2], __uint_as_float(TRI_INDEX_MASK | (opaque ? TRI_OPAQUE << 29 : 0u)));
     r.e1n = make_float4(plan.mhi[0] - plan.mlo[0], plan.mhi[1] - plan.mlo[1], plan.mhi[2] - plan.mlo[2], 0.f);
     r.e2p = make_float4(0.f, 0.f, 0.f, 0.f);
     prox.push_back(r);
@@ -497,6 +505,39 @@ inline void build_structures(Scene* s)
   build_blases(s, plan);
   build_tlas(s, plan);
   bind_device_scenes(s);
+  // the tables of the read-back: node base per instance from the plan, BLAS ranges from the bases (a BLAS ends where the next one starts)
+  s->instNodeBase.assign(s->inst.size(), 0u);
+  for(uint32_t i = 0; i < uint32_t(s->inst.size()); ++i)
+  {
+    if(plan.isMerged[i])
+      s->mergedList.push_back(i);
+    else if(s->inst[i].triCount)
+    {
+      s->instNodeBase[i] = uint32_t(plan.nodeBaseOf[s->inst[i].primMesh]);
+      ++s->numActive;
+    }
+  }
+  std::vector<uint32_t> bases;
+  for(int64_t b : plan.nodeBaseOf)
+    if(b >= 0)
+      bases.push_back(uint32_t(b));
+  std::sort(bases.begin(), bases.end());
+  for(size_t k = 0; k < bases.size(); ++k)
+  {
+    s->blasRanges.push_back(bases[k]);
+    s->blasRanges.push_back((k + 1 < bases.size() ? bases[k + 1] : uint32_t(s->blasWide.size())) - bases[k]);
+  }
+  if(plan.haveMerged)
+  {
+    for(uint32_t i : s->mergedList)
+      s->mergedTris += s->inst[i].triCount;
+    s->mergedWide = bases.empty() ? uint32_t(s->blasWide.size()) : bases[0];
+    for(int a = 0; a < 3; ++a)
+    {
+      s->mergedBox[a]     = plan.mlo[a];
+      s->mergedBox[3 + a] = plan.mhi[a];
+    }
+  }
   if(s->options & TH_COMPACT_NODES)
     encode_compact_nodes(s);
 }

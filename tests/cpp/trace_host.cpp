@@ -8,6 +8,7 @@
 // pt_scene_records.cpp's two_level_pad) must report exactly the candidates brute force reports -- every candidate along the ray, in key order.
 // The structures are assembled by th_scene.h; the walk context, the parallel loop and the machine leg are th_walk.h's.
 #include "th_walk.h"
+#include "pt_accel_dump.h"
 
 extern "C" int pt_debug_two_level_pad(const float* worldMatrix16, float Bo, float* out27);
 extern "C" int pt_debug_mat_lines(const pt_SceneDesc* d, void* linesOut, char* err, size_t errLen);
@@ -170,6 +171,60 @@ void th_world_tri(void* p, uint32_t w, float* out9, uint32_t* flags)
   const float   v[9] = {r.p0w.x, r.p0w.y, r.p0w.z, r.e1n.x, r.e1n.y, r.e1n.z, r.e2p.x, r.e2p.y, r.e2p.z};
   std::memcpy(out9, v, sizeof(v));
   *flags = __float_as_uint(r.p0w.w) >> 29;
+}
+
+// The harness's structures through the read-back interface of the product (pt_accel_dump.h; pt_debug_accel_info / pt_debug_accel_read): two = 0 the flat
+// structure, 1 the two-level one.  The harness keeps no binary nodes in node form, no list of active instances, no pad table and no shading lines:
+// those arrays hold 0 bytes.
+int th_accel_info(void* p, int two, uint32_t* out, int words)
+{
+  const Scene* s = static_cast<const Scene*>(p);
+  if(!out || words < 0)
+    return -1;
+  uint32_t v[PT_DUMPI_WORDS] = {};
+  v[PT_DUMPI_ACCEL_MODE] = two ? 1u : 0u; v[PT_DUMPI_NUM_TRIS] = uint32_t(s->world.size()); v[PT_DUMPI_NUM_INSTANCES] = uint32_t(s->inst.size());
+  v[PT_DUMPI_NUM_WIDE_NODES] = uint32_t(two ? s->blasWide.size() : s->flat.wide.size());
+  v[PT_DUMPI_HAVE_CNODES] = th_compact_in_use(p, two) ? 1u : 0u;
+  v[PT_DUMPI_BUILDER] = 3u;  // the device binned SAH, through its emulation
+  if(two)
+  {
+    v[PT_DUMPI_NODE_CAPACITY] = uint32_t(s->blasWide.size()); v[PT_DUMPI_NUM_TLAS_NODES] = uint32_t(s->tlas.wide.size()); v[PT_DUMPI_NUM_ACTIVE] = s->numActive;
+    v[PT_DUMPI_NUM_BLAS] = uint32_t(s->blasRanges.size() / 2) + (s->mergedTris ? 1u : 0u); v[PT_DUMPI_MERGED_TRIS] = s->mergedTris; v[PT_DUMPI_MERGED_WIDE] = s->mergedWide;
+    v[PT_DUMPI_MERGED_ONLY] = s->mergedTris && s->numActive == 0 ? 1u : 0u;
+    std::memcpy(&v[PT_DUMPI_MERGED_BOX], s->mergedBox, sizeof(s->mergedBox));
+  }
+  std::copy(v, v + std::min(words, int(PT_DUMPI_WORDS)), out);
+  return PT_DUMPI_WORDS;
+}
+long long th_accel_read(void* p, int two, int which, void* dst, size_t bytes)
+{
+  const Scene* s    = static_cast<const Scene*>(p);
+  const void*  src  = nullptr;
+  size_t       have = 0;
+  auto take = [&](const auto& vec, size_t count) { src = vec.data(); have = sizeof(vec[0]) * count; };
+  const bool cn = th_compact_in_use(p, two) != 0;
+  switch(which)
+  {
+    case PT_DUMP_WIDE: two ? take(s->blasWide, s->blasWide.size()) : take(s->flat.wide, s->flat.wide.size()); break;
+    case PT_DUMP_CNODES: if(cn) { two ? take(s->blasCNodes, s->blasCNodes.size()) : take(s->flatCNodes, s->flatCNodes.size()); } break;
+    case PT_DUMP_TRIS: two ? take(s->blasTris, s->blasTris.size()) : take(s->flat.tris, s->flat.tris.size()); break;
+    case PT_DUMP_ALPHA_RECS: two ? take(s->blasAlpha, s->blasTris.size()) : take(s->flatAlpha, s->flat.tris.size()); break;
+    case PT_DUMP_TLAS: if(two) take(s->tlas.wide, s->tlas.wide.size()); break;
+    case PT_DUMP_CTLAS: if(two && cn) take(s->tlasCNodes, s->tlasCNodes.size()); break;
+    case PT_DUMP_TLAS_LEAVES: if(two) take(s->tlasLeaves, s->tlas.tris.size()); break;
+    case PT_DUMP_INST_TRI_BASE: if(two) take(s->instTriBase, s->inst.size()); break;
+    case PT_DUMP_INST_BLOCK: if(two) take(s->instBlock, s->instBlock.size()); break;
+    case PT_DUMP_INST_NODE_BASE: if(two) take(s->instNodeBase, s->instNodeBase.size()); break;
+    case PT_DUMP_BLAS_RANGES: if(two) take(s->blasRanges, s->blasRanges.size()); break;
+    case PT_DUMP_MERGED_LIST: if(two) take(s->mergedList, s->mergedList.size()); break;
+    default: break;  // BVH2, INST_PAD, ACTIVE, SHADE_TRIS: the harness has none
+  }
+  if(have == 0)
+    return 0;
+  if(!dst || bytes < have)
+    return -1;
+  std::memcpy(dst, src, have);
+  return (long long)have;
 }
 
 // Every candidate of every ray in key order (t, world index), at most maxCand per ray: mode 0 brute force over all world triangles with the

@@ -99,6 +99,8 @@ SIGNATURES = [
     ("th_candidates", _U, [_P, _I, _U, _P, _P, C.c_float, _U, _P, _P]),
     ("th_settle", _U, [_P, _I, _I, _I, _I, _U] + [_P] * 8),
     ("th_take_sp_hist", None, [_P]),
+    ("th_accel_info", _I, [_P, _I, _P, _I]),                            # csrc/pt_accel_dump.h: (scene, two, out[words], words)
+    ("th_accel_read", C.c_longlong, [_P, _I, _I, _P, C.c_size_t]),      # (scene, two, array id, dst, bytes) -> bytes the array holds
     # tests/cpp/render_host.cpp
     ("th_set_env", _I, [_P, _P, _I, _I, _P]),
     ("th_set_camera", None, [_P, _P, _P]),

@@ -101,6 +101,8 @@ DEBUG_API = [
     ("pt_debug_denoise_lds", C.c_int, [_P, C.c_int]),  # csrc/pt_denoise.hip: (ctx, largest step staged in LDS; negative: the default) -> the value in force
     ("pt_debug_denoise_time", C.c_int, [_P, C.POINTER(hd.DenoiseParams), C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_denoise.hip: (ctx, params, reps, ms per run out): the filter alone, device events
     ("pt_debug_bounce_counts", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[max_bounces][16], max_bounces) -> staged bounces of the newest finished launch sequence
+    ("pt_debug_accel_info", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[words], words) -> words of the info record (csrc/pt_accel_dump.h)
+    ("pt_debug_accel_read", C.c_longlong, [_P, C.c_int, _P, C.c_size_t]),  # csrc/pt_debug.hip: (ctx, array id, dst, bytes) -> bytes the array holds; 0: no such array
 ]
 
 _lib = None

@@ -1855,7 +1855,7 @@ int pt_merged_build(hipStream_t stream, const PtTuning& tune, const InstanceRec*
 
 int pt_tlas_build(hipStream_t stream, const PtTuning& tune, const InstanceRec* dInst, const uint32_t* dActive, uint32_t numActive, const uint32_t* dInstNodeBase, const float* dInstPad,
                   const float4* dVertices, const uint32_t* dIndices, WideNode* dTlasOut, TlasLeaf* dLeavesOut, BvhNode* rootOut, uint32_t* numWideOut, char* err, size_t errLen,
-                  const float* mergedBox, uint32_t mergedNodeBase)
+                  const float* mergedBox, uint32_t mergedNodeBase, bool mergedOpaque)
 {
   *numWideOut = 0;
   const uint32_t n = numActive + (mergedBox ? 1u : 0u);  // the merged structure is one more primitive of the TLAS
@@ -1873,7 +1873,7 @@ int pt_tlas_build(hipStream_t stream, const PtTuning& tune, const InstanceRec* d
   if(mergedBox)
   {
     TriRec r;
-    const uint32_t tag = TRI_INDEX_MASK;  // k_tlas_leaves recognises the proxy by this index
+    const uint32_t tag = TRI_INDEX_MASK | (mergedOpaque ? TRI_OPAQUE << 29 : 0u);  // k_tlas_leaves recognises the proxy by this index; the flag decides the BVH_ALPHA tag
     float          tagF;
     std::memcpy(&tagF, &tag, 4);
     r.p0w = make_float4(mergedBox[0], mergedBox[1], mergedBox[2], tagF);

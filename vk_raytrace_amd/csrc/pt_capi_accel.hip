@@ -120,6 +120,9 @@ int build_tlas(pt_context* c)
   }
   if((rc = upload(c, c->dInstPad, pad.data(), 4 * pad.size())) != PT_OK) return rc;
   if((rc = upload(c, c->dInstNodeBase, c->hInstNodeBase.empty() ? &none : c->hInstNodeBase.data(), 4 * std::max<size_t>(1, c->hInstNodeBase.size()))) != PT_OK) return rc;
+  bool mergedOpaque = true;  // the reference to the merged structure's leaf is tagged BVH_ALPHA only when one of its triangles can draw
+  for(uint32_t i : c->hMerged)
+    mergedOpaque = mergedOpaque && (inst[i].flags & TRI_OPAQUE) != 0;
   const uint32_t numPrims = c->numActive + (c->mergedTris ? 1u : 0u);
   if((rc = dev_alloc(c, c->dTlas, sizeof(WideNode) * size_t(std::max(1u, numPrims)))) != PT_OK) return rc;
   if((rc = dev_alloc(c, c->dTlasLeaves, sizeof(TlasLeaf) * size_t(std::max(1u, numPrims)))) != PT_OK) return rc;
@@ -128,7 +131,7 @@ int build_tlas(pt_context* c)
   BvhNode root{};
   if(pt_tlas_build(c->stream, c->tune, (const InstanceRec*)c->dInstances.p, (const uint32_t*)c->dActive.p, c->numActive, (const uint32_t*)c->dInstNodeBase.p, (const float*)c->dInstPad.p,
                    (const float4*)c->dVertices.p, (const uint32_t*)c->dIndices.p, (WideNode*)c->dTlas.p, (TlasLeaf*)c->dTlasLeaves.p, &root, &c->numTlasNodes, msg, sizeof(msg),
-                   c->mergedTris ? c->mergedBox : nullptr, 0u) != 0)
+                   c->mergedTris ? c->mergedBox : nullptr, 0u, mergedOpaque) != 0)
     return c->fail(PT_ERR_HIP, "TLAS build: %s", msg);
   c->msBuildTlas = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   for(int k = 0; k < 3; ++k)

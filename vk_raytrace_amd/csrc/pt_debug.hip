@@ -3,6 +3,7 @@
 #include <algorithm>
 #include "pt_context.h"
 #include "pt_probe.h"
+#include "pt_accel_dump.h"
 
 extern "C" {
 
@@ -337,4 +338,94 @@ extern "C" __attribute__((visibility("default"))) int pt_debug_bounce_counts(pt_
   const int n = std::min(newest->countsDepths, PT_MAX_DEPTH);
   std::copy(newest->hCounts, newest->hCounts + size_t(CNT_STRIDE) * size_t(std::min(n, max_bounces)), out);
   return n;
+}
+// The acceleration structure as it was built, copied back for tests/accel_audit.py (ids and info layout: pt_accel_dump.h).  Copies of buffers the context
+// holds, no kernel.  pt_debug_accel_info fills at most `words` words of the info record and returns PT_DUMPI_WORDS.  Not part of the ABI.
+extern "C" __attribute__((visibility("default"))) int pt_debug_accel_info(pt_context* c, uint32_t* out, int words)
+{
+  CTX_CHECK(c);
+  if(!out || words < 0)
+    return c->fail(PT_ERR_INVALID, "pt_debug_accel_info: bad arguments");
+  if(!c->haveAccel)
+    return c->fail(PT_ERR_STATE, "pt_debug_accel_info before pt_build_accel");
+  uint32_t v[PT_DUMPI_WORDS] = {};
+  v[PT_DUMPI_ACCEL_MODE] = uint32_t(c->accelMode); v[PT_DUMPI_NUM_TRIS] = c->numTris; v[PT_DUMPI_NUM_INSTANCES] = c->numInstances;
+  v[PT_DUMPI_NUM_WIDE_NODES] = c->numWideNodes; v[PT_DUMPI_NODE_CAPACITY] = c->nodeCapacity; v[PT_DUMPI_NUM_BVH_NODES] = c->numBvhNodes;
+  v[PT_DUMPI_NUM_TLAS_NODES] = c->numTlasNodes; v[PT_DUMPI_NUM_ACTIVE] = c->numActive; v[PT_DUMPI_NUM_BLAS] = c->numBlas;
+  v[PT_DUMPI_MERGED_TRIS] = c->mergedTris; v[PT_DUMPI_MERGED_WIDE] = c->mergedWide; v[PT_DUMPI_MERGED_ONLY] = c->mergedOnly ? 1u : 0u;
+  v[PT_DUMPI_HAVE_CNODES] = c->haveCNodes ? 1u : 0u; v[PT_DUMPI_HAVE_SHADE_TRIS] = c->haveShadeTris ? 1u : 0u;
+  std::memcpy(&v[PT_DUMPI_MERGED_BOX], c->mergedBox, sizeof(c->mergedBox));
+  v[PT_DUMPI_BUILDER] = uint32_t(c->tune.sahBuild);
+  std::copy(v, v + std::min(words, int(PT_DUMPI_WORDS)), out);
+  return PT_DUMPI_WORDS;
+}
+// Array `which` of the structure -> dst.  Returns the number of bytes the array holds (0: no such array in the current mode); copies nothing and returns
+// PT_ERR_INVALID when `bytes` is smaller than that.
+extern "C" __attribute__((visibility("default"))) long long pt_debug_accel_read(pt_context* c, int which, void* dst, size_t bytes)
+{
+  CTX_CHECK(c);
+  if(which < 0 || which >= PT_DUMP_COUNT)
+    return c->fail(PT_ERR_INVALID, "pt_debug_accel_read: no array %d", which);
+  if(!c->haveAccel)
+    return c->fail(PT_ERR_STATE, "pt_debug_accel_read before pt_build_accel");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_all(c));
+  const bool two = c->accelMode == PT_ACCEL_TWO_LEVEL;
+  size_t     slots = c->numTris;  // leaf records: every world triangle, or the merged structure's + one set per prim-mesh with an object-space BLAS
+  if(two)
+  {
+    std::vector<char> merged(c->hInstances.size(), 0), seen;
+    for(uint32_t i : c->hMerged)
+      merged[i] = 1;
+    slots = c->mergedTris;
+    for(size_t i = 0; i < c->hInstances.size(); ++i)
+    {
+      const InstanceRec& I = c->hInstances[i];
+      if(I.triCount == 0 || merged[i] || I.primMesh < 0)
+        continue;
+      if(seen.size() <= size_t(I.primMesh))
+        seen.resize(size_t(I.primMesh) + 1, 0);
+      if(!seen[I.primMesh])
+        slots += I.triCount;
+      seen[I.primMesh] = 1;
+    }
+  }
+  const size_t   nodes = two ? c->nodeCapacity : c->numWideNodes;
+  const size_t   cnodes = !c->haveCNodes ? 0 : (two && c->mergedOnly) ? c->mergedWide : nodes;
+  const void*    src  = nullptr;
+  bool           host = false;
+  size_t         have = 0;
+  const DevBuf*  buf  = nullptr;
+  switch(which)
+  {
+    case PT_DUMP_WIDE: buf = &c->dWide; have = sizeof(WideNode) * nodes; break;
+    case PT_DUMP_CNODES: buf = &c->dCNodes; have = sizeof(CompactNode) * cnodes; break;
+    case PT_DUMP_TRIS: buf = &c->dTris; have = sizeof(TriRec) * slots; break;
+    case PT_DUMP_ALPHA_RECS: buf = &c->dAlphaRecs; have = sizeof(AlphaRec) * slots; break;
+    case PT_DUMP_BVH2: buf = &c->dBvh; have = two ? 0 : sizeof(BvhNode) * size_t(c->numBvhNodes); break;
+    case PT_DUMP_TLAS: buf = &c->dTlas; have = two ? sizeof(WideNode) * size_t(c->numTlasNodes) : 0; break;
+    case PT_DUMP_CTLAS: buf = &c->dCTlas; have = two && c->haveCNodes && !c->mergedOnly ? sizeof(CompactNode) * size_t(c->numTlasNodes) : 0; break;
+    case PT_DUMP_TLAS_LEAVES: buf = &c->dTlasLeaves; have = two ? sizeof(TlasLeaf) * (size_t(c->numActive) + (c->mergedTris ? 1 : 0)) : 0; break;
+    case PT_DUMP_INST_TRI_BASE: buf = &c->dInstTriBase; have = two ? 4 * size_t(c->numInstances) : 0; break;
+    case PT_DUMP_INST_BLOCK: buf = &c->dInstBlock; have = two ? 4 * ((size_t(c->numTris) >> PT_INST_BLOCK_SHIFT) + 2) : 0; break;
+    case PT_DUMP_INST_PAD: buf = &c->dInstPad; have = two ? 8 * size_t(c->numInstances) : 0; break;
+    case PT_DUMP_ACTIVE: buf = &c->dActive; have = two ? 4 * size_t(c->numActive) : 0; break;
+    case PT_DUMP_SHADE_TRIS: buf = &c->dShadeTris; have = c->haveShadeTris ? sizeof(float4) * PT_SHADE_REC_QUADS * size_t(two ? c->mergedTris : c->numTris) : 0; break;
+    case PT_DUMP_INST_NODE_BASE: host = true; src = c->hInstNodeBase.data(); have = two ? 4 * c->hInstNodeBase.size() : 0; break;
+    case PT_DUMP_BLAS_RANGES: host = true; src = c->hBlasRanges.data(); have = two ? 4 * c->hBlasRanges.size() : 0; break;
+    default: host = true; src = c->hMerged.data(); have = two ? 4 * c->hMerged.size() : 0; break;  // PT_DUMP_MERGED_LIST
+  }
+  if(have == 0)
+    return 0;
+  if(!dst || bytes < have)
+    return c->fail(PT_ERR_INVALID, "pt_debug_accel_read: array %d holds %zu bytes, the buffer %zu", which, have, bytes);
+  if(host)
+    std::memcpy(dst, src, have);
+  else
+  {
+    if(!buf->p || buf->bytes < have)
+      return c->fail(PT_ERR_STATE, "pt_debug_accel_read: array %d is not allocated", which);
+    HIP_TRY(c, hipMemcpy(dst, buf->p, have, hipMemcpyDeviceToHost));
+  }
+  return (long long)have;
 }

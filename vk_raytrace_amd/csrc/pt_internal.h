@@ -169,10 +169,11 @@ int pt_merged_build(hipStream_t stream, const PtTuning& tune, const InstanceRec*
                     size_t errLen);
 // ... and one TLAS over the world boxes of the `numActive` non-empty instances listed in dActive (exact bounds of the T1 world triangles).
 // dInstNodeBase[inst]: root node of the instance's BLAS; dInstPad[2 * inst + {0,1}]: TlasLeaf::padC0 / padC1.  rootOut: the binary root (world bounds).
-// mergedBox (may be null): the merged structure's box, one more TLAS primitive whose leaf points at mergedNodeBase.
+// mergedBox (may be null): the merged structure's box, one more TLAS primitive whose leaf points at mergedNodeBase; mergedOpaque: no triangle of that
+// structure lacks TRI_OPAQUE, so the reference to its leaf carries no BVH_ALPHA tag (like the reference to an opaque instance).
 int pt_tlas_build(hipStream_t stream, const PtTuning& tune, const InstanceRec* dInst, const uint32_t* dActive, uint32_t numActive, const uint32_t* dInstNodeBase, const float* dInstPad,
                   const float4* dVertices, const uint32_t* dIndices, WideNode* dTlasOut, TlasLeaf* dLeavesOut, BvhNode* rootOut, uint32_t* numWideOut, char* err, size_t errLen,
-                  const float* mergedBox = nullptr, uint32_t mergedNodeBase = 0);
+                  const float* mergedBox = nullptr, uint32_t mergedNodeBase = 0, bool mergedOpaque = false);
 // WideNode -> CompactNode for the first n nodes; -1 when a node cannot be represented (the caller keeps the WideNode walk).  reachOut: max |p| + 2047 step over the nodes
 int pt_compact_nodes(hipStream_t stream, uint32_t n, const WideNode* in, CompactNode* out, float* reachOut = nullptr);
 // ... over numRanges node ranges given as (base, count) pairs
