@@ -14,7 +14,7 @@
  *    pt_get_stats and pt_synchronize wait for it.
  *  - Traversal-stack overflow: a ray whose walk needs more than 64 stack entries drops a subtree, so the image misses geometry.  Once
  *    such an overflow has been counted, every call that hands out results returns PT_ERR_STATE ("BVH traversal stack overflowed ...")
- *    instead of PT_OK: pt_synchronize, pt_read_accum, pt_tonemap, pt_tonemap_zoom, pt_tonemap_end, pt_denoise, pt_tonemap_denoised, pt_pick,
+ *    instead of PT_OK: pt_synchronize, pt_read_accum, pt_tonemap, pt_tonemap_zoom, pt_tonemap_end, pt_denoise, pt_tonemap_denoised, pt_read_denoise_guides, pt_pick,
  *    pt_trace_rays, pt_local_shard, pt_gather_shards and pt_get_stats, and pt_tonemap_begin once the overflow is known (it then enqueues nothing).  The state stays
  *    until pt_reset_stats or the next pt_build_accel (a new scene) clears it; images begun before the clear no longer report it.
  *  - there is no CPU fallback: without a gfx950 device pt_create fails with PT_ERR_NO_DEVICE.
@@ -182,7 +182,8 @@ int pt_tonemap_pending(pt_context* ctx);
  * An edge-avoiding a-trous filter (Dammertz et al. 2010) as a stage of its own between the accumulation image and the display pass; DESIGN.md
  * "Denoiser" has the definition, csrc/pt_denoise.h the one fp32 operation sequence host and device share.  The stage reads the row-major image
  * pt_read_accum returns and guide planes the CALLER supplies -- typically frame-0 debug frames (base colour, normal) and pt_trace_rays depths, all
- * obtained through entry points that exist already; no render kernel captures anything for it. */
+ * obtained through entry points that exist already -- or that pt_render_guides renders on the device in a pass of its own; no render kernel
+ * captures anything for it. */
 
 /* No reference counterpart.  Installs the guide planes: planes[j] is NULL (plane j unset) or a row-major image of width * height * 4 floats whose
  * .xyz are read; copied before the call returns.  Guides must be finite (the filter's result is unspecified otherwise; its reads stay in bounds).
@@ -202,6 +203,28 @@ int pt_denoise(pt_context* ctx, const pt_DenoiseParams* params, float* rgba32f_o
  * of pt_tonemap on a context whose accumulation image was replaced by pt_denoise's output with pt_write_accum.  Synchronous; errors as pt_denoise
  * and pt_tonemap.  (Not provided: the pt_tonemap_begin / pt_tonemap_end form and pt_tonemap_zoom of a denoised image.) */
 int pt_tonemap_denoised(pt_context* ctx, const pt_DenoiseParams* params, const pt_Tonemapper* tm, uint8_t* rgba8_out);
+
+/* No reference counterpart.  The guide pass (DESIGN.md "Guide pass", csrc/pt_guides.h): renders the selected guide planes for the current camera at
+ * the pt_resize size, on the device, straight into the context's guide planes -- one first-hit pass of a kernel of its own, no render kernel and no
+ * host round trip.  Per pixel: the camera ray of the first sample of frame 0 (seed tea(W * y + x, 0), jitter (0.5, 0.5), the two depth-of-field
+ * draws), its closest hit under the trace contract (T5: culling, stochastic alpha from the running seed), and there plane 0 = (base colour, 1),
+ * plane 1 = ((normal + 1) / 2, 1) -- what a frame-0 debug frame (eBaseColor / eNormal, maxDepth >= 2) accumulates -- and plane 2 = (t, 0, 0, 0);
+ * a miss gives (0, 0, 0, 1), (0, 0, 0, 1) and (miss_depth, 0, 0, 0).  A selected plane replaces whatever the caller installed in it; a plane outside
+ * the mask stays as it is, installed or unset.  The whole image is rendered whatever pt_set_shard says (the scene is replicated, and the denoiser
+ * only runs on a gathered image).  Asynchronous on the context's stream like pt_render_frame: the next synchronising call reports a traversal-stack
+ * overflow of its walks.  The accumulation tiles, the path state, the frame slots and every pt_Stats field stay as they are: a frame sequence with
+ * calls in between continues bit for bit.  PT_ERR_STATE: before pt_set_scene / pt_build_accel, before pt_set_camera, before pt_resize.
+ * PT_ERR_INVALID, with nothing launched: planes == 0, unknown mask bits, miss_depth not finite (guides must be finite). */
+#define PT_GUIDES_BASECOLOR 1u /* plane 0 */
+#define PT_GUIDES_NORMAL 2u    /* plane 1 */
+#define PT_GUIDES_DEPTH 4u     /* plane 2 */
+int pt_render_guides(pt_context* ctx, uint32_t planes, float miss_depth);
+
+/* No reference counterpart.  Copies every installed guide plane j whose planes_out[j] is not NULL to it (width * height * 4 floats, row-major), whether
+ * pt_set_denoise_guides or pt_render_guides put it there.  Synchronous like pt_read_accum: waits for the work in flight and reports its
+ * traversal-stack overflow with PT_ERR_STATE.  PT_ERR_STATE: before pt_resize; a requested plane that is not installed (nothing is copied).
+ * planes_out == NULL: PT_ERR_INVALID. */
+int pt_read_denoise_guides(pt_context* ctx, float* const planes_out[PT_DENOISE_GUIDES]);
 
 /* Test access to the image the display pass samples: builds the offscreen image of a disp_width x disp_height viewport and its full mip chain exactly
  * as pt_tonemap_zoom does with auto-exposure on, and copies level `level` (RGBA32F, row-major) to rgba32f_out, its extent to *width / *height (each may

@@ -125,6 +125,13 @@ public:
     const float* const planes[PT_DENOISE_GUIDES] = {albedo, normal, depth};
     return check(pt_set_denoise_guides(m_ctx, planes));
   }
+  // ... or rendered on the device for the current camera (planes: PT_GUIDES_* mask; asynchronous), and read back (each pointer NULL or width * height * 4 floats)
+  bool renderGuides(uint32_t planes = PT_GUIDES_BASECOLOR | PT_GUIDES_NORMAL | PT_GUIDES_DEPTH, float missDepth = 1.0e30f) { return check(pt_render_guides(m_ctx, planes, missDepth)); }
+  bool readDenoiseGuides(float* albedo, float* normal, float* depth)
+  {
+    float* const planes[PT_DENOISE_GUIDES] = {albedo, normal, depth};
+    return check(pt_read_denoise_guides(m_ctx, planes));
+  }
   bool denoise(const pt_DenoiseParams& p, float* rgba32f) { return check(pt_denoise(m_ctx, &p, rgba32f)); }
   bool tonemapDenoised(const pt_DenoiseParams& p, const pt_Tonemapper& tm, uint8_t* rgba8) { return check(pt_tonemap_denoised(m_ctx, &p, &tm, rgba8)); }
 

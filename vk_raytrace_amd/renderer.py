@@ -249,7 +249,8 @@ class HipRenderer(Renderer):
         """Guide planes for the current camera, from entry points that exist for other purposes: one frame-0 debug frame each for base colour and
         normal, and the closest-hit distance of the pixel-centre camera rays (`t` in .x; `miss_depth` where nothing is hit).  Installs all three
         and returns them.  To be called right after a camera change, before frame 0 of the real accumulation: frame 0 overwrites the accumulation
-        image, so nothing needs saving.  `state`: the push constants of the frames to come (not modified); the camera is what set_camera was given."""
+        image, so nothing needs saving.  `state`: the push constants of the frames to come (not modified); the camera is what set_camera was given.
+        capture_guides renders the same planes on the device in one pass, without a frame and without a copy."""
         if self._camera is None:
             raise capi.PtError(capi.PT_ERR_STATE, "render_guides before set_camera")
         w, h = self.size
@@ -267,6 +268,22 @@ class HipRenderer(Renderer):
         planes.append(depth)
         self.set_denoise_guides(*planes)
         return tuple(planes)
+
+    def capture_guides(self, planes=7, miss_depth=1.0e30):
+        """pt_render_guides: the guide planes selected by `planes` (capi.PT_GUIDES_BASECOLOR | PT_GUIDES_NORMAL | PT_GUIDES_DEPTH) for the current
+        camera, rendered on the device into the context's guide planes by one first-hit pass.  Asynchronous like run(); a plane outside the mask
+        stays as it is.  The depth plane holds `miss_depth` where nothing is hit."""
+        self._check(self._lib.pt_render_guides(self._ctx, int(planes), float(miss_depth)))
+
+    def read_guides(self, planes=None):
+        """pt_read_denoise_guides: the installed guide planes as a tuple of three (H, W, 4) float32 images.  planes: mask of the planes to read
+        (None: all three); a plane outside it comes back as None, one inside it that is not installed is an error (PT_ERR_STATE)."""
+        w, h = self.size
+        mask = 7 if planes is None else int(planes)
+        out = [np.empty((h, w, 4), np.float32) if mask & (1 << j) else None for j in range(capi.PT_DENOISE_GUIDES)]
+        ptrs = (C.c_void_p * capi.PT_DENOISE_GUIDES)(*[None if p is None else p.ctypes.data for p in out])
+        self._check(self._lib.pt_read_denoise_guides(self._ctx, ptrs))
+        return tuple(out)
 
     def tonemap_begin(self, tm: hd.Tonemapper, display_size=None):
         """pt_tonemap_begin: the display pass enqueued behind the frames rendered so far; later frames overlap it.  tonemap_end() returns the
