@@ -167,6 +167,12 @@ class St:
         self.N, self.T, self.B, self.eta, self.thin = r[:, 22:25], r[:, 25:28], r[:, 28:31], r[:, 31], rows[:, 32] != 0
         self.V, self.L = r[:, 33:36], r[:, 36:39]
         self.seed = rows[:, 39].copy().view(np.uint32)
+        self.back = np.zeros(len(rows), bool)   # dot(ffnormal, normal) < 0; never in this state (ffnormal == normal).  gen_path_kat.py builds states where it happens.
+
+
+def state_of(rows, ft):
+    """the probe rows as a state; a state built elsewhere (gen_path_kat.py: from a hit, in ft throughout) passes through"""
+    return rows if isinstance(rows, St) else St(rows, ft)
 
 
 def schlick_fresnel(u):  # :114-119
@@ -329,9 +335,9 @@ def half_vector(s, V, N, L):  # :526-534 == pbr_gltf.glsl:367-375
 
 
 def disney_eval(rows, ft):  # :524-599
-    s = St(rows, ft)
+    s = state_of(rows, ft)
     V, N, L = s.V, s.N, s.L
-    z1, z3 = np.zeros(len(rows), ft), np.zeros((len(rows), 3), ft)
+    z1, z3 = np.zeros(len(s.V), ft), np.zeros((len(s.V), 3), ft)
     H = half_vector(s, V, N, L)
     dr, psr, tw = ft(0.5) * (ft(1) - s.metallic), ft(1) / (ft(1) + s.clearcoat), (ft(1) - s.metallic) * s.transmission
     back = dot(N, L) < 0
@@ -385,9 +391,9 @@ DISNEY_BRANCHES = ["reflection", "refraction", "subsurface", "diffuse", "specula
 
 
 def disney_sample(rows, ft):  # :414-520
-    s = St(rows, ft)
+    s = state_of(rows, ft)
     V, N = s.V, s.N
-    n = len(rows)
+    n = len(V)
     all_, z1 = np.ones(n, bool), np.zeros(n, ft)
     d = Draws(s.seed, ft)
     r1, r2 = d.rand(), d.rand()
@@ -399,7 +405,7 @@ def disney_sample(rows, ft):  # :414-520
         H = to_world(s, sample_gtr2(s.roughness, r1, r2))
         R = reflect(-V, H)
         F = dielectric_fresnel(np.abs(dot(R, H)), s.eta)
-        F = np.where(s.thin & (dot(s.N, s.N) < 0), ft(0), F)  # ffnormal == normal in this state
+        F = np.where(s.thin & s.back, ft(0), F)  # :442-446
         eta = np.where(s.thin, ft(1.001), s.eta)
         refl = d.less(F, trans)
         L0 = normalize(R)
@@ -513,9 +519,9 @@ def g_clearcoat(s, V, N, L, H):  # :289-314
 
 
 def gltf_eval(rows, ft):  # :365-434
-    s = St(rows, ft)
+    s = state_of(rows, ft)
     V, N, L = s.V, s.N, s.L
-    z1, z3 = np.zeros(len(rows), ft), np.zeros((len(rows), 3), ft)
+    z1, z3 = np.zeros(len(s.V), ft), np.zeros((len(s.V), 3), ft)
     with np.errstate(all="ignore"):
         H = half_vector(s, V, N, L)
         dr, psr, tw = ft(0.5) * (ft(1) - s.metallic), ft(1) / (ft(1) + s.clearcoat), (ft(1) - s.metallic) * s.transmission
@@ -537,9 +543,9 @@ GLTF_BRANCHES = ["transmission-reflect", "transmission-refract", "diffuse", "spe
 
 
 def gltf_sample(rows, ft):  # :439-554
-    s = St(rows, ft)
+    s = state_of(rows, ft)
     V, N = s.V, s.N
-    n = len(rows)
+    n = len(V)
     all_ = np.ones(n, bool)
     d = Draws(s.seed, ft)
     prob = d.rand()
@@ -553,7 +559,7 @@ def gltf_sample(rows, ft):  # :439-554
         vdh = dot(V, H)
         F = f_schlick(R0 * R0, ft(1), vdh)
         disc = ft(1) - s.eta * s.eta * (ft(1) - vdh * vdh)
-        inside = s.thin & (dot(s.N, s.N) < 0)  # ffnormal == normal in this state
+        inside = s.thin & s.back  # :466-474
         F, disc = np.where(inside, ft(0), F), np.where(inside, ft(0), disc)
         eta = np.where(s.thin, ft(1), s.eta)
         tir = trans & (disc < 0)  # `discriminat < 0.0 || rand(seed) < F`: no draw behind a true left operand

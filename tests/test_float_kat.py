@@ -21,7 +21,9 @@ and different for every mix-up of rows and columns).
 Oracle and reference only, because the product has no such FUNCTION (the entry answers -1 / PT_ERR_INVALID and the test asserts that):
   * vec4 * mat4: no call site in the product.
   * EnvSample's sun-disk direction (env_sampling.glsl:111-125): written inline in shade_path (pt_shade.h); reached through the sun & sky frames of
-    tests/test_trace_host.py / tests/test_gpu_parity.py, bit-identical to the oracle, which IS held to the model here.
+    tests/test_trace_host.py / tests/test_gpu_parity.py, bit-identical to the oracle, which IS held to the model here.  (The rest of DirectLight -- pSelect, the
+    light pick, the punctual lights, the environment NEE, lightPdf and the MIS weight -- has a per-pixel expectation of its own: tests/golden/gen_path_kat.py,
+    tests/test_path_model.py, tests/test_path_gpu.py.  Sun & sky stays out of that model too.)
   * step, clamp, sign, fract, mod, atan(y, x), roundEven: all in ref_glue/glsl_compat.h (what the reference's shaders run on), step and clamp in
     oracle/glsl_math.h.  The oracle and the product write the others inline where the shaders call them -- floor / fract in the texture and environment
     filters (orc_scene.h sample_texture / sample_env, pt_surface.h:51-115), sign / mod / atan inside sun_and_sky and GetSphericalUv (pt_atan2) -- so their

@@ -390,8 +390,9 @@ PT_DEV int shade_path(const DeviceScene& S, const RB& rb, const FrameParams& fp,
     else
       ret = false;
     if(ret)
-    {
-      rb.ps.rad[slot] = make_float4(r.x, r.y, r.z, 0.f);
+    {  // the bounce has drawn (DirectLight, the BSDF sample): the next sample of the frame continues from here (pathtrace.comp:97-105)
+      rb.ps.rad[slot]    = make_float4(r.x, r.y, r.z, 0.f);
+      rb.ps.rayD[slot].w = __uint_as_float(seed);
       return SHADE_DONE;
     }
   }
