@@ -226,6 +226,44 @@ int pt_render_guides(pt_context* ctx, uint32_t planes, float miss_depth);
  * planes_out == NULL: PT_ERR_INVALID. */
 int pt_read_denoise_guides(pt_context* ctx, float* const planes_out[PT_DENOISE_GUIDES]);
 
+/* ---- temporal reprojection (no reference counterpart: the reference restarts its accumulation on every camera change) ------------------------
+ * The temporal half of SVGF as a stage of its own, the companion of the denoiser above: last call's result -- the *history* the context keeps -- is
+ * reprojected into the current camera through the depth guide, tested tap by tap against depth and normal, and blended with the accumulation
+ * image.  DESIGN.md section 5.3 has the definition, csrc/pt_temporal.h the one fp32 operation sequence host and device share.  Typical use after a
+ * camera move: pt_set_camera, pt_render_guides, pt_render_frame (frame 0), pt_temporal_accumulate, pt_tonemap_history.  No render kernel captures
+ * anything for it. */
+
+/* No reference counterpart.  One step of the stage: reads the image pt_read_accum would return, guide planes 1 (normal) and 2 (depth) and the camera
+ * of pt_set_camera; writes only the history, which becomes the blended image (colour, normal and depth, length), made with params->worldToClip.
+ * rgba32f_out (may be NULL): the new history colour, width * height * 4 floats, alpha the accumulation image's.  The first call, and the first after
+ * pt_temporal_reset or a pt_resize to another size, has no history: it stores the current image.  Synchronous like pt_denoise: waits for the frames
+ * in flight and reports their traversal-stack overflow with PT_ERR_STATE.  The accumulation tiles, the path state, the frame slots, the guide planes
+ * and every pt_Stats field stay as they are.  Depths (miss_depth included) must stay below about 1e18: beyond it the squared distance overflows and
+ * the pixel simply has no history.  PT_ERR_STATE: before pt_resize; before pt_set_camera; without guide planes 1 and 2 installed (pt_render_guides or
+ * pt_set_denoise_guides); nranks > 1 without a gathered image.  PT_ERR_INVALID, with nothing launched and the history untouched: null parameters, a
+ * worldToClip entry that is not finite, depthTol not positive and finite, normalDist2 negative or not finite, maxHistory below 1 or not finite, any
+ * flag bit. */
+int pt_temporal_accumulate(pt_context* ctx, const pt_TemporalParams* params, float* rgba32f_out);
+
+/* No reference counterpart.  Drops the history (a scene change, a cut): the next pt_temporal_accumulate behaves as a first call.  No error besides a
+ * null context. */
+int pt_temporal_reset(pt_context* ctx);
+
+/* No reference counterpart.  Copies the history's colour image (width * height * 4 floats) and its length plane (width * height floats) out; either
+ * pointer may be NULL.  Synchronous.  PT_ERR_STATE: there is no history. */
+int pt_read_temporal_history(pt_context* ctx, float* rgba32f_out, float* length_out);
+
+/* No reference counterpart.  pt_denoise with the history's colour image in place of the accumulation image: the same filter, the current guide planes,
+ * the same parameter checks.  Read-only with respect to the history.  PT_ERR_STATE: before pt_resize; there is no history; PT_DENOISE_DEMODULATE
+ * without guide plane 0.  PT_ERR_INVALID as pt_denoise. */
+int pt_denoise_history(pt_context* ctx, const pt_DenoiseParams* params, float* rgba32f_out);
+
+/* No reference counterpart.  pt_tonemap_denoised with the history's colour image in place of the accumulation image; params == NULL: no spatial
+ * filter, and the bytes are those of pt_tonemap on a context whose accumulation image was replaced by the history with pt_write_accum.  Read-only
+ * with respect to the history.  Errors as pt_denoise_history (params != NULL) and pt_tonemap; tm or rgba8_out NULL: PT_ERR_INVALID.  (Not provided:
+ * pt_tonemap_zoom of the history and a begin / end form.) */
+int pt_tonemap_history(pt_context* ctx, const pt_DenoiseParams* params, const pt_Tonemapper* tm, uint8_t* rgba8_out);
+
 /* Test access to the image the display pass samples: builds the offscreen image of a disp_width x disp_height viewport and its full mip chain exactly
  * as pt_tonemap_zoom does with auto-exposure on, and copies level `level` (RGBA32F, row-major) to rgba32f_out, its extent to *width / *height (each may
  * be NULL).  Returns the number of levels (>= 1), or a negative pt_Result. */
@@ -291,6 +329,11 @@ int pt_pack_vertices(uint32_t n, const float* positions, const float* normals, c
 /* src/scene.cpp:629-640 with glm::lookAt / perspectiveRH_ZO(fov, aspect, 0.001, 1e5), proj[1][1] *= -1 */
 int pt_camera_lookat(const float eye[3], const float center[3], const float up[3], float fov_degrees,
                      float aspect, pt_SceneCamera* out);
+
+/* No reference counterpart (the reference never needs the forward matrix).  out16 = proj * view, column-major, world -> clip, from the same
+ * double-precision view and proj whose inverses pt_camera_lookat returns: what pt_TemporalParams::worldToClip takes for a camera set up with
+ * pt_camera_lookat (callers with matrices of their own pass their own product).  PT_ERR_INVALID: null pointers, aspect <= 0, eye == center. */
+int pt_camera_world_to_clip(const float eye[3], const float center[3], const float up[3], float fov_degrees, float aspect, float out16[16]);
 
 /* src/hdr_sampling.cpp:107-248 on the host; pt_set_env calls this internally. */
 int pt_build_env_accel(const float* rgba32f, int width, int height, pt_EnvAccel* out_accel, float* out_integral,

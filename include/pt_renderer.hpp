@@ -125,7 +125,8 @@ public:
     const float* const planes[PT_DENOISE_GUIDES] = {albedo, normal, depth};
     return check(pt_set_denoise_guides(m_ctx, planes));
   }
-  // ... or rendered on the device for the current camera (planes: PT_GUIDES_* mask; asynchronous), and read back (each pointer NULL or width * height * 4 floats)
+  // ... or rendered on the device for the current camera (planes: PT_GUIDES_* mask; asynchronous), and read back (each pointer NULL or width * height * 4 floats).
+  // (The default missDepth = 1e30 is beyond the temporal stage's domain of about 1e18: misses then carry no history; see temporalAccumulate.)
   bool renderGuides(uint32_t planes = PT_GUIDES_BASECOLOR | PT_GUIDES_NORMAL | PT_GUIDES_DEPTH, float missDepth = 1.0e30f) { return check(pt_render_guides(m_ctx, planes, missDepth)); }
   bool readDenoiseGuides(float* albedo, float* normal, float* depth)
   {
@@ -134,6 +135,15 @@ public:
   }
   bool denoise(const pt_DenoiseParams& p, float* rgba32f) { return check(pt_denoise(m_ctx, &p, rgba32f)); }
   bool tonemapDenoised(const pt_DenoiseParams& p, const pt_Tonemapper& tm, uint8_t* rgba8) { return check(pt_tonemap_denoised(m_ctx, &p, &tm, rgba8)); }
+  // temporal reprojection (no reference counterpart): the history across camera moves.  worldToClip in `p` is the CURRENT camera's forward matrix
+  // (pt_camera_world_to_clip).  With renderGuides' default missDepth = 1e30 a miss has no history: its squared distance overflows (pt_api.h); pass a
+  // miss depth below about 1e18 to carry the sky along under rotation.
+  bool temporalAccumulate(const pt_TemporalParams& p, float* rgba32f = nullptr) { return check(pt_temporal_accumulate(m_ctx, &p, rgba32f)); }
+  bool temporalReset() { return check(pt_temporal_reset(m_ctx)); }
+  bool readTemporalHistory(float* rgba32f, float* length) { return check(pt_read_temporal_history(m_ctx, rgba32f, length)); }
+  bool denoiseHistory(const pt_DenoiseParams& p, float* rgba32f) { return check(pt_denoise_history(m_ctx, &p, rgba32f)); }
+  // dp == nullptr: no spatial filter
+  bool tonemapHistory(const pt_DenoiseParams* dp, const pt_Tonemapper& tm, uint8_t* rgba8) { return check(pt_tonemap_history(m_ctx, dp, &tm, rgba8)); }
 
   bool               ok() const { return m_status == PT_OK; }
   int                status() const { return m_status; }

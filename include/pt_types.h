@@ -267,6 +267,17 @@ typedef struct pt_DenoiseParams {
   uint32_t flags;                         /* PT_DENOISE_DEMODULATE */
 } pt_DenoiseParams;
 
+/* pt_temporal_accumulate: the temporal reprojection stage (no reference counterpart; defined in DESIGN.md section 5.3 and stated once in
+ * csrc/pt_temporal.h).  pt_SceneCamera carries only inverses, so the caller supplies the forward matrix of the CURRENT camera (column-major, world ->
+ * clip: proj * view; pt_camera_world_to_clip builds the one that belongs to pt_camera_lookat); the library keeps it with the history it writes. */
+typedef struct pt_TemporalParams {
+  float    worldToClip[16]; /* of the current camera; every entry finite */
+  float    depthTol;        /* a history tap counts when |its depth - the expected depth| <= depthTol * the expected depth; > 0, finite */
+  float    normalDist2;     /* ... and when the squared distance of the encoded normals is at most this ((1 - cos) / 2 for unit normals); >= 0, finite */
+  float    maxHistory;      /* cap of the history length: the blend factor never falls below 1 / maxHistory; >= 1, finite */
+  uint32_t flags;           /* none defined: must be 0 */
+} pt_TemporalParams;
+
 /* Counters the measurement contract needs; all totals since pt_reset_stats. */
 typedef struct pt_Stats {
   uint64_t samples;          /* pixel-samples rendered */
@@ -330,6 +341,7 @@ static_assert(sizeof(pt_PrimMesh) == 20, "PrimMesh");
 static_assert(sizeof(pt_Node) == 68, "Node");
 static_assert(sizeof(pt_Ray) == 32 && sizeof(pt_RayHit) == 32, "Ray / RayHit");
 static_assert(sizeof(pt_DenoiseParams) == 24, "DenoiseParams");
+static_assert(sizeof(pt_TemporalParams) == 80, "TemporalParams");
 #endif
 
 #endif /* PT_TYPES_H */

@@ -62,6 +62,11 @@ API = [
     ("pt_tonemap_denoised", C.c_int, [_P, C.POINTER(hd.DenoiseParams), C.POINTER(hd.Tonemapper), _P]),
     ("pt_render_guides", C.c_int, [_P, C.c_uint32, C.c_float]),
     ("pt_read_denoise_guides", C.c_int, [_P, C.POINTER(_P)]),
+    ("pt_temporal_accumulate", C.c_int, [_P, C.POINTER(hd.TemporalParams), _P]),
+    ("pt_temporal_reset", C.c_int, [_P]),
+    ("pt_read_temporal_history", C.c_int, [_P, _P, _P]),
+    ("pt_denoise_history", C.c_int, [_P, C.POINTER(hd.DenoiseParams), _P]),
+    ("pt_tonemap_history", C.c_int, [_P, C.POINTER(hd.DenoiseParams), C.POINTER(hd.Tonemapper), _P]),
     ("pt_debug_display_level", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_local_shard", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_scatter_shards", C.c_int, [_P, _P, C.c_int]),
@@ -86,6 +91,7 @@ API = [
     ("pt_compress_unit_vec", C.c_uint32, [_P]),
     ("pt_pack_vertices", C.c_int, [C.c_uint32, _P, _P, _P, _P, _P, _P]),
     ("pt_camera_lookat", C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.POINTER(hd.SceneCamera)]),
+    ("pt_camera_world_to_clip", C.c_int, [_P, _P, _P, C.c_float, C.c_float, _P]),
     ("pt_build_env_accel", C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("pt_sampler_from_gltf", C.c_int, [C.c_int] * 5 + [C.POINTER(hd.TextureDesc)]),
     ("pt_gltf_load", C.c_int, [C.c_char_p, C.POINTER(_P), C.c_char_p, C.c_size_t]),
@@ -104,6 +110,7 @@ DEBUG_API = [
     ("pt_debug_denoise_lds", C.c_int, [_P, C.c_int]),  # csrc/pt_denoise.hip: (ctx, largest step staged in LDS; negative: the default) -> the value in force
     ("pt_debug_denoise_time", C.c_int, [_P, C.POINTER(hd.DenoiseParams), C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_denoise.hip: (ctx, params, reps, ms per run out): the filter alone, device events
     ("pt_debug_guides_time", C.c_int, [_P, C.c_uint32, C.c_float, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_guides.hip: (ctx, planes, miss_depth, reps, ms per run out): the guide pass alone, device events
+    ("pt_debug_temporal_time", C.c_int, [_P, C.POINTER(hd.TemporalParams), C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_temporal.hip: (ctx, params, reps, ms per run out): the temporal kernel alone, device events
     ("pt_debug_bounce_counts", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[max_bounces][16], max_bounces) -> staged bounces of the newest finished launch sequence
     ("pt_debug_accel_info", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[words], words) -> words of the info record (csrc/pt_accel_dump.h)
     ("pt_debug_accel_read", C.c_longlong, [_P, C.c_int, _P, C.c_size_t]),  # csrc/pt_debug.hip: (ctx, array id, dst, bytes) -> bytes the array holds; 0: no such array
@@ -164,6 +171,16 @@ def camera_lookat(cam, aspect, nb_lights=0):
     if cam.focal_dist is not None:
         out.focalDist = cam.focal_dist
     out.nbLights = nb_lights
+    return out
+
+
+def camera_world_to_clip(cam, aspect):
+    """pt_camera_world_to_clip: proj * view (column-major, 16 float32) of the scene.Camera whose inverses camera_lookat returns"""
+    out = np.zeros(16, np.float32)
+    e, c, u = (np.asarray(v, np.float32) for v in (cam.eye, cam.center, cam.up))
+    rc = lib().pt_camera_world_to_clip(e.ctypes.data, c.ctypes.data, u.ctypes.data, cam.fov, aspect, out.ctypes.data)
+    if rc != PT_OK:
+        raise PtError(rc, "pt_camera_world_to_clip")
     return out
 
 

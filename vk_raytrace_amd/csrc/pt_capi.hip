@@ -334,6 +334,7 @@ int pt_destroy(pt_context* c)
   for(DevBuf* b : all)
     dev_free(*b);
   denoise_release(c);
+  temporal_release(c);
   for(auto& fs : c->slots)
   {
     fs.release_paths();
@@ -640,6 +641,7 @@ int pt_resize(pt_context* c, int width, int height)
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_all(c));
   denoise_release(c);  // the denoiser's buffers and the guide planes were sized for the old image
+  temporal_release(c);  // ... and so was the history
   c->tilesX = (width + PT_TILE - 1) / PT_TILE;
   c->tilesY = (height + PT_TILE - 1) / PT_TILE;
   std::vector<uint32_t> local;

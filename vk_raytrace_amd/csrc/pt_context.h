@@ -124,6 +124,12 @@ struct pt_context {
   // denoiser (pt_denoise.hip): the two ping-pong images, allocated on first use, and the caller's guide planes; pt_resize and pt_destroy free them
   DevBuf   dDenoise[2], dGuide[PT_DENOISE_GUIDES];
   int      denoiseLdsMaxStep = -1;  // largest step whose iteration stages its tile in LDS (-1: the measured default; pt_debug_denoise_lds)
+  // temporal stage (pt_temporal.hip): the history -- colour, packed guide (encoded normal, depth) and length, each twice (one set is read while the other
+  // is written) -- allocated on first use, and the camera it was made with; pt_resize and pt_destroy free it, pt_temporal_reset drops it
+  DevBuf   dHistColour[2], dHistGuide[2], dHistLength[2];
+  int      histSet     = 0;      // the set that holds the history (the next call reads it and writes the other)
+  bool     haveHistory = false;
+  float    histWorldToClip[16] = {0}, histEye[3] = {0, 0, 0};
   bool     haveFull = false;
   // pipelined display (pt_tonemap_begin / pt_tonemap_end): a ring of pinned host images, each with the event that says its copy has landed
   // and the event after which the accumulation image may be written again (the untile pass has read it)
@@ -176,6 +182,7 @@ int        display_chain(pt_context* c, int dispW, int dispH, bool chain, hipEve
 int        display_levels(pt_context* c, const float4* image, int dispW, int dispH, bool chain, MipView& mv);  // ... the part after level 0 (`image`, accumulation size) is chosen
 int        display_finish(pt_context* c, const pt_Tonemapper* tm, MipView& mv, int dispW, int dispH, uint8_t* out);  // ... the tonemap kernel and the copy to `out` (host), enqueued
 void       denoise_release(pt_context* c);  // pt_denoise.hip: frees the denoiser's images and drops the guide planes
+void       temporal_release(pt_context* c);  // pt_temporal.hip: frees the history
 void       refresh_scene_ptrs(pt_context* c);
 int        upload_instances(pt_context* c);
 std::vector<InstanceRec> effective_instances(const pt_context* c);  // the instance records as the kernels see them

@@ -118,7 +118,8 @@ void denoise_release(pt_context* c)
 }
 
 // Everything the entry points check, then the row-major accumulation image enqueued on the context's stream behind the frames rendered so far
-static int prepare_denoise(pt_context* c, const char* who, const pt_DenoiseParams* p, DenoiseConst& k)
+// (untile == false: the caller filters another image, the history of pt_temporal.hip, and the accumulation image is not asked for)
+static int prepare_denoise(pt_context* c, const char* who, const pt_DenoiseParams* p, DenoiseConst& k, bool untile = true)
 {
   if(c->width == 0)
     return c->fail(PT_ERR_STATE, "%s before pt_resize", who);
@@ -133,14 +134,14 @@ static int prepare_denoise(pt_context* c, const char* who, const pt_DenoiseParam
   for(DevBuf& b : c->dDenoise)
     if((rc = dev_alloc(c, b, sizeof(float4) * n)) != PT_OK)
       return rc;
-  return untile_to_rowmajor(c);
+  return untile ? untile_to_rowmajor(c) : PT_OK;
 }
-// The filter over dRowMajor, enqueued on the context's stream; returns the filtered row-major image (one of the denoiser's two, valid until the next call)
-static const float4* enqueue_filter(pt_context* c, const pt_DenoiseParams* p, const DenoiseConst& k)
+// The filter over the row-major image `src`, enqueued on the context's stream; returns the filtered row-major image (one of the denoiser's two, valid until the next call)
+static const float4* enqueue_filter(pt_context* c, const float4* src, const pt_DenoiseParams* p, const DenoiseConst& k)
 {
   const size_t  n      = size_t(c->width) * size_t(c->height);
   float4* const buf[2] = {(float4*)c->dDenoise[0].p, (float4*)c->dDenoise[1].p};
-  const float4* cur    = (const float4*)c->dRowMajor.p;
+  const float4* cur    = src;
   const bool    demod  = (p->flags & PT_DENOISE_DEMODULATE) != 0u;
   const auto    blocks = uint32_t((n + 255u) / 256u);
   if(demod)
@@ -173,7 +174,30 @@ static int enqueue_denoise(pt_context* c, const char* who, const pt_DenoiseParam
   const int    rc = prepare_denoise(c, who, p, k);
   if(rc != PT_OK)
     return rc;
-  result = enqueue_filter(c, p, k);
+  result = enqueue_filter(c, (const float4*)c->dRowMajor.p, p, k);
+  HIP_TRY(c, hipGetLastError());
+  return PT_OK;
+}
+// ... of the history's colour image (pt_temporal.hip) instead of the accumulation image; p == NULL (pt_tonemap_history): no spatial filter, the
+// history itself.  Reads the history and the current guide planes; writes the denoiser's own images only.
+static int enqueue_denoise_history(pt_context* c, const char* who, const pt_DenoiseParams* p, const float4*& result)
+{
+  if(c->width == 0)
+    return c->fail(PT_ERR_STATE, "%s before pt_resize", who);
+  if(!c->haveHistory)
+    return c->fail(PT_ERR_STATE, "%s: there is no history (no pt_temporal_accumulate since pt_resize / pt_temporal_reset)", who);
+  const float4* hist = (const float4*)c->dHistColour[c->histSet].p;
+  if(!p)
+  {
+    HIP_TRY(c, hipSetDevice(c->device));
+    result = hist;
+    return PT_OK;
+  }
+  DenoiseConst k;
+  const int    rc = prepare_denoise(c, who, p, k, false);
+  if(rc != PT_OK)
+    return rc;
+  result = enqueue_filter(c, hist, p, k);
   HIP_TRY(c, hipGetLastError());
   return PT_OK;
 }
@@ -235,6 +259,36 @@ int pt_tonemap_denoised(pt_context* c, const pt_DenoiseParams* p, const pt_Tonem
   return check_traversal(c);
 }
 
+int pt_denoise_history(pt_context* c, const pt_DenoiseParams* p, float* out)
+{
+  CTX_CHECK(c);
+  if(!p || !out)
+    return c->fail(PT_ERR_INVALID, "pt_denoise_history: null");
+  const float4* img = nullptr;
+  int           rc  = enqueue_denoise_history(c, "pt_denoise_history", p, img);
+  if(rc != PT_OK)
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(out, img, sizeof(float4) * size_t(c->width) * size_t(c->height), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, sync_all(c));
+  return check_traversal(c);
+}
+
+int pt_tonemap_history(pt_context* c, const pt_DenoiseParams* p, const pt_Tonemapper* tm, uint8_t* out)
+{
+  CTX_CHECK(c);
+  if(!tm || !out)
+    return c->fail(PT_ERR_INVALID, "pt_tonemap_history: null");
+  const float4* img = nullptr;
+  int           rc  = enqueue_denoise_history(c, "pt_tonemap_history", p, img);
+  if(rc != PT_OK)
+    return rc;
+  MipView mv{};
+  if((rc = display_levels(c, img, c->width, c->height, (tm->autoExposure & 1) != 0, mv)) != PT_OK || (rc = display_finish(c, tm, mv, c->width, c->height, out)) != PT_OK)
+    return rc;
+  HIP_TRY(c, sync_all(c));
+  return check_traversal(c);
+}
+
 // Test and measurement access (not part of pt_api.h): the largest step whose iteration stages its tile in LDS, 0 .. DN_LDS_MAX_STEP (0: every
 // iteration reads its taps from memory; negative: back to the default).  Results do not depend on it.  Returns the value in force.
 __attribute__((visibility("default"))) int pt_debug_denoise_lds(pt_context* c, int maxStep)
@@ -263,10 +317,10 @@ __attribute__((visibility("default"))) int pt_debug_denoise_time(pt_context* c, 
     (void)hipEventDestroy(ev[0]);
     return c->fail(PT_ERR_HIP, "pt_debug_denoise_time: hipEventCreate");
   }
-  (void)enqueue_filter(c, p, k);
+  (void)enqueue_filter(c, (const float4*)c->dRowMajor.p, p, k);
   hipError_t e = hipEventRecord(ev[0], c->stream);
   for(int i = 0; i < reps && e == hipSuccess; ++i)
-    (void)enqueue_filter(c, p, k);
+    (void)enqueue_filter(c, (const float4*)c->dRowMajor.p, p, k);
   if(e == hipSuccess) e = hipGetLastError();
   if(e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
   if(e == hipSuccess) e = sync_all(c);

@@ -198,10 +198,12 @@ int pt_build_env_accel(const float* px, int width, int height, pt_EnvAccel* acce
   return PT_OK;
 }
 
-int pt_camera_lookat(const float eye[3], const float center[3], const float up[3], float fov_degrees, float aspect, pt_SceneCamera* out)
+// glm::lookAt (right handed) and glm::perspectiveRH_ZO(fovy, aspect, 0.001, 100000) with [1][1] negated, column-major, in double: the two matrices
+// pt_camera_lookat inverts and pt_camera_world_to_clip multiplies.  *dist: |center - eye|.  false: null pointers, aspect <= 0, eye == center.
+static bool lookat_view_proj(const float eye[3], const float center[3], const float up[3], float fov_degrees, float aspect, double view[16], double proj[16], double* dist_out)
 {
-  if(!eye || !center || !up || !out || !(aspect > 0))
-    return PT_ERR_INVALID;
+  if(!eye || !center || !up || !(aspect > 0))
+    return false;
   auto sub   = [](const double* a, const double* b, double* r) { for(int i = 0; i < 3; ++i) r[i] = a[i] - b[i]; };
   auto dot   = [](const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
   auto cross = [](const double* a, const double* b, double* r) {
@@ -219,20 +221,46 @@ int pt_camera_lookat(const float eye[3], const float center[3], const float up[3
   sub(c, e, f);
   const double dist = norm(f);
   if(!(dist > 0))
-    return PT_ERR_INVALID;
+    return false;
   cross(f, u0, s);
   norm(s);
   cross(s, f, u);
   // glm::lookAt (right handed), column-major
-  const double view[16] = {s[0], u[0], -f[0], 0, s[1], u[1], -f[1], 0, s[2], u[2], -f[2], 0, -dot(s, e), -dot(u, e), dot(f, e), 1};
+  const double v[16] = {s[0], u[0], -f[0], 0, s[1], u[1], -f[1], 0, s[2], u[2], -f[2], 0, -dot(s, e), -dot(u, e), dot(f, e), 1};
+  std::memcpy(view, v, sizeof(v));
   // glm::perspectiveRH_ZO(fovy, aspect, 0.001, 100000) with [1][1] negated
   const double zn = 0.001, zf = 100000.0, th = std::tan(double(fov_degrees) * M_PI / 180.0 * 0.5);
-  double       proj[16] = {0};
+  std::memset(proj, 0, 16 * sizeof(double));
   proj[0]  = 1.0 / (double(aspect) * th);
   proj[5]  = -1.0 / th;
   proj[10] = zf / (zn - zf);
   proj[11] = -1.0;
   proj[14] = -(zf * zn) / (zf - zn);
+  *dist_out = dist;
+  return true;
+}
+
+int pt_camera_world_to_clip(const float eye[3], const float center[3], const float up[3], float fov_degrees, float aspect, float out16[16])
+{
+  double view[16], proj[16], dist;
+  if(!out16 || !lookat_view_proj(eye, center, up, fov_degrees, aspect, view, proj, &dist))
+    return PT_ERR_INVALID;
+  for(int col = 0; col < 4; ++col)
+    for(int r = 0; r < 4; ++r)
+    {
+      double acc = 0.0;
+      for(int i = 0; i < 4; ++i)
+        acc += proj[i * 4 + r] * view[col * 4 + i];
+      out16[col * 4 + r] = float(acc);
+    }
+  return PT_OK;
+}
+
+int pt_camera_lookat(const float eye[3], const float center[3], const float up[3], float fov_degrees, float aspect, pt_SceneCamera* out)
+{
+  double view[16], proj[16], dist;
+  if(!out || !lookat_view_proj(eye, center, up, fov_degrees, aspect, view, proj, &dist))
+    return PT_ERR_INVALID;
   double vi[16], pi[16];
   if(!invert_4x4(view, vi) || !invert_4x4(proj, pi))
     return PT_ERR_INVALID;

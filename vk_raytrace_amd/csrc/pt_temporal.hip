@@ -1,0 +1,200 @@
+// pt_temporal_accumulate / pt_temporal_reset / pt_read_temporal_history (include/pt_api.h): the temporal reprojection stage of the display path
+// (DESIGN.md section 5.3).  The per-pixel arithmetic is pt_temporal.h; this unit holds its kernel, the launch, the history the context keeps and the
+// entry points.  No existing kernel is involved: the stage reads the row-major image the display pass already produces (untile_to_rowmajor), guide
+// planes 1 and 2 and the camera, and writes only the history.
+#include "pt_context.h"
+#include "pt_temporal.h"
+
+// One block covers a TP_TX x TP_TY tile of the image, one pixel per lane: a wave covers two rows of 32 pixels, so that adjacent lanes read and write
+// adjacent 16-byte pixels (512 contiguous bytes per row and plane) and the 4-byte length plane in 128-byte runs.  The gather is data dependent but
+// coherent: neighbouring pixels reproject to neighbouring history positions.
+#define TP_TX 32
+#define TP_TY 8
+#define TP_BLOCK (TP_TX * TP_TY)
+
+struct TpArgs {
+  const float4 *c, *g1, *g2;  // accumulation image (row-major), guide planes 1 and 2
+  const float4 *hc, *hg;      // the history set that is read (never the set that is written: a lane gathers from positions other lanes write)
+  const float*  hn;
+  float4 *      hcOut, *hgOut;
+  float*        hnOut;
+  int           w, h;
+  TemporalConst k;
+};
+
+PT_DN DnPx tp_px(const float4& v) { return DnPx{v.x, v.y, v.z, v.w}; }
+
+struct TpGlobal {
+  const TpArgs& a;
+  __device__ size_t at(int x, int y) const { return size_t(y) * size_t(a.w) + size_t(x); }
+  __device__ DnPx   colour(int x, int y) const { return tp_px(a.c[at(x, y)]); }
+  __device__ DnPx   normal(int x, int y) const { return tp_px(a.g1[at(x, y)]); }
+  __device__ DnPx   depth(int x, int y) const { return tp_px(a.g2[at(x, y)]); }
+  __device__ DnPx   histColour(int x, int y) const { return tp_px(a.hc[at(x, y)]); }
+  __device__ DnPx   histGuide(int x, int y) const { return tp_px(a.hg[at(x, y)]); }
+  __device__ float  histLength(int x, int y) const { return a.hn[at(x, y)]; }
+};
+
+__global__ void __launch_bounds__(TP_BLOCK) k_temporal(TpArgs a)
+{
+  const int x = int(blockIdx.x) * TP_TX + int(threadIdx.x), y = int(blockIdx.y) * TP_TY + int(threadIdx.y);
+  if(x >= a.w || y >= a.h)
+    return;
+  const TemporalOut o  = temporal_pixel(TpGlobal{a}, a.k, x, y, a.w, a.h, nullptr);
+  const size_t      at = size_t(y) * size_t(a.w) + size_t(x);
+  a.hcOut[at]          = make_float4(o.colour.x, o.colour.y, o.colour.z, o.colour.w);
+  a.hgOut[at]          = make_float4(o.guide.x, o.guide.y, o.guide.z, o.guide.w);
+  a.hnOut[at]          = o.length;
+}
+
+static void launch_temporal(hipStream_t stream, const TpArgs& a)
+{
+  const dim3 grid((a.w + TP_TX - 1) / TP_TX, (a.h + TP_TY - 1) / TP_TY), block(TP_TX, TP_TY);
+  k_temporal<<<grid, block, 0, stream>>>(a);
+}
+
+void temporal_release(pt_context* c)
+{
+  for(int s = 0; s < 2; ++s)
+  {
+    dev_free(c->dHistColour[s]);
+    dev_free(c->dHistGuide[s]);
+    dev_free(c->dHistLength[s]);
+  }
+  c->haveHistory = false;
+}
+
+// Everything pt_temporal_accumulate checks, then both history sets allocated and the row-major accumulation image enqueued on the context's stream
+// behind the frames rendered so far; the kernel's arguments in `a`.  Nothing of the history changes here.
+static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalParams* p, TpArgs& a)
+{
+  if(c->width == 0)
+    return c->fail(PT_ERR_STATE, "%s before pt_resize", who);
+  if(!c->haveCamera)
+    return c->fail(PT_ERR_STATE, "%s before pt_set_camera", who);
+  if(!c->dGuide[1].p || !c->dGuide[2].p)
+    return c->fail(PT_ERR_STATE, "%s: guide planes 1 (normal) and 2 (depth) must be installed (pt_render_guides or pt_set_denoise_guides)", who);
+  if(c->nranks > 1 && !c->haveFull)
+    return c->fail(PT_ERR_STATE, "%s: rank %d of %d holds only its own tiles; gather the image first", who, c->rank, c->nranks);
+  const char* why = "";
+  int         rc  = temporal_constants(p, &why);
+  if(rc != PT_OK)
+    return c->fail(rc, "%s: %s", who, why);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t n = size_t(c->width) * size_t(c->height);
+  for(int s = 0; s < 2; ++s)
+    if((rc = dev_alloc(c, c->dHistColour[s], sizeof(float4) * n)) != PT_OK || (rc = dev_alloc(c, c->dHistGuide[s], sizeof(float4) * n)) != PT_OK
+       || (rc = dev_alloc(c, c->dHistLength[s], sizeof(float) * n)) != PT_OK)
+      return rc;
+  if((rc = untile_to_rowmajor(c)) != PT_OK)
+    return rc;
+  const int r = c->histSet, wr = r ^ 1;
+  a.c     = (const float4*)c->dRowMajor.p;
+  a.g1    = (const float4*)c->dGuide[1].p;
+  a.g2    = (const float4*)c->dGuide[2].p;
+  a.hc    = (const float4*)c->dHistColour[r].p;
+  a.hg    = (const float4*)c->dHistGuide[r].p;
+  a.hn    = (const float*)c->dHistLength[r].p;
+  a.hcOut = (float4*)c->dHistColour[wr].p;
+  a.hgOut = (float4*)c->dHistGuide[wr].p;
+  a.hnOut = (float*)c->dHistLength[wr].p;
+  a.w     = c->width;
+  a.h     = c->height;
+  for(int i = 0; i < 16; ++i)
+  {
+    a.k.viewInverse[i]  = c->scene.camera.viewInverse[i];
+    a.k.projInverse[i]  = c->scene.camera.projInverse[i];
+    a.k.worldToClipH[i] = c->histWorldToClip[i];
+  }
+  for(int i = 0; i < 3; ++i)
+    a.k.eyeH[i] = c->histEye[i];
+  a.k.haveHistory = c->haveHistory ? 1 : 0;
+  a.k.depthTol    = p->depthTol;
+  a.k.normalDist2 = p->normalDist2;
+  a.k.maxHistory  = p->maxHistory;
+  return PT_OK;
+}
+
+extern "C" {
+
+int pt_temporal_accumulate(pt_context* c, const pt_TemporalParams* p, float* out)
+{
+  CTX_CHECK(c);
+  TpArgs a;
+  int    rc = prepare_temporal(c, "pt_temporal_accumulate", p, a);
+  if(rc != PT_OK)
+    return rc;
+  launch_temporal(c->stream, a);
+  HIP_TRY(c, hipGetLastError());
+  if(out)
+    HIP_TRY(c, hipMemcpyAsync(out, a.hcOut, sizeof(float4) * size_t(c->width) * size_t(c->height), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, sync_all(c));
+  // the set just written is the history now, made with the current camera
+  for(int i = 0; i < 16; ++i)
+    c->histWorldToClip[i] = p->worldToClip[i];
+  for(int i = 0; i < 3; ++i)
+    c->histEye[i] = c->scene.camera.viewInverse[12 + i];
+  c->histSet ^= 1;
+  c->haveHistory = true;
+  return check_traversal(c);
+}
+
+int pt_temporal_reset(pt_context* c)
+{
+  CTX_CHECK(c);
+  c->haveHistory = false;  // the buffers stay for the next call; pt_resize and pt_destroy free them
+  return PT_OK;
+}
+
+int pt_read_temporal_history(pt_context* c, float* rgba32f_out, float* length_out)
+{
+  CTX_CHECK(c);
+  if(!c->haveHistory)
+    return c->fail(PT_ERR_STATE, "pt_read_temporal_history: there is no history (no pt_temporal_accumulate since pt_resize / pt_temporal_reset)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t n = size_t(c->width) * size_t(c->height);
+  if(rgba32f_out)
+    HIP_TRY(c, hipMemcpyAsync(rgba32f_out, c->dHistColour[c->histSet].p, sizeof(float4) * n, hipMemcpyDeviceToHost, c->stream));
+  if(length_out)
+    HIP_TRY(c, hipMemcpyAsync(length_out, c->dHistLength[c->histSet].p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, sync_all(c));
+  return check_traversal(c);
+}
+
+// Measurement access (not part of pt_api.h; tools/temporal_rate.py): the kernel of pt_temporal_accumulate enqueued `reps` times between two events on
+// the context's stream, after one untimed run -- milliseconds per run in *ms_out, without the untile pass before it and without any copy.  Every run
+// reads the history and writes the other set; the history itself stays as it was.  Synchronous.
+__attribute__((visibility("default"))) int pt_debug_temporal_time(pt_context* c, const pt_TemporalParams* p, int reps, float* ms_out)
+{
+  CTX_CHECK(c);
+  if(!ms_out || reps < 1)
+    return c->fail(PT_ERR_INVALID, "pt_debug_temporal_time: null or reps < 1");
+  TpArgs a;
+  int    rc = prepare_temporal(c, "pt_debug_temporal_time", p, a);
+  if(rc != PT_OK)
+    return rc;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  HIP_TRY(c, hipEventCreate(&ev[0]));
+  if(hipEventCreate(&ev[1]) != hipSuccess)
+  {
+    (void)hipEventDestroy(ev[0]);
+    return c->fail(PT_ERR_HIP, "pt_debug_temporal_time: hipEventCreate");
+  }
+  launch_temporal(c->stream, a);
+  hipError_t e = hipEventRecord(ev[0], c->stream);
+  for(int i = 0; i < reps && e == hipSuccess; ++i)
+    launch_temporal(c->stream, a);
+  if(e == hipSuccess) e = hipGetLastError();
+  if(e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  if(e == hipSuccess) e = sync_all(c);
+  float ms = 0.0f;
+  if(e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  (void)hipEventDestroy(ev[0]);
+  (void)hipEventDestroy(ev[1]);
+  if(e != hipSuccess)
+    return c->fail(PT_ERR_HIP, "pt_debug_temporal_time: %s", hipGetErrorString(e));
+  *ms_out = ms / float(reps);
+  return check_traversal(c);
+}
+
+}  // extern "C"

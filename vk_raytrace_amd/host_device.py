@@ -120,6 +120,11 @@ class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("sigmaColor", C.c_float), ("sigmaGuide", C.c_float * 3), ("flags", C.c_uint32)]
 
 
+class TemporalParams(C.Structure):
+    """pt_TemporalParams (pt_temporal_accumulate): worldToClip is the forward matrix (proj * view, column-major) of the CURRENT camera"""
+    _fields_ = [("worldToClip", C.c_float * 16), ("depthTol", C.c_float), ("normalDist2", C.c_float), ("maxHistory", C.c_float), ("flags", C.c_uint32)]
+
+
 class Peaks(C.Structure):
     """pt_Peaks (pt_measure_peaks): ceilings measured on the device"""
     _fields_ = [("valuWaveInstrPerSec", C.c_double), ("hbmCopyBytesPerSec", C.c_double), ("hbmReadBytesPerSec", C.c_double), ("computeUnits", C.c_int32),
@@ -146,7 +151,7 @@ class Stats(C.Structure):
 assert C.sizeof(RtxState) == 48 and C.sizeof(SceneCamera) == 140 and C.sizeof(VertexAttributes) == 32
 assert C.sizeof(GltfShadeMaterial) == 216 and C.sizeof(Light) == 64 and C.sizeof(EnvAccel) == 16
 assert C.sizeof(Tonemapper) == 48 and C.sizeof(SunAndSky) == 96 and C.sizeof(PrimMesh) == 20 and C.sizeof(Node) == 68
-assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32 and C.sizeof(DenoiseParams) == 24
+assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32 and C.sizeof(DenoiseParams) == 24 and C.sizeof(TemporalParams) == 80
 
 vertex_dtype = np.dtype(VertexAttributes)
 ray_dtype = np.dtype(Ray)

@@ -285,6 +285,51 @@ class HipRenderer(Renderer):
         self._check(self._lib.pt_read_denoise_guides(self._ctx, ptrs))
         return tuple(out)
 
+    # -- temporal reprojection (no reference counterpart) ----------------------------------------------
+    @staticmethod
+    def world_to_clip(camera, aspect):
+        """The forward matrix (proj * view, column-major, 16 float32) of a scene.Camera at `aspect`: TemporalParams.worldToClip of the camera that
+        set_camera was given (pt_camera_world_to_clip)"""
+        return capi.camera_world_to_clip(camera, aspect)
+
+    @staticmethod
+    def temporal_params(world_to_clip, depth_tol=0.05, normal_dist2=0.05, max_history=32.0):
+        return hd.TemporalParams(worldToClip=tuple(float(v) for v in np.asarray(world_to_clip, np.float32).reshape(16)), depthTol=depth_tol,
+                                 normalDist2=normal_dist2, maxHistory=max_history, flags=0)
+
+    def temporal_accumulate(self, params: hd.TemporalParams, read=True):
+        """pt_temporal_accumulate: reprojects the history into the current camera and blends the accumulation image into it; needs guide planes 1
+        and 2 (capture_guides).  Returns the new history colour ((H, W, 4) float32), or None with read=False."""
+        w, h = self.size
+        out = np.empty((h, w, 4), np.float32) if read else None
+        self._check(self._lib.pt_temporal_accumulate(self._ctx, C.byref(params), None if out is None else out.ctypes.data))
+        return out
+
+    def temporal_reset(self):
+        """pt_temporal_reset: drops the history (scene change, cut)"""
+        self._check(self._lib.pt_temporal_reset(self._ctx))
+
+    def read_temporal_history(self):
+        """pt_read_temporal_history: (colour (H, W, 4), length (H, W)) float32"""
+        w, h = self.size
+        colour, length = np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32)
+        self._check(self._lib.pt_read_temporal_history(self._ctx, colour.ctypes.data, length.ctypes.data))
+        return colour, length
+
+    def denoise_history(self, params: hd.DenoiseParams):
+        """pt_denoise_history: denoise() of the history's colour image"""
+        w, h = self.size
+        out = np.empty((h, w, 4), np.float32)
+        self._check(self._lib.pt_denoise_history(self._ctx, C.byref(params), out.ctypes.data))
+        return out
+
+    def tonemap_history(self, params, tm: hd.Tonemapper):
+        """pt_tonemap_history: tonemap() of the history's colour image, spatially filtered first unless params is None"""
+        w, h = self.size
+        out = np.empty((h, w, 4), np.uint8)
+        self._check(self._lib.pt_tonemap_history(self._ctx, None if params is None else C.byref(params), C.byref(tm), out.ctypes.data))
+        return out
+
     def tonemap_begin(self, tm: hd.Tonemapper, display_size=None):
         """pt_tonemap_begin: the display pass enqueued behind the frames rendered so far; later frames overlap it.  tonemap_end() returns the
         oldest image begun (at most 4 may be pending)."""
