@@ -264,6 +264,44 @@ int pt_denoise_history(pt_context* ctx, const pt_DenoiseParams* params, float* r
  * pt_tonemap_zoom of the history and a begin / end form.) */
 int pt_tonemap_history(pt_context* ctx, const pt_DenoiseParams* params, const pt_Tonemapper* tm, uint8_t* rgba8_out);
 
+/* ---- variance-guided filtering of the history (no reference counterpart) -----------------------------------------------------------------------
+ * The spatial half of SVGF, which completes the 1 spp display path: while tracking is on, the history also keeps the first two moments of the
+ * luminance; from them (where the history is long) or from a 7 x 7 neighbourhood (where it is short) every pixel gets a variance estimate, and the
+ * a-trous filter stops at luminance differences measured in standard deviations of it, carrying the variance through its iterations.  DESIGN.md
+ * section 5.4 has the definition, csrc/pt_svgf.h the one fp32 operation sequence host and device share.  Typical use: pt_temporal_track_moments(1)
+ * once, then per camera move pt_set_camera, pt_render_guides, pt_render_frame (frame 0), pt_temporal_accumulate, pt_tonemap_svgf.  No render
+ * kernel captures anything for it, and with tracking off every other entry point behaves bit for bit as it does without this section. */
+
+/* No reference counterpart.  on = 1: pt_temporal_accumulate also writes the moments image (width * height * 2 floats: mean of the luminance, mean of
+ * its square, blended exactly as the colour is); on = 0 (the default): it does not.  The history's colour, guide and length images and the returned
+ * image are bit for bit the same either way.  A change of the value drops the history as pt_temporal_reset does; the setting survives pt_resize.
+ * PT_ERR_INVALID: on is neither 0 nor 1. */
+int pt_temporal_track_moments(pt_context* ctx, int on);
+
+/* No reference counterpart.  Copies the history's moments image (width * height * 2 floats) out.  Synchronous.  PT_ERR_STATE: there is no history,
+ * or it was made while tracking was off.  m_out == NULL: PT_ERR_INVALID. */
+int pt_read_temporal_moments(pt_context* ctx, float* m_out);
+
+/* No reference counterpart.  The initial variance estimate V0 of the history alone (width * height floats, each in [0, FLT_MAX]): m2 - m1^2 where the
+ * history is at least params->minTemporal long, else the guide-weighted 7 x 7 estimate scaled by minTemporal / length.  Reads the history and the
+ * current guide planes (each installed plane gives a term, none is required).  Synchronous like pt_denoise_history: waits for the frames in flight
+ * and reports their traversal-stack overflow with PT_ERR_STATE.  The history, the accumulation tiles, the path state, the frame slots, the guide
+ * planes and every pt_Stats field stay as they are.  PT_ERR_STATE: before pt_resize; there is no history; the history was made while tracking was
+ * off.  PT_ERR_INVALID, with nothing launched: null arguments, iterations outside 1 .. 8, sigmaLum or lumFloor not positive and finite, minTemporal
+ * below 1 or not finite, sigmaGuide of an installed plane not positive and finite or so small that 1 / sigma^2 overflows, any flag bit. */
+int pt_svgf_variance(pt_context* ctx, const pt_SvgfParams* params, float* variance_out);
+
+/* No reference counterpart.  The history's colour image after params->iterations iterations of the variance-guided filter (width * height * 4
+ * floats, alpha copied), and in variance_out (may be NULL; width * height floats) the variance after the last iteration.  Guides must be finite (the
+ * result is unspecified otherwise; reads stay in bounds).  Synchronous; read-only as pt_svgf_variance; errors as pt_svgf_variance. */
+int pt_svgf_history(pt_context* ctx, const pt_SvgfParams* params, float* rgba32f_out, float* variance_out);
+
+/* No reference counterpart.  pt_tonemap (viewport = accumulation size) with pt_svgf_history's image as level 0 of the offscreen image: the bytes are
+ * those of pt_tonemap on a context whose accumulation image was replaced by pt_svgf_history's output with pt_write_accum.  Synchronous; errors as
+ * pt_svgf_history and pt_tonemap; tm or rgba8_out NULL: PT_ERR_INVALID.  (Not provided: pt_tonemap_zoom of the filtered history and a begin / end
+ * form.) */
+int pt_tonemap_svgf(pt_context* ctx, const pt_SvgfParams* params, const pt_Tonemapper* tm, uint8_t* rgba8_out);
+
 /* Test access to the image the display pass samples: builds the offscreen image of a disp_width x disp_height viewport and its full mip chain exactly
  * as pt_tonemap_zoom does with auto-exposure on, and copies level `level` (RGBA32F, row-major) to rgba32f_out, its extent to *width / *height (each may
  * be NULL).  Returns the number of levels (>= 1), or a negative pt_Result. */

@@ -141,6 +141,14 @@ public:
   bool temporalAccumulate(const pt_TemporalParams& p, float* rgba32f = nullptr) { return check(pt_temporal_accumulate(m_ctx, &p, rgba32f)); }
   bool temporalReset() { return check(pt_temporal_reset(m_ctx)); }
   bool readTemporalHistory(float* rgba32f, float* length) { return check(pt_read_temporal_history(m_ctx, rgba32f, length)); }
+  // variance-guided filter of the history (no reference counterpart): with trackMoments(true) temporalAccumulate also keeps the
+  // luminance moments, from which svgfVariance estimates a per-pixel variance and svgfHistory / tonemapSvgf filter the history with a luminance stop
+  // measured in standard deviations.  A change of trackMoments drops the history.
+  bool trackMoments(bool on) { return check(pt_temporal_track_moments(m_ctx, on ? 1 : 0)); }
+  bool readTemporalMoments(float* m) { return check(pt_read_temporal_moments(m_ctx, m)); }
+  bool svgfVariance(const pt_SvgfParams& p, float* variance) { return check(pt_svgf_variance(m_ctx, &p, variance)); }
+  bool svgfHistory(const pt_SvgfParams& p, float* rgba32f, float* variance = nullptr) { return check(pt_svgf_history(m_ctx, &p, rgba32f, variance)); }
+  bool tonemapSvgf(const pt_SvgfParams& p, const pt_Tonemapper& tm, uint8_t* rgba8) { return check(pt_tonemap_svgf(m_ctx, &p, &tm, rgba8)); }
   bool denoiseHistory(const pt_DenoiseParams& p, float* rgba32f) { return check(pt_denoise_history(m_ctx, &p, rgba32f)); }
   // dp == nullptr: no spatial filter
   bool tonemapHistory(const pt_DenoiseParams* dp, const pt_Tonemapper& tm, uint8_t* rgba8) { return check(pt_tonemap_history(m_ctx, dp, &tm, rgba8)); }

@@ -278,6 +278,18 @@ typedef struct pt_TemporalParams {
   uint32_t flags;           /* none defined: must be 0 */
 } pt_TemporalParams;
 
+/* pt_svgf_variance / pt_svgf_history / pt_tonemap_svgf: the variance-guided filter of the history (no reference counterpart; defined in DESIGN.md
+ * section 5.4 and stated once in csrc/pt_svgf.h).  The luminance edge stop is measured in standard deviations of the per-pixel variance estimate
+ * that the moments in the history (pt_temporal_track_moments) give; guide terms are those of pt_DenoiseParams. */
+typedef struct pt_SvgfParams {
+  int32_t  iterations;                    /* 1 .. 8; iteration i taps at distance 2^i */
+  float    sigmaLum;                      /* luminance differences are divided by sigmaLum * sqrt(variance) + lumFloor; > 0, finite (SVGF: 4) */
+  float    lumFloor;                      /* > 0, finite: keeps the divisor positive where the variance is 0 */
+  float    sigmaGuide[PT_DENOISE_GUIDES]; /* of the term of guide plane j; read only for the planes that are installed */
+  float    minTemporal;                   /* a pixel whose history is shorter estimates its variance spatially; >= 1, finite (SVGF: 4) */
+  uint32_t flags;                         /* none defined: must be 0 */
+} pt_SvgfParams;
+
 /* Counters the measurement contract needs; all totals since pt_reset_stats. */
 typedef struct pt_Stats {
   uint64_t samples;          /* pixel-samples rendered */
@@ -342,6 +354,7 @@ static_assert(sizeof(pt_Node) == 68, "Node");
 static_assert(sizeof(pt_Ray) == 32 && sizeof(pt_RayHit) == 32, "Ray / RayHit");
 static_assert(sizeof(pt_DenoiseParams) == 24, "DenoiseParams");
 static_assert(sizeof(pt_TemporalParams) == 80, "TemporalParams");
+static_assert(sizeof(pt_SvgfParams) == 32, "SvgfParams");
 #endif
 
 #endif /* PT_TYPES_H */

@@ -1,0 +1,132 @@
+// The host build of the variance-guided filter: vk_raytrace_amd/csrc/pt_svgf.h compiled by g++, whole calls over row-major images in ordinary memory.
+// tests/svgf_host.py compiles and binds it; tests/test_svgf_model.py holds it to a float64 model, tests/test_svgf_gpu.py holds the device to it.
+#include <cstring>
+#include <vector>
+#include "pt_svgf.h"
+
+namespace {
+uint32_t planes_of(const float* const g[PT_DENOISE_GUIDES])
+{
+  uint32_t m = 0;
+  for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
+    m |= g && g[j] ? 1u << j : 0u;
+  return m;
+}
+SvRowMajor source(const float* colour, const float* const g[PT_DENOISE_GUIDES], const float* variance, const float* length, const float* moments, int w)
+{
+  SvRowMajor s{};
+  s.c = (const DnPx*)colour;
+  for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
+    s.g[j] = g ? (const DnPx*)g[j] : nullptr;
+  s.v  = variance;
+  s.hn = length;
+  s.hm = (const SvM*)moments;
+  s.w  = w;
+  return s;
+}
+}  // namespace
+
+extern "C" {
+
+// pt_temporal_accumulate with tracking on, on the host: the arguments of th_temporal (tests/cpp/temporal_host.cpp) and the moments image of the history
+// that is read (w * h * 2 floats; not read for a first call), the four new history images out.
+int sh_temporal_m(const float* colour, const float* normal, const float* depth, int w, int h, const float* view_inverse, const float* proj_inverse,
+                  const pt_TemporalParams* params, const float* hist_colour, const float* hist_guide, const float* hist_length, const float* hist_moments,
+                  const float* world_to_clip_h, const float* eye_h, float* out_colour, float* out_guide, float* out_length, float* out_moments)
+{
+  const char* why = "";
+  const int   rc  = temporal_constants(params, &why);
+  if(rc != PT_OK)
+    return rc;
+  if(!colour || !normal || !depth || !view_inverse || !proj_inverse || !out_colour || !out_guide || !out_length || !out_moments || w <= 0 || h <= 0
+     || (hist_colour && (!hist_guide || !hist_length || !hist_moments || !world_to_clip_h || !eye_h)))
+    return PT_ERR_INVALID;
+  TemporalConst k;
+  std::memset(&k, 0, sizeof(k));
+  std::memcpy(k.viewInverse, view_inverse, sizeof(k.viewInverse));
+  std::memcpy(k.projInverse, proj_inverse, sizeof(k.projInverse));
+  if(hist_colour)
+  {
+    std::memcpy(k.worldToClipH, world_to_clip_h, sizeof(k.worldToClipH));
+    std::memcpy(k.eyeH, eye_h, sizeof(k.eyeH));
+  }
+  k.haveHistory = hist_colour ? 1 : 0;
+  k.depthTol    = params->depthTol;
+  k.normalDist2 = params->normalDist2;
+  k.maxHistory  = params->maxHistory;
+  const TpRowMajor src{(const DnPx*)colour, (const DnPx*)normal, (const DnPx*)depth, (const DnPx*)hist_colour, (const DnPx*)hist_guide, hist_length, w};
+  const SvRowMajor msrc = source(nullptr, nullptr, nullptr, nullptr, hist_moments, w);
+#pragma omp parallel for schedule(static)
+  for(int y = 0; y < h; ++y)
+    for(int x = 0; x < w; ++x)
+    {
+      TemporalProbe     pr;
+      const TemporalOut o  = temporal_pixel(src, k, x, y, w, h, &pr);
+      const SvM         m  = svgf_moments(msrc, pr, o, src.colour(x, y));
+      const size_t      at = size_t(y) * size_t(w) + size_t(x);
+      std::memcpy(out_colour + 4 * at, &o.colour, sizeof(DnPx));
+      std::memcpy(out_guide + 4 * at, &o.guide, sizeof(DnPx));
+      out_length[at]          = o.length;
+      out_moments[2 * at]     = m.x;
+      out_moments[2 * at + 1] = m.y;
+    }
+  return PT_OK;
+}
+
+// pt_svgf_variance on the host: V0 from the history's colour, length and moments and the guide planes (guides[j] NULL: plane j not installed)
+int sh_variance(const float* hist_colour, const float* hist_length, const float* hist_moments, const float* const guides[PT_DENOISE_GUIDES], int w, int h,
+                const pt_SvgfParams* params, float* out_variance)
+{
+  SvgfConst   k;
+  const char* why = "";
+  const int   rc  = svgf_constants(params, planes_of(guides), &k, &why);
+  if(rc != PT_OK)
+    return rc;
+  if(!hist_colour || !hist_length || !hist_moments || !out_variance || w <= 0 || h <= 0)
+    return PT_ERR_INVALID;
+  const SvRowMajor src = source(hist_colour, guides, nullptr, hist_length, hist_moments, w);
+#pragma omp parallel for schedule(static)
+  for(int y = 0; y < h; ++y)
+    for(int x = 0; x < w; ++x)
+      out_variance[size_t(y) * size_t(w) + size_t(x)] = svgf_variance_pixel(src, x, y, w, h, k);
+  return PT_OK;
+}
+
+// ONE iteration of the filter on the host, colour and variance given directly (a test may hand in any variance plane)
+int sh_iteration(const float* colour, const float* variance, const float* const guides[PT_DENOISE_GUIDES], int w, int h, const pt_SvgfParams* params,
+                 int iteration, float* out_colour, float* out_variance)
+{
+  SvgfConst   k;
+  const char* why = "";
+  const int   rc  = svgf_constants(params, planes_of(guides), &k, &why);
+  if(rc != PT_OK)
+    return rc;
+  if(!colour || !variance || !out_colour || !out_variance || w <= 0 || h <= 0 || iteration < 0 || iteration >= PT_SVGF_MAX_ITERATIONS)
+    return PT_ERR_INVALID;
+  const SvRowMajor src = source(colour, guides, variance, nullptr, nullptr, w);
+#pragma omp parallel for schedule(static)
+  for(int y = 0; y < h; ++y)
+    for(int x = 0; x < w; ++x)
+    {
+      const SvOut  o  = svgf_pixel(src, x, y, w, h, iteration, k);
+      const size_t at = size_t(y) * size_t(w) + size_t(x);
+      std::memcpy(out_colour + 4 * at, &o.colour, sizeof(DnPx));
+      out_variance[at] = o.variance;
+    }
+  return PT_OK;
+}
+
+// svgf_constants: the status, and the static reason in why_out (why_len bytes, may be NULL).  planes: bit j = guide plane j is installed
+int sh_constants(const pt_SvgfParams* params, unsigned planes, char* why_out, int why_len)
+{
+  SvgfConst   k;
+  const char* why = "";
+  const int   rc  = svgf_constants(params, planes, &k, &why);
+  if(why_out && why_len > 0)
+  {
+    std::strncpy(why_out, why, size_t(why_len) - 1);
+    why_out[why_len - 1] = 0;
+  }
+  return rc;
+}
+}

@@ -67,6 +67,11 @@ API = [
     ("pt_read_temporal_history", C.c_int, [_P, _P, _P]),
     ("pt_denoise_history", C.c_int, [_P, C.POINTER(hd.DenoiseParams), _P]),
     ("pt_tonemap_history", C.c_int, [_P, C.POINTER(hd.DenoiseParams), C.POINTER(hd.Tonemapper), _P]),
+    ("pt_temporal_track_moments", C.c_int, [_P, C.c_int]),
+    ("pt_read_temporal_moments", C.c_int, [_P, _P]),
+    ("pt_svgf_variance", C.c_int, [_P, C.POINTER(hd.SvgfParams), _P]),
+    ("pt_svgf_history", C.c_int, [_P, C.POINTER(hd.SvgfParams), _P, _P]),
+    ("pt_tonemap_svgf", C.c_int, [_P, C.POINTER(hd.SvgfParams), C.POINTER(hd.Tonemapper), _P]),
     ("pt_debug_display_level", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_local_shard", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_scatter_shards", C.c_int, [_P, _P, C.c_int]),
@@ -111,6 +116,8 @@ DEBUG_API = [
     ("pt_debug_denoise_time", C.c_int, [_P, C.POINTER(hd.DenoiseParams), C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_denoise.hip: (ctx, params, reps, ms per run out): the filter alone, device events
     ("pt_debug_guides_time", C.c_int, [_P, C.c_uint32, C.c_float, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_guides.hip: (ctx, planes, miss_depth, reps, ms per run out): the guide pass alone, device events
     ("pt_debug_temporal_time", C.c_int, [_P, C.POINTER(hd.TemporalParams), C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_temporal.hip: (ctx, params, reps, ms per run out): the temporal kernel alone, device events
+    ("pt_debug_svgf_lds", C.c_int, [_P, C.c_int]),  # csrc/pt_svgf.hip: (ctx, largest step staged in LDS; negative: the default) -> the value in force
+    ("pt_debug_svgf_time", C.c_int, [_P, C.POINTER(hd.SvgfParams), C.c_int, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_svgf.hip: (ctx, params, part (-2 whole, -1 variance, i: iteration i), reps, ms per run out), device events
     ("pt_debug_bounce_counts", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[max_bounces][16], max_bounces) -> staged bounces of the newest finished launch sequence
     ("pt_debug_accel_info", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[words], words) -> words of the info record (csrc/pt_accel_dump.h)
     ("pt_debug_accel_read", C.c_longlong, [_P, C.c_int, _P, C.c_size_t]),  # csrc/pt_debug.hip: (ctx, array id, dst, bytes) -> bytes the array holds; 0: no such array

@@ -130,6 +130,11 @@ struct pt_context {
   int      histSet     = 0;      // the set that holds the history (the next call reads it and writes the other)
   bool     haveHistory = false;
   float    histWorldToClip[16] = {0}, histEye[3] = {0, 0, 0};
+  // variance-guided filter (pt_svgf.hip): with trackMoments the history has a fourth image, the luminance moments (float2, twice like the others);
+  // histHasMoments: the history that is held was made while tracking was on.  dSvgfVar: the filter's two variance planes, allocated on first use.
+  DevBuf   dHistMoments[2], dSvgfVar[2];
+  bool     trackMoments = false, histHasMoments = false;
+  int      svgfLdsMaxStep = -1;  // largest step whose iteration stages its tile in LDS (-1: the measured default; pt_debug_svgf_lds)
   bool     haveFull = false;
   // pipelined display (pt_tonemap_begin / pt_tonemap_end): a ring of pinned host images, each with the event that says its copy has landed
   // and the event after which the accumulation image may be written again (the untile pass has read it)
@@ -183,6 +188,17 @@ int        display_levels(pt_context* c, const float4* image, int dispW, int dis
 int        display_finish(pt_context* c, const pt_Tonemapper* tm, MipView& mv, int dispW, int dispH, uint8_t* out);  // ... the tonemap kernel and the copy to `out` (host), enqueued
 void       denoise_release(pt_context* c);  // pt_denoise.hip: frees the denoiser's images and drops the guide planes
 void       temporal_release(pt_context* c);  // pt_temporal.hip: frees the history
+struct TemporalConst;
+struct TemporalMArgs {  // pt_svgf.hip: k_temporal_m, the temporal kernel that also writes the moments -- the arguments of k_temporal and the fourth image
+  const float4 *c, *g1, *g2, *hc, *hg;
+  const float*  hn;
+  const float2* hm;
+  float4 *      hcOut, *hgOut;
+  float*        hnOut;
+  float2*       hmOut;
+  int           w, h;
+};
+void       launch_temporal_m(hipStream_t stream, const TemporalMArgs& a, const TemporalConst& k);
 void       refresh_scene_ptrs(pt_context* c);
 int        upload_instances(pt_context* c);
 std::vector<InstanceRec> effective_instances(const pt_context* c);  // the instance records as the kernels see them

@@ -47,10 +47,18 @@ __global__ void __launch_bounds__(TP_BLOCK) k_temporal(TpArgs a)
   a.hnOut[at]          = o.length;
 }
 
-static void launch_temporal(hipStream_t stream, const TpArgs& a)
+// with tracking on (pt_temporal_track_moments) the kernel of pt_svgf.hip runs instead: the same pixel function, and the moments image besides
+static void launch_temporal(const pt_context* c, const TpArgs& a)
 {
+  if(c->trackMoments)
+  {
+    const int r = c->histSet;
+    launch_temporal_m(c->stream, TemporalMArgs{a.c, a.g1, a.g2, a.hc, a.hg, a.hn, (const float2*)c->dHistMoments[r].p, a.hcOut, a.hgOut, a.hnOut,
+                                                (float2*)c->dHistMoments[r ^ 1].p, a.w, a.h}, a.k);
+    return;
+  }
   const dim3 grid((a.w + TP_TX - 1) / TP_TX, (a.h + TP_TY - 1) / TP_TY), block(TP_TX, TP_TY);
-  k_temporal<<<grid, block, 0, stream>>>(a);
+  k_temporal<<<grid, block, 0, c->stream>>>(a);
 }
 
 void temporal_release(pt_context* c)
@@ -60,8 +68,10 @@ void temporal_release(pt_context* c)
     dev_free(c->dHistColour[s]);
     dev_free(c->dHistGuide[s]);
     dev_free(c->dHistLength[s]);
+    dev_free(c->dHistMoments[s]);
+    dev_free(c->dSvgfVar[s]);
   }
-  c->haveHistory = false;
+  c->haveHistory = c->histHasMoments = false;
 }
 
 // Everything pt_temporal_accumulate checks, then both history sets allocated and the row-major accumulation image enqueued on the context's stream
@@ -86,6 +96,10 @@ static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalPar
     if((rc = dev_alloc(c, c->dHistColour[s], sizeof(float4) * n)) != PT_OK || (rc = dev_alloc(c, c->dHistGuide[s], sizeof(float4) * n)) != PT_OK
        || (rc = dev_alloc(c, c->dHistLength[s], sizeof(float) * n)) != PT_OK)
       return rc;
+  if(c->trackMoments)
+    for(int s = 0; s < 2; ++s)
+      if((rc = dev_alloc(c, c->dHistMoments[s], sizeof(float2) * n)) != PT_OK)
+        return rc;
   if((rc = untile_to_rowmajor(c)) != PT_OK)
     return rc;
   const int r = c->histSet, wr = r ^ 1;
@@ -124,7 +138,7 @@ int pt_temporal_accumulate(pt_context* c, const pt_TemporalParams* p, float* out
   int    rc = prepare_temporal(c, "pt_temporal_accumulate", p, a);
   if(rc != PT_OK)
     return rc;
-  launch_temporal(c->stream, a);
+  launch_temporal(c, a);
   HIP_TRY(c, hipGetLastError());
   if(out)
     HIP_TRY(c, hipMemcpyAsync(out, a.hcOut, sizeof(float4) * size_t(c->width) * size_t(c->height), hipMemcpyDeviceToHost, c->stream));
@@ -135,14 +149,28 @@ int pt_temporal_accumulate(pt_context* c, const pt_TemporalParams* p, float* out
   for(int i = 0; i < 3; ++i)
     c->histEye[i] = c->scene.camera.viewInverse[12 + i];
   c->histSet ^= 1;
-  c->haveHistory = true;
+  c->haveHistory    = true;
+  c->histHasMoments = c->trackMoments;
   return check_traversal(c);
 }
 
 int pt_temporal_reset(pt_context* c)
 {
   CTX_CHECK(c);
-  c->haveHistory = false;  // the buffers stay for the next call; pt_resize and pt_destroy free them
+  c->haveHistory = c->histHasMoments = false;  // the buffers stay for the next call; pt_resize and pt_destroy free them
+  return PT_OK;
+}
+
+int pt_temporal_track_moments(pt_context* c, int on)
+{
+  CTX_CHECK(c);
+  if(on != 0 && on != 1)
+    return c->fail(PT_ERR_INVALID, "pt_temporal_track_moments: on must be 0 or 1");
+  if((on != 0) != c->trackMoments)
+  {
+    c->trackMoments = on != 0;
+    c->haveHistory = c->histHasMoments = false;  // a history without moments cannot be continued with them, and the other way round
+  }
   return PT_OK;
 }
 
@@ -180,10 +208,10 @@ __attribute__((visibility("default"))) int pt_debug_temporal_time(pt_context* c,
     (void)hipEventDestroy(ev[0]);
     return c->fail(PT_ERR_HIP, "pt_debug_temporal_time: hipEventCreate");
   }
-  launch_temporal(c->stream, a);
+  launch_temporal(c, a);  // (the kernel the setting of pt_temporal_track_moments selects)
   hipError_t e = hipEventRecord(ev[0], c->stream);
   for(int i = 0; i < reps && e == hipSuccess; ++i)
-    launch_temporal(c->stream, a);
+    launch_temporal(c, a);
   if(e == hipSuccess) e = hipGetLastError();
   if(e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
   if(e == hipSuccess) e = sync_all(c);

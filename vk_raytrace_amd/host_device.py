@@ -125,6 +125,13 @@ class TemporalParams(C.Structure):
     _fields_ = [("worldToClip", C.c_float * 16), ("depthTol", C.c_float), ("normalDist2", C.c_float), ("maxHistory", C.c_float), ("flags", C.c_uint32)]
 
 
+class SvgfParams(C.Structure):
+    """pt_SvgfParams (pt_svgf_variance, pt_svgf_history, pt_tonemap_svgf): the luminance stop is sigmaLum standard deviations of the estimated variance plus
+    lumFloor; sigmaGuide[j] is read for installed planes only; a history shorter than minTemporal estimates its variance spatially"""
+    _fields_ = [("iterations", C.c_int32), ("sigmaLum", C.c_float), ("lumFloor", C.c_float), ("sigmaGuide", C.c_float * 3), ("minTemporal", C.c_float),
+                ("flags", C.c_uint32)]
+
+
 class Peaks(C.Structure):
     """pt_Peaks (pt_measure_peaks): ceilings measured on the device"""
     _fields_ = [("valuWaveInstrPerSec", C.c_double), ("hbmCopyBytesPerSec", C.c_double), ("hbmReadBytesPerSec", C.c_double), ("computeUnits", C.c_int32),
@@ -152,6 +159,7 @@ assert C.sizeof(RtxState) == 48 and C.sizeof(SceneCamera) == 140 and C.sizeof(Ve
 assert C.sizeof(GltfShadeMaterial) == 216 and C.sizeof(Light) == 64 and C.sizeof(EnvAccel) == 16
 assert C.sizeof(Tonemapper) == 48 and C.sizeof(SunAndSky) == 96 and C.sizeof(PrimMesh) == 20 and C.sizeof(Node) == 68
 assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32 and C.sizeof(DenoiseParams) == 24 and C.sizeof(TemporalParams) == 80
+assert C.sizeof(SvgfParams) == 32
 
 vertex_dtype = np.dtype(VertexAttributes)
 ray_dtype = np.dtype(Ray)

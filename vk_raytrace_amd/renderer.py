@@ -330,6 +330,45 @@ class HipRenderer(Renderer):
         self._check(self._lib.pt_tonemap_history(self._ctx, None if params is None else C.byref(params), C.byref(tm), out.ctypes.data))
         return out
 
+    # -- variance-guided filter of the history (no reference counterpart) ------------------------------
+    @staticmethod
+    def svgf_params(iterations=5, sigma_lum=4.0, lum_floor=1.0e-4, sigma_guide=(1.0, 0.3, 0.5), min_temporal=4.0):
+        return hd.SvgfParams(iterations=iterations, sigmaLum=sigma_lum, lumFloor=lum_floor, sigmaGuide=tuple(float(v) for v in sigma_guide),
+                             minTemporal=min_temporal, flags=0)
+
+    def track_moments(self, on=True):
+        """pt_temporal_track_moments: the history also keeps the first two moments of the luminance; a change drops the history"""
+        self._check(self._lib.pt_temporal_track_moments(self._ctx, int(on)))
+
+    def read_temporal_moments(self):
+        """pt_read_temporal_moments: (H, W, 2) float32, (m1, m2)"""
+        w, h = self.size
+        out = np.empty((h, w, 2), np.float32)
+        self._check(self._lib.pt_read_temporal_moments(self._ctx, out.ctypes.data))
+        return out
+
+    def svgf_variance(self, params: hd.SvgfParams):
+        """pt_svgf_variance: the initial variance estimate of the history ((H, W) float32)"""
+        w, h = self.size
+        out = np.empty((h, w), np.float32)
+        self._check(self._lib.pt_svgf_variance(self._ctx, C.byref(params), out.ctypes.data))
+        return out
+
+    def svgf_history(self, params: hd.SvgfParams, variance=True):
+        """pt_svgf_history: (the filtered history (H, W, 4), the variance after the last iteration (H, W) or None with variance=False), float32"""
+        w, h = self.size
+        out = np.empty((h, w, 4), np.float32)
+        var = np.empty((h, w), np.float32) if variance else None
+        self._check(self._lib.pt_svgf_history(self._ctx, C.byref(params), out.ctypes.data, None if var is None else var.ctypes.data))
+        return out, var
+
+    def tonemap_svgf(self, params: hd.SvgfParams, tm: hd.Tonemapper):
+        """pt_tonemap_svgf: tonemap() of svgf_history()'s image"""
+        w, h = self.size
+        out = np.empty((h, w, 4), np.uint8)
+        self._check(self._lib.pt_tonemap_svgf(self._ctx, C.byref(params), C.byref(tm), out.ctypes.data))
+        return out
+
     def tonemap_begin(self, tm: hd.Tonemapper, display_size=None):
         """pt_tonemap_begin: the display pass enqueued behind the frames rendered so far; later frames overlap it.  tonemap_end() returns the
         oldest image begun (at most 4 may be pending)."""
