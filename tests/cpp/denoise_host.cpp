@@ -2,7 +2,7 @@
 // tests/denoise_host.py compiles and binds it; tests/test_denoise_model.py holds it to a float64 model, tests/test_denoise_gpu.py holds the device to it.
 #include <cstring>
 #include <vector>
-#include "pt_denoise.h"
+#include "stage/stage_host_common.h"
 
 extern "C" {
 
@@ -11,12 +11,9 @@ extern "C" {
 // Returns what denoise_constants returns (PT_OK, PT_ERR_INVALID, PT_ERR_STATE); nothing is written on an error.
 int dh_denoise(const float* colour, const float* const guides[PT_DENOISE_GUIDES], int w, int h, const pt_DenoiseParams* params, float* out, float* per_iteration_out)
 {
-  uint32_t set = 0;
-  for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
-    set |= guides && guides[j] ? 1u << j : 0u;
   DenoiseConst k;
   const char*  why = "";
-  const int    rc  = denoise_constants(params, set, &k, &why);
+  const int    rc  = denoise_constants(params, planes_of(guides), &k, &why);
   if(rc != PT_OK)
     return rc;
   if(!colour || !out || w <= 0 || h <= 0)

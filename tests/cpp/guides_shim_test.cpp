@@ -5,17 +5,14 @@
 #include <cstdio>
 #include <cstring>
 #include <vector>
-#include "pt_renderer.hpp"
+#include "stage/shim_common.h"
 
 int main()
 {
   ptmi::HipPathTracer r;
   r.setup(0);
   if(!r.ok())
-  {
-    std::printf("NO_DEVICE status=%d msg=%s\n", r.status(), r.lastError().c_str());
-    return r.status() == PT_ERR_NO_DEVICE ? 0 : 3;
-  }
+    return shim_no_device(r);
   const float pos[12] = {-1, -1, 0, 1, -1, 0, 1, 1, 0, -1, 1, 0}, nrm[12] = {0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 1};
   const float tan[16] = {1, 0, 0, 1, 1, 0, 0, 1, 1, 0, 0, 1, 1, 0, 0, 1}, uv[8] = {0, 0, 1, 0, 1, 1, 0, 1};
   float       col[16];
@@ -73,7 +70,7 @@ int main()
     }
     // the denoiser on the planes where the pass left them, and on the same planes installed by the caller
     std::vector<float> img(n), den0(n), den1(n);
-    for(size_t i = 0; i < n; ++i) img[i] = float((i * 37u) % 101u) / 50.f;
+    shim_image(img, 0);
     r.writeAccum(img.data());
     const pt_DenoiseParams p{3, 1.0f, {0.1f, 0.3f, 0.5f}, PT_DENOISE_DEMODULATE};
     if(!r.denoise(p, den0.data()) || !r.setDenoiseGuides(a.data(), nr.data(), d.data()) || !r.denoise(p, den1.data()) || std::memcmp(den0.data(), den1.data(), n * sizeof(float)) != 0)

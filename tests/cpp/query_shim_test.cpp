@@ -6,17 +6,14 @@
 #include <cstdio>
 #include <cstring>
 #include <vector>
-#include "pt_renderer.hpp"
+#include "stage/shim_common.h"
 
 int main()
 {
   ptmi::HipPathTracer r;
   r.setup(0);
   if(!r.ok())
-  {
-    std::printf("NO_DEVICE status=%d msg=%s\n", r.status(), r.lastError().c_str());
-    return r.status() == PT_ERR_NO_DEVICE ? 0 : 3;
-  }
+    return shim_no_device(r);
   const float pos[12] = {-1, -1, 0, 1, -1, 0, 1, 1, 0, -1, 1, 0}, nrm[12] = {0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 1};
   const float tan[16] = {1, 0, 0, 1, 1, 0, 0, 1, 1, 0, 0, 1, 1, 0, 0, 1}, uv[8] = {0, 0, 1, 0, 1, 1, 0, 1};
   float       col[16];

@@ -4,7 +4,7 @@
 #include <cstdio>
 #include <cstring>
 #include <vector>
-#include "pt_renderer.hpp"
+#include "stage/shim_common.h"
 
 int main(int argc, char** argv)
 {
@@ -13,10 +13,7 @@ int main(int argc, char** argv)
     return 2;
   r.setup(0);
   if(!r.ok())
-  {
-    std::printf("NO_DEVICE status=%d msg=%s\n", r.status(), r.lastError().c_str());
-    return r.status() == PT_ERR_NO_DEVICE ? 0 : 3;
-  }
+    return shim_no_device(r);
   const float pos[12] = {-1, -1, 0, 1, -1, 0, 1, 1, 0, -1, 1, 0}, nrm[12] = {0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 1};
   const float tan[16] = {1, 0, 0, 1, 1, 0, 0, 1, 1, 0, 0, 1, 1, 0, 0, 1}, uv[8] = {0, 0, 1, 0, 1, 1, 0, 1};
   float       col[16];
@@ -88,7 +85,7 @@ int main(int argc, char** argv)
     r.setAccelMode(PT_ACCEL_FLAT);
   }
   {  // the display pass with frames in flight (tonemapBegin / tonemapEnd) hands out the images of the synchronous pass
-    pt_Tonemapper        tm{1.f, 1.f, 1.f, 0.f, 1.f, 1.f, {1.f, 1.f}, 0, 0.5f, 0.5f, 1};
+    const pt_Tonemapper  tm = shim_tonemapper();
     std::vector<uint8_t> a(64 * 64 * 4), b(64 * 64 * 4), sync(64 * 64 * 4);
     r.setPushContants(st);
     r.run({64, 64});

@@ -3,15 +3,9 @@
 #include <cstring>
 #include <vector>
 #include "pt_svgf.h"
+#include "stage/stage_host_common.h"
 
 namespace {
-uint32_t planes_of(const float* const g[PT_DENOISE_GUIDES])
-{
-  uint32_t m = 0;
-  for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
-    m |= g && g[j] ? 1u << j : 0u;
-  return m;
-}
 SvRowMajor source(const float* colour, const float* const g[PT_DENOISE_GUIDES], const float* variance, const float* length, const float* moments, int w)
 {
   SvRowMajor s{};
@@ -41,19 +35,7 @@ int sh_temporal_m(const float* colour, const float* normal, const float* depth, 
   if(!colour || !normal || !depth || !view_inverse || !proj_inverse || !out_colour || !out_guide || !out_length || !out_moments || w <= 0 || h <= 0
      || (hist_colour && (!hist_guide || !hist_length || !hist_moments || !world_to_clip_h || !eye_h)))
     return PT_ERR_INVALID;
-  TemporalConst k;
-  std::memset(&k, 0, sizeof(k));
-  std::memcpy(k.viewInverse, view_inverse, sizeof(k.viewInverse));
-  std::memcpy(k.projInverse, proj_inverse, sizeof(k.projInverse));
-  if(hist_colour)
-  {
-    std::memcpy(k.worldToClipH, world_to_clip_h, sizeof(k.worldToClipH));
-    std::memcpy(k.eyeH, eye_h, sizeof(k.eyeH));
-  }
-  k.haveHistory = hist_colour ? 1 : 0;
-  k.depthTol    = params->depthTol;
-  k.normalDist2 = params->normalDist2;
-  k.maxHistory  = params->maxHistory;
+  const TemporalConst k = temporal_const(view_inverse, proj_inverse, hist_colour ? world_to_clip_h : nullptr, hist_colour ? eye_h : nullptr, params);
   const TpRowMajor src{(const DnPx*)colour, (const DnPx*)normal, (const DnPx*)depth, (const DnPx*)hist_colour, (const DnPx*)hist_guide, hist_length, w};
   const SvRowMajor msrc = source(nullptr, nullptr, nullptr, nullptr, hist_moments, w);
 #pragma omp parallel for schedule(static)
@@ -122,11 +104,7 @@ int sh_constants(const pt_SvgfParams* params, unsigned planes, char* why_out, in
   SvgfConst   k;
   const char* why = "";
   const int   rc  = svgf_constants(params, planes, &k, &why);
-  if(why_out && why_len > 0)
-  {
-    std::strncpy(why_out, why, size_t(why_len) - 1);
-    why_out[why_len - 1] = 0;
-  }
+  copy_why(why, why_out, why_len);
   return rc;
 }
 }

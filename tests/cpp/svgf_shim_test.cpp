@@ -5,26 +5,14 @@
 #include <cstdio>
 #include <cstring>
 #include <vector>
-#include "pt_renderer.hpp"
-
-static unsigned long long fnv(const void* p, size_t bytes)
-{
-  unsigned long long   h = 1469598103934665603ull;
-  const unsigned char* b = static_cast<const unsigned char*>(p);
-  for(size_t i = 0; i < bytes; ++i)
-    h = (h ^ b[i]) * 1099511628211ull;
-  return h;
-}
+#include "stage/shim_common.h"
 
 int main()
 {
   ptmi::HipPathTracer r;
   r.setup(0);
   if(!r.ok())
-  {
-    std::printf("NO_DEVICE status=%d msg=%s\n", r.status(), r.lastError().c_str());
-    return r.status() == PT_ERR_NO_DEVICE ? 0 : 3;
-  }
+    return shim_no_device(r);
   const int    W = 40, H = 24;
   const size_t n = size_t(W) * H;
   r.create({uint32_t(W), uint32_t(H)});
@@ -37,13 +25,7 @@ int main()
   }
   if(r.trackMoments(true) == false)
     return 5;
-  for(int y = 0; y < H; ++y)
-    for(int x = 0; x < W; ++x)
-    {
-      const size_t at = (size_t(y) * W + x) * 4;
-      normal[at] = 0.5f, normal[at + 1] = 0.5f, normal[at + 2] = 1.f, normal[at + 3] = 1.f;
-      depth[at] = 4.f + float((x * 3 + y * 5) % 16) * 0.125f;
-    }
+  shim_planes(W, H, normal, depth);
   if(!r.setDenoiseGuides(nullptr, normal.data(), depth.data()))
     return 6;
   const float       up[3] = {0, 1, 0}, eye[3] = {0, 0, 5}, center[3] = {0, 0, 0};
@@ -55,8 +37,7 @@ int main()
   r.setCamera(cam);
   for(int k = 0; k < 3; ++k)
   {
-    for(size_t i = 0; i < n * 4; ++i)
-      img[i] = float((i * (37u + 4u * unsigned(k))) % 101u) / 50.f;
+    shim_image(img, k);
     r.writeAccum(img.data());
     if(!r.temporalAccumulate(p))
     {
@@ -64,9 +45,7 @@ int main()
       return 8;
     }
   }
-  pt_Tonemapper tm{};
-  tm.brightness = 1.f, tm.contrast = 1.f, tm.saturation = 1.f, tm.vignette = 0.f, tm.avgLum = 1.f, tm.zoom = 1.f, tm.renderingRatio[0] = tm.renderingRatio[1] = 1.f;
-  tm.autoExposure = 0, tm.Ywhite = 0.5f, tm.key = 0.5f, tm.dither = 1;
+  const pt_Tonemapper tm = shim_tonemapper();
   std::vector<uint8_t> shown(n * 4);
   if(!r.readTemporalMoments(m.data()) || !r.svgfVariance(sp, v0.data()) || !r.svgfHistory(sp, filtered.data(), v.data()) || !r.tonemapSvgf(sp, tm, shown.data()))
   {

@@ -3,6 +3,7 @@
 #include <cstring>
 #include <vector>
 #include "pt_temporal.h"
+#include "stage/stage_host_common.h"
 
 namespace {
 // the constants of a call; hist_colour == NULL: no history
@@ -15,18 +16,7 @@ int make_const(const float* view_inverse, const float* proj_inverse, const pt_Te
     return rc;
   if(!view_inverse || !proj_inverse || (hist_colour && (!world_to_clip_h || !eye_h)))
     return PT_ERR_INVALID;
-  std::memset(&k, 0, sizeof(k));
-  std::memcpy(k.viewInverse, view_inverse, sizeof(k.viewInverse));
-  std::memcpy(k.projInverse, proj_inverse, sizeof(k.projInverse));
-  if(hist_colour)
-  {
-    std::memcpy(k.worldToClipH, world_to_clip_h, sizeof(k.worldToClipH));
-    std::memcpy(k.eyeH, eye_h, sizeof(k.eyeH));
-  }
-  k.haveHistory = hist_colour ? 1 : 0;
-  k.depthTol    = params->depthTol;
-  k.normalDist2 = params->normalDist2;
-  k.maxHistory  = params->maxHistory;
+  k = temporal_const(view_inverse, proj_inverse, hist_colour ? world_to_clip_h : nullptr, hist_colour ? eye_h : nullptr, params);
   return PT_OK;
 }
 }  // namespace
@@ -104,11 +94,7 @@ int th_temporal_constants(const pt_TemporalParams* params, char* why_out, int wh
 {
   const char* why = "";
   const int   rc  = temporal_constants(params, &why);
-  if(why_out && why_len > 0)
-  {
-    std::strncpy(why_out, why, size_t(why_len) - 1);
-    why_out[why_len - 1] = 0;
-  }
+  copy_why(why, why_out, why_len);
   return rc;
 }
 }

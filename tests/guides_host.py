@@ -1,57 +1,20 @@
-"""The host build of the guide pass (tests/cpp/guides_host.cpp: vk_raytrace_amd/csrc/pt_guides.h compiled by g++) and its Python side.  A library of
-its own with its own g++ call -- the compile flags are host_harness.build's -- cached under tests/cpp/_build/.  It works on the scene handle a
-host_harness.TracedScene (or Traced) holds, with the camera th_set_camera gave it.  A plain module: no test lives here."""
+"""The host build of the guide pass (tests/cpp/guides_host.cpp: vk_raytrace_amd/csrc/pt_guides.h compiled by g++) and its Python side.  The library is
+one of host_harness.build_library's, cached under tests/cpp/_build/.  It works on the scene handle a host_harness.TracedScene (or Traced) holds, with
+the camera th_set_camera gave it.  A plain module: no test lives here."""
 import ctypes as C
-import glob
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests import host_harness as hh
 from vk_raytrace_amd import host_device as hd
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
-BUILD_DIR = os.path.join(CPP, "_build")
-OUT = os.path.join(BUILD_DIR, "libguideshost.so")
-UNIT = os.path.join(CPP, "guides_host.cpp")
-COMPILE = ["-std=c++17", "-O2", "-fopenmp", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-DSTACK_LDS=24", "-Wno-attributes",
-           "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "vk_raytrace_amd", "csrc"), "-I" + os.path.join(ROOT, "include")]
-_lib = None
-
-
-def _sources():
-    """the unit, the harness headers it includes and every header of the product (the unit reaches most of them through pt_shade.h)"""
-    return [UNIT, os.path.abspath(__file__)] + glob.glob(os.path.join(CPP, "th_*.h")) + glob.glob(os.path.join(ROOT, "vk_raytrace_amd", "csrc", "*.h")) + \
-        glob.glob(os.path.join(ROOT, "include", "*.h"))
-
-
-def build():
-    """libguideshost.so, compiled if it is missing or older than a source it is made of; returns its path"""
-    if os.path.exists(OUT) and all(os.path.getmtime(s) <= os.path.getmtime(OUT) for s in _sources()):
-        return OUT
-    os.makedirs(BUILD_DIR, exist_ok=True)
-    fd, tmp = tempfile.mkstemp(suffix=".so", dir=BUILD_DIR)   # concurrent builders each write a file of their own; nobody loads a half-written one
-    os.close(fd)
-    try:
-        subprocess.check_call(["g++"] + COMPILE + ["-shared", "-o", tmp, UNIT])
-        os.replace(tmp, OUT)
-    finally:
-        if os.path.exists(tmp):
-            os.unlink(tmp)
-    return OUT
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        L = C.CDLL(build())
-        P = C.c_void_p
-        L.gh_guides.restype, L.gh_guides.argtypes = C.c_uint32, [P, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_float, P, P, P]
-        L.gh_rays.restype, L.gh_rays.argtypes = C.c_uint32, [P, C.c_int, C.c_int, P, P, P, P]
-        _lib = L
-    return _lib
+_P = C.c_void_p
+SIGNATURES = [
+    ("gh_guides", C.c_uint32, [_P, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_float, _P, _P, _P]),
+    ("gh_rays", C.c_uint32, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
+]
+_host = hh.StageLibrary("libguideshost", "guides_host.cpp", SIGNATURES)
+build, compile_to, bind, lib = _host.build, _host.compile_to, _host.bind, _host.lib
 
 
 def set_camera(traced, camera: hd.SceneCamera, sunsky=None):

@@ -1,7 +1,8 @@
 """The host harness of the trace source: the product's own headers (vk_raytrace_amd/csrc/pt_trace.h, pt_machine.h, pt_settle.h, pt_shade.h, pt_probe.h,
-pt_query.h) compiled for the host by g++ from the units under tests/cpp/, and its Python side -- the one build function, the one table of ctypes
-signatures, the scene wrappers (Traced, TracedScene, host_render) and the scenes and rays the host tests, the device tests that take the host build
-as their reference, and the CPU experiments under tools/ share.  A plain module: no test lives here."""
+pt_query.h) compiled for the host by g++ from the units under tests/cpp/, and its Python side -- the one build function (build_library, which the host
+builds of the display stages' headers go through as well: tests/denoise_host.py, guides_host.py, temporal_host.py, svgf_host.py), the one binder of
+ctypes signature tables, the scene wrappers (Traced, TracedScene, host_render) and the scenes and rays the host tests, the device tests that take the
+host build as their reference, and the CPU experiments under tools/ share.  A plain module: no test lives here."""
 import concurrent.futures
 import ctypes as C
 import json
@@ -23,6 +24,10 @@ OPAQUE, NOCULL = 1, 2
 MERGE_SINGLES, COMPACT_NODES = 1, 2   # the options word of th_create / th_create_scene (tests/cpp/th_scene.h)
 
 # ---- the build ---------------------------------------------------------------------------------------------------------------------------------------
+CSRC = os.path.join(ROOT, "vk_raytrace_amd", "csrc")
+# what every host build of a product header is compiled with: the device build's floating-point contract
+COMPILE = ["-std=c++17", "-O2", "-fopenmp", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-DSTACK_LDS=24", "-Wno-attributes",
+           "-I/opt/rocm/include", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
 UNITS = ["trace_host.cpp", "render_host.cpp", "probe_host.cpp", "query_host.cpp", "handover_host.cpp"]
 # flavour -> (extra compiler flags, extra units).  "" is what every test uses; the others carry the experiments of tools/ (tests/cpp/experiments/)
 FLAVOURS = {"": ([], []), "steps": ([], ["experiments/step_model.cpp"]), "robust": (["-DTH_ROBUST_T2"], ["experiments/t2_experiment.cpp"]),
@@ -42,21 +47,22 @@ def _project_deps(dfile):
     return sorted(os.path.relpath(p, root) for p in paths if p.startswith(root))
 
 
-def build(flavour=""):
-    """libtracehost[_<flavour>].so, compiled if it is missing or older than any project file the compiler read for it or than libptmi.so, or if
-    the recipe changed; returns its path.  The list of those files is kept next to it (<library>.json)."""
-    capi.lib()  # libptmi.so must exist: the harness links its host-side test hooks (device-builder emulation, two_level_pad, scene records)
-    flags, extra = FLAVOURS[flavour]
-    out = os.path.join(BUILD_DIR, "libtracehost%s.so" % ("_" + flavour if flavour else ""))
-    lib_dir = os.path.dirname(capi.LIB_PATH)
-    compile_args = ["-std=c++17", "-O2", "-fopenmp", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-DSTACK_LDS=24", "-Wno-attributes"] + flags + [
-        "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "vk_raytrace_amd", "csrc"), "-I" + os.path.join(ROOT, "include")]
-    link_args = ["-shared", "-fopenmp", "-L" + lib_dir, "-l:libptmi.so", "-Wl,-rpath," + lib_dir, "-Wl,-rpath,/opt/rocm/lib"]
-    recipe = {"units": UNITS + extra, "compile": compile_args, "link": link_args}
+def build_library(name, units, flags=(), needs_libptmi=False):
+    """tests/cpp/_build/<name>.so from the units (paths under tests/cpp/), compiled if it is missing or older than any project file the compiler read
+    for it, or if the recipe changed; returns its path.  The list of those files is kept next to it (<library>.json).  needs_libptmi: the library
+    links libptmi.so's host-side test hooks -- that must exist then, and a newer one rebuilds; without it nothing of the product need be built."""
+    out = os.path.join(BUILD_DIR, name + ".so")
+    compile_args, link_args, newer = COMPILE + list(flags), ["-shared", "-fopenmp"], []
+    if needs_libptmi:
+        capi.lib()
+        lib_dir = os.path.dirname(capi.LIB_PATH)
+        link_args += ["-L" + lib_dir, "-l:libptmi.so", "-Wl,-rpath," + lib_dir, "-Wl,-rpath,/opt/rocm/lib"]
+        newer = [capi.LIB_PATH]
+    recipe = {"units": list(units), "compile": compile_args, "link": link_args}
     try:
         stamp = json.load(open(out + ".json"))
         built = os.path.getmtime(out)
-        if stamp["recipe"] == recipe and all(os.path.getmtime(os.path.join(ROOT, d)) <= built for d in stamp["deps"]) and os.path.getmtime(capi.LIB_PATH) <= built:
+        if stamp["recipe"] == recipe and all(os.path.getmtime(f) <= built for f in [os.path.join(ROOT, d) for d in stamp["deps"]] + newer):
             return out
     except (OSError, ValueError, KeyError):
         pass
@@ -77,9 +83,57 @@ def build(flavour=""):
     return out
 
 
-def deps(flavour=""):
-    """the project files build() recorded for the library, relative to the repository's root"""
-    return json.load(open(build(flavour) + ".json"))["deps"]
+def compile_to(out, unit, header_dir):
+    """The one-unit library `out` with `header_dir` searched before csrc/ (a scratch copy of a header with a planted break); no cache, no record"""
+    _gxx(["-I" + header_dir] + COMPILE + ["-shared", "-o", out, os.path.join(CPP, unit)])
+    return out
+
+
+def build(flavour=""):
+    """libtracehost[_<flavour>].so (build_library); it links libptmi.so: the device-builder emulation, two_level_pad, the scene records"""
+    flags, extra = FLAVOURS[flavour]
+    return build_library("libtracehost" + ("_" + flavour if flavour else ""), UNITS + extra, flags, needs_libptmi=True)
+
+
+def bind(path, signatures):
+    """the library at `path` with every (name, restype, argtypes) of the table applied; a name that does not resolve is an error"""
+    L = C.CDLL(path)
+    for name, restype, argtypes in signatures:
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
+class StageLibrary:
+    """the host build of one stage header: a one-unit library that needs no libptmi.so, and its signature table"""
+    def __init__(self, name, unit, signatures):
+        self.name, self.unit, self.signatures, self._lib = name, unit, signatures, None
+
+    def build(self):
+        return build_library(self.name, [self.unit])
+
+    def compile_to(self, out, header_dir):
+        return compile_to(out, self.unit, header_dir)
+
+    def bind(self, path):
+        return bind(path, self.signatures)
+
+    def lib(self):
+        if self._lib is None:
+            self._lib = self.bind(self.build())
+        return self._lib
+
+
+def planes_arg(guides, h, w):
+    """three guide planes (None: not installed) as the host builds take them: (the arrays to keep alive, a void*[3])"""
+    keep = [None if g is None else np.ascontiguousarray(g, np.float32) for g in (guides or (None, None, None))]
+    assert len(keep) == 3 and all(g is None or g.shape == (h, w, 4) for g in keep)
+    return keep, (C.c_void_p * 3)(*[None if g is None else g.ctypes.data for g in keep])
+
+
+def deps(path=None):
+    """the project files build_library recorded for the library at `path` (None: the trace library, built if need be), relative to the repository's root"""
+    return json.load(open((path or build()) + ".json"))["deps"]
 
 
 # ---- the entry points: (name, restype, argtypes) -----------------------------------------------------------------------------------------------------
@@ -126,13 +180,9 @@ _libs = {}
 
 
 def lib(flavour=""):
-    """the library of that flavour, built if need be, with every signature of the table applied; a name that does not resolve is an error"""
+    """the library of that flavour, built if need be, with every signature of the table applied"""
     if flavour not in _libs:
-        L = C.CDLL(build(flavour))
-        for name, restype, argtypes in SIGNATURES + EXPERIMENT_SIGNATURES.get(flavour, []):
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _libs[flavour] = L
+        _libs[flavour] = bind(build(flavour), SIGNATURES + EXPERIMENT_SIGNATURES.get(flavour, []))
     return _libs[flavour]
 
 

@@ -1,63 +1,23 @@
-"""The host build of the variance-guided filter (tests/cpp/svgf_host.cpp: vk_raytrace_amd/csrc/pt_svgf.h compiled by g++) and its Python side.  A
-library of its own with its own g++ call -- the compile flags are temporal_host's -- cached under tests/cpp/_build/.  A plain module: no test lives
-here."""
+"""The host build of the variance-guided filter (tests/cpp/svgf_host.cpp: vk_raytrace_amd/csrc/pt_svgf.h compiled by g++) and its Python side.  The
+library is one of host_harness.build_library's, cached under tests/cpp/_build/; it needs no libptmi.so.  A plain module: no test lives here."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from tests import temporal_host as th
+from tests import host_harness as hh, temporal_host as th
 from vk_raytrace_amd import host_device as hd
 
-ROOT, CPP, CSRC, BUILD_DIR = th.ROOT, th.CPP, th.CSRC, th.BUILD_DIR
-OUT = os.path.join(BUILD_DIR, "libsvgfhost.so")
-SOURCES = [os.path.join(CPP, "svgf_host.cpp"), os.path.join(CSRC, "pt_svgf.h")] + th.SOURCES[1:]
-COMPILE = th.COMPILE
-_lib = None
-
-
-def compile_to(out, header_dir=None):
-    """g++ of svgf_host.cpp to `out`; header_dir: a directory searched before csrc/ (a scratch copy of pt_svgf.h with a planted break)"""
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    fd, tmp = tempfile.mkstemp(suffix=".so", dir=os.path.dirname(out))   # concurrent builders each write a file of their own; nobody loads a half-written one
-    os.close(fd)
-    try:
-        subprocess.check_call(["g++"] + ([] if header_dir is None else ["-I" + header_dir]) + COMPILE + ["-shared", "-o", tmp, SOURCES[0]])
-        os.replace(tmp, out)
-    finally:
-        if os.path.exists(tmp):
-            os.unlink(tmp)
-    return out
-
-
-def build():
-    """libsvgfhost.so, compiled if it is missing or older than a source it is made of; returns its path"""
-    if os.path.exists(OUT) and all(os.path.getmtime(s) <= os.path.getmtime(OUT) for s in SOURCES + [os.path.abspath(__file__)]):
-        return OUT
-    return compile_to(OUT)
-
-
+CSRC = hh.CSRC
 _P = C.c_void_p
 _G = C.POINTER(_P)
-
-
-def bind(path):
-    L = C.CDLL(path)
-    L.sh_temporal_m.restype = C.c_int
-    L.sh_temporal_m.argtypes = [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(hd.TemporalParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]
-    L.sh_variance.restype, L.sh_variance.argtypes = C.c_int, [_P, _P, _P, _G, C.c_int, C.c_int, C.POINTER(hd.SvgfParams), _P]
-    L.sh_iteration.restype, L.sh_iteration.argtypes = C.c_int, [_P, _P, _G, C.c_int, C.c_int, C.POINTER(hd.SvgfParams), C.c_int, _P, _P]
-    L.sh_constants.restype, L.sh_constants.argtypes = C.c_int, [C.POINTER(hd.SvgfParams), C.c_uint, C.c_char_p, C.c_int]
-    return L
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        _lib = bind(build())
-    return _lib
+SIGNATURES = [
+    ("sh_temporal_m", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(hd.TemporalParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("sh_variance", C.c_int, [_P, _P, _P, _G, C.c_int, C.c_int, C.POINTER(hd.SvgfParams), _P]),
+    ("sh_iteration", C.c_int, [_P, _P, _G, C.c_int, C.c_int, C.POINTER(hd.SvgfParams), C.c_int, _P, _P]),
+    ("sh_constants", C.c_int, [C.POINTER(hd.SvgfParams), C.c_uint, C.c_char_p, C.c_int]),
+]
+_host = hh.StageLibrary("libsvgfhost", "svgf_host.cpp", SIGNATURES)
+build, compile_to, bind, lib = _host.build, _host.compile_to, _host.bind, _host.lib
 
 
 def params(iterations, sigma_lum=4.0, lum_floor=1e-4, sigma_guide=(1.0, 1.0, 1.0), min_temporal=3.5, flags=0):
@@ -72,12 +32,6 @@ class History(th.History):
     def __init__(self, colour, guide, length, moments, world_to_clip, eye):
         super().__init__(colour, guide, length, world_to_clip, eye)
         self.moments = moments
-
-
-def _planes(guides, h, w):
-    keep = [None if g is None else np.ascontiguousarray(g, np.float32) for g in (guides or (None, None, None))]
-    assert len(keep) == 3 and all(g is None or g.shape == (h, w, 4) for g in keep)
-    return keep, (_P * 3)(*[None if g is None else g.ctypes.data for g in keep])
 
 
 def temporal_m(colour, normal, depth, view_inverse, proj_inverse, p, hist=None, L=None):
@@ -102,7 +56,7 @@ def variance(hist_colour, hist_length, hist_moments, guides, p, L=None):
     hc, hn, hm = (np.ascontiguousarray(a, np.float32) for a in (hist_colour, hist_length, hist_moments))
     h, w = hn.shape
     assert hc.shape == (h, w, 4) and hm.shape == (h, w, 2)
-    keep, ptrs = _planes(guides, h, w)
+    keep, ptrs = hh.planes_arg(guides, h, w)
     out = np.empty((h, w), np.float32)
     rc = (L or lib()).sh_variance(hc.ctypes.data, hn.ctypes.data, hm.ctypes.data, ptrs, w, h, C.byref(p), out.ctypes.data)
     return rc, (out if rc == 0 else None)
@@ -113,7 +67,7 @@ def iteration(colour, var, guides, p, i, L=None):
     c, v = np.ascontiguousarray(colour, np.float32), np.ascontiguousarray(var, np.float32)
     h, w = v.shape
     assert c.shape == (h, w, 4)
-    keep, ptrs = _planes(guides, h, w)
+    keep, ptrs = hh.planes_arg(guides, h, w)
     oc, ov = np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32)
     rc = (L or lib()).sh_iteration(c.ctypes.data, v.ctypes.data, ptrs, w, h, C.byref(p), i, oc.ctypes.data, ov.ctypes.data)
     return (rc, oc, ov) if rc == 0 else (rc, None, None)

@@ -1,69 +1,25 @@
-"""The host build of the temporal stage (tests/cpp/temporal_host.cpp: vk_raytrace_amd/csrc/pt_temporal.h compiled by g++) and its Python side.  A
-library of its own with its own g++ call -- the compile flags are denoise_host's -- cached under tests/cpp/_build/.  A plain module: no test lives
-here."""
+"""The host build of the temporal stage (tests/cpp/temporal_host.cpp: vk_raytrace_amd/csrc/pt_temporal.h compiled by g++) and its Python side.  The
+library is one of host_harness.build_library's, cached under tests/cpp/_build/; it needs no libptmi.so.  A plain module: no test lives here."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests import host_harness as hh
 from vk_raytrace_amd import host_device as hd
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
-CSRC = os.path.join(ROOT, "vk_raytrace_amd", "csrc")
-BUILD_DIR = os.path.join(CPP, "_build")
-OUT = os.path.join(BUILD_DIR, "libtemporalhost.so")
-SOURCES = [os.path.join(CPP, "temporal_host.cpp"), os.path.join(CSRC, "pt_temporal.h"), os.path.join(CSRC, "pt_denoise.h"), os.path.join(ROOT, "include", "pt_fpmath.h"),
-           os.path.join(ROOT, "include", "pt_types.h"), os.path.join(ROOT, "include", "pt_api.h")]
-COMPILE = ["-std=c++17", "-O2", "-fopenmp", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-DSTACK_LDS=24", "-Wno-attributes",
-           "-I/opt/rocm/include", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
-_lib = None
-
+CSRC, COMPILE = hh.CSRC, hh.COMPILE   # where the header lies and what it is compiled with, for the tests that plant a break in a scratch copy
+_P = C.c_void_p
+_CALL = [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(hd.TemporalParams), _P, _P, _P, _P, _P]
+SIGNATURES = [
+    ("th_temporal", C.c_int, _CALL + [_P, _P, _P]),
+    ("th_temporal_probe", C.c_int, _CALL + [_P, _P, _P, _P, _P, _P]),
+    ("th_temporal_constants", C.c_int, [C.POINTER(hd.TemporalParams), C.c_char_p, C.c_int]),
+]
 # TemporalProbe::verdict and the outcomes of step 4 (csrc/pt_temporal.h)
 COUNTED, OUTSIDE, TOO_SHORT, NOT_FINITE, DEPTH, NORMAL = 1, 2, 3, 4, 5, 6
 BLEND, HISTORY_ONLY, CURRENT, NOTHING = 0, 1, 2, 3
-
-
-def compile_to(out, header_dir=None):
-    """g++ of temporal_host.cpp to `out`; header_dir: a directory searched before csrc/ (a scratch copy of pt_temporal.h with a planted break)"""
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    fd, tmp = tempfile.mkstemp(suffix=".so", dir=os.path.dirname(out))   # concurrent builders each write a file of their own; nobody loads a half-written one
-    os.close(fd)
-    try:
-        subprocess.check_call(["g++"] + ([] if header_dir is None else ["-I" + header_dir]) + COMPILE + ["-shared", "-o", tmp, SOURCES[0]])
-        os.replace(tmp, out)
-    finally:
-        if os.path.exists(tmp):
-            os.unlink(tmp)
-    return out
-
-
-def build():
-    """libtemporalhost.so, compiled if it is missing or older than a source it is made of; returns its path"""
-    if os.path.exists(OUT) and all(os.path.getmtime(s) <= os.path.getmtime(OUT) for s in SOURCES + [os.path.abspath(__file__)]):
-        return OUT
-    return compile_to(OUT)
-
-
-_P = C.c_void_p
-_CALL = [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(hd.TemporalParams), _P, _P, _P, _P, _P]
-
-
-def bind(path):
-    L = C.CDLL(path)
-    L.th_temporal.restype, L.th_temporal.argtypes = C.c_int, _CALL + [_P, _P, _P]
-    L.th_temporal_probe.restype, L.th_temporal_probe.argtypes = C.c_int, _CALL + [_P, _P, _P, _P, _P, _P]
-    L.th_temporal_constants.restype, L.th_temporal_constants.argtypes = C.c_int, [C.POINTER(hd.TemporalParams), C.c_char_p, C.c_int]
-    return L
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        _lib = bind(build())
-    return _lib
+_host = hh.StageLibrary("libtemporalhost", "temporal_host.cpp", SIGNATURES)
+build, compile_to, bind, lib = _host.build, _host.compile_to, _host.bind, _host.lib
 
 
 def params(world_to_clip, depth_tol, normal_dist2, max_history, flags=0):

@@ -338,6 +338,7 @@ def test_refusals():
 # ---- C++ shim ---------------------------------------------------------------------------------------------------------------------------------------
 def test_cpp_shim_traces_rays(tmp_path):
     """include/pt_renderer.hpp traceRays / traceRaysDevice (device memory from hipMalloc), tests/cpp/query_shim_test.cpp"""
+    from tests import shim
     from tests.test_query_host import build_query_shim
-    out = subprocess.run([build_query_shim(tmp_path)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout + out.stderr
+    verdict, _ = shim.run(build_query_shim(tmp_path))
+    assert verdict == "OK"

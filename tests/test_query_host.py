@@ -8,17 +8,15 @@ already has:
 
 Scenes, rays and rules are the harness's, the ones tests/test_trace_host.py uses.  tests/test_query_gpu.py runs the same rays through the C ABI on the device and compares them, record
 by record, with what this harness returns (the helpers below are shared with it)."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import shim
 from tests.host_harness import NONE, NOCULL, OPAQUE, Traced, TracedScene, accidental_differences, alpha_scenes, instanced_scene, rays_for, scene_rays
 from vk_raytrace_amd import capi, host_device as hd
 from vk_raytrace_amd.scene import Scene, translate, rotate_y
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLOSEST, OCCLUDED, NEAREST, CANDIDATES = capi.PT_RAYS_CLOSEST, capi.PT_RAYS_OCCLUDED, capi.PT_RAYS_NEAREST, capi.PT_RAYS_CANDIDATES
 HIT, INVALID = capi.PT_RAY_HIT, capi.PT_RAY_INVALID
 INF = np.float32(1e32)  # PT_INFINITY: what th_candidates / th_settle take for "unbounded"
@@ -292,15 +290,10 @@ def test_sixteen_results_for_a_ray_with_three_candidates():
 
 # ---- C++ shim -----------------------------------------------------------------------------------------------------------------------------------
 def build_query_shim(tmp_path):
-    exe = str(tmp_path / "query_shim_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__=1", "-I/opt/rocm/include", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "query_shim_test.cpp"),
-                           "-L", os.path.join(ROOT, "vk_raytrace_amd"), "-l:libptmi.so", "-Wl,-rpath," + os.path.join(ROOT, "vk_raytrace_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-o", exe])
-    return exe
+    return shim.build_shim(tmp_path, "query_shim_test", ("-D__HIP_PLATFORM_AMD__=1", "-I/opt/rocm/include"))   # (the program calls hipMalloc itself)
 
 
 def test_cpp_shim_with_ray_queries_builds_and_fails_loudly_without_gpu(tmp_path):
     """in the style of tests/test_cpp_shim.py: the shim's traceRays / traceRaysDevice compile against the C ABI and link; without a device setup() says so"""
-    out = subprocess.run([build_query_shim(tmp_path)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.startswith("NO_DEVICE") or out.stdout.startswith("OK")
+    verdict, _ = shim.run(build_query_shim(tmp_path))   # (exit status 0)
+    assert verdict in ("NO_DEVICE", "OK")

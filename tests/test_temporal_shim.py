@@ -1,34 +1,16 @@
 """The temporal stage through the header-only C++ shim (include/pt_renderer.hpp temporalAccumulate / readTemporalHistory / denoiseHistory /
 tonemapHistory, tests/cpp/temporal_shim_test.cpp): it compiles against the C ABI, links with libptmi.so, and either runs one round whose checksums
 equal those of the same round through the Python route (GPU box) or fails loudly with PT_ERR_NO_DEVICE."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build_temporal_shim(tmp_path):
-    exe = str(tmp_path / "temporal_shim_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "temporal_shim_test.cpp"),
-                           "-L", os.path.join(ROOT, "vk_raytrace_amd"), "-l:libptmi.so", "-Wl,-rpath," + os.path.join(ROOT, "vk_raytrace_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-o", exe])
-    return exe
+from tests import shim
+from tests.shim import fnv
 
 
 def test_cpp_shim_with_the_temporal_stage_builds_and_fails_loudly_without_gpu(tmp_path):
-    out = subprocess.run([build_temporal_shim(tmp_path)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.startswith("NO_DEVICE") or out.stdout.startswith("OK")
-
-
-def fnv(a):
-    h = 1469598103934665603
-    for b in np.ascontiguousarray(a).tobytes():
-        h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return f"{h:016x}"
+    verdict, _ = shim.run(shim.build_shim(tmp_path, "temporal_shim_test"))   # (exit status 0)
+    assert verdict in ("NO_DEVICE", "OK")
 
 
 def python_route():
@@ -39,23 +21,17 @@ def python_route():
     from vk_raytrace_amd.scene import Camera
     w, h = 40, 24
     aspect = float(np.float32(w) / np.float32(h))
-    ys, xs = np.mgrid[0:h, 0:w]
-    normal = np.zeros((h, w, 4), np.float32)
-    normal[...] = (0.5, 0.5, 1.0, 1.0)
-    depth = np.zeros((h, w, 4), np.float32)
-    depth[..., 0] = np.float32(4.0) + ((xs * 3 + ys * 5) % 16).astype(np.float32) * np.float32(0.125)
+    normal, depth = shim.planes(w, h)
     r = HipRenderer()
     r.setup(0)
     try:
         r.create((w, h))
         r.set_denoise_guides(None, normal, depth)
-        i = np.arange(w * h * 4, dtype=np.uint64)
         for k in range(2):
             x = float(np.float32(0.05) * np.float32(k))
             cam = Camera(eye=(x, 0, 5), center=(x, 0, 0), up=(0, 1, 0), fov=60.0)
             r.set_camera(capi.camera_lookat(cam, aspect))
-            img = (((i * np.uint64(37 + 4 * k)) % np.uint64(101)).astype(np.float32) / np.float32(50.0)).reshape(h, w, 4)
-            r.write_accum(img)
+            r.write_accum(shim.image(w, h, k))
             out = r.temporal_accumulate(r.temporal_params(r.world_to_clip(cam, aspect), 0.05, 0.05, 8.0))
         hc, hn = r.read_temporal_history()
         assert np.array_equal(hc.view(np.uint32), out.view(np.uint32))
@@ -67,7 +43,6 @@ def python_route():
 
 @pytest.mark.gpu
 def test_cpp_shim_round_equals_the_python_route(tmp_path):
-    out = subprocess.run([build_temporal_shim(tmp_path)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout + out.stderr
-    got = dict(kv.split("=") for kv in out.stdout.split()[1:])
+    verdict, got = shim.run(shim.build_shim(tmp_path, "temporal_shim_test"))
+    assert verdict == "OK"
     assert got == python_route()

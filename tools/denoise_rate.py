@@ -18,11 +18,10 @@ import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from vk_raytrace_amd import capi, host_device as hd  # noqa: E402
-from vk_raytrace_amd.renderer import HipRenderer  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from rate_common import ROUNDS, HipRenderer, capi, hd, rounds, stage_ms  # noqa: E402
 
-W, H, ITERATIONS, REPS, ROUNDS = 1920, 1080, 5, 50, 3
+W, H, ITERATIONS = 1920, 1080, 5
 
 
 def inputs(rng):
@@ -40,9 +39,7 @@ def inputs(rng):
 
 
 def filter_ms(r, p):
-    ms = C.c_float()
-    r._check(capi.lib().pt_debug_denoise_time(r._ctx, C.byref(p), REPS, C.byref(ms)))
-    return ms.value
+    return stage_ms(r, "pt_debug_denoise_time", C.byref(p))
 
 
 def main():
@@ -68,7 +65,7 @@ def main():
         s1, s2, full, dem = med[(lds, 1, 0)], med[(lds, 2, 0)] - med[(lds, 1, 0)], med[(lds, ITERATIONS, 0)], med[(lds, ITERATIONS, 1)]
         print(f"LDS up to step {lds}: step 1 {s1:.3f} ms, step 2 {s2:.3f} ms, {ITERATIONS} iterations {full:.3f} ms ({full / ITERATIONS:.3f} ms each, "
               f"{min_bytes / (full / ITERATIONS * 1e-3) / copy_rate:.3f} of the copy rate at {min_bytes / 1e6:.0f} MB least traffic each), with demodulation {dem:.3f} ms"
-              f"   [rounds: {' '.join(f'{x:.3f}' for x in table[(lds, ITERATIONS, 0)])}]")
+              f"   {rounds(table[(lds, ITERATIONS, 0)])}")
     capi.lib().pt_debug_denoise_lds(r._ctx, -1)
     p = hd.DenoiseParams(iterations=ITERATIONS, sigmaColor=1.0, sigmaGuide=(0.1, 0.3, 0.5), flags=0)
     print(f"default choice: {ITERATIONS} iterations {filter_ms(r, p):.3f} ms")

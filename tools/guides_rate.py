@@ -10,42 +10,24 @@ replaces and against the HBM streaming rate measured in the same run:
 (d) for scale: one frame-0, 1 spp, maxDepth = 1 pt_render_frame with pt_synchronize, host clock, median of 10.
 (e) pt_measure_peaks of the same run.  The traffic floor of the pass is one 48-byte write per pixel (the three planes) plus whatever the traversal and
     the hit's vertex, material and texture reads cost; the write alone is priced at the float4 copy rate.  A measurement, not a threshold."""
-import ctypes as C
 import os
 import statistics
 import sys
-import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from vk_raytrace_amd import capi, host_device as hd, workloads  # noqa: E402
-from vk_raytrace_amd.renderer import HipRenderer  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from rate_common import ROUNDS, HipRenderer, c3_workload, capi, hd, host_ms, rounds, stage_ms  # noqa: E402
 
-W, H, REPS, ROUNDS = 1920, 1080, 50, 3
+W, H = 1920, 1080
 MASKS = ((7, "all three planes"), (capi.PT_GUIDES_BASECOLOR, "base colour"), (capi.PT_GUIDES_NORMAL, "normal"), (capi.PT_GUIDES_DEPTH, "depth"))
 
 
 def pass_ms(r, planes):
-    ms = C.c_float()
-    r._check(capi.lib().pt_debug_guides_time(r._ctx, planes, 1.0e30, REPS, C.byref(ms)))
-    return ms.value
-
-
-def host_ms(fn, n=10):
-    fn()
-    out = []
-    for _ in range(n):
-        t0 = time.perf_counter()
-        fn()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(out), min(out), max(out)
+    return stage_ms(r, "pt_debug_guides_time", planes, 1.0e30)
 
 
 def main():
     pass_only = "--pass-only" in sys.argv[1:]
-    wl = workloads.c3_sponza(W, H, 1)
-    if wl.scene.vertices is None:
-        wl.scene.finalize(capi.pack_vertices)
-    print(f"{wl.name}; library {os.path.relpath(capi.LIB_PATH, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))}")
+    wl = c3_workload(W, H)
     # every prim-mesh of the stand-in is instantiated once: by default the two-level structure is the merged world-space one and the FLAT kernel
     # walks it; PT_TUNE mergeSingles=0 gives every prim-mesh its own object-space BLAS, which the two-level kernel walks
     for accel, tune, what in ((capi.PT_ACCEL_FLAT, None, "flat"), (capi.PT_ACCEL_TWO_LEVEL, None, "two-level (merged: flat kernel)"),
@@ -67,7 +49,7 @@ def main():
                 table.setdefault(planes, []).append(pass_ms(r, planes))
         for planes, name in MASKS:
             v = table[planes]
-            print(f"{what}: pt_render_guides({planes}) {name}: {statistics.median(v):.3f} ms   [rounds: {' '.join(f'{x:.3f}' for x in v)}]")
+            print(f"{what}: pt_render_guides({planes}) {name}: {statistics.median(v):.3f} ms   {rounds(v)}")
         if pass_only:
             r.destroy()
             continue

@@ -20,59 +20,26 @@ import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from temporal_rate import MISS_DEPTH, moved  # noqa: E402
-from vk_raytrace_amd import capi, host_device as hd, workloads  # noqa: E402
-from vk_raytrace_amd.renderer import HipRenderer  # noqa: E402
+from rate_common import ROUNDS, c3_renderer, frame_at, hd, med, moved, stage_ms  # noqa: E402
 
-W, H, REPS, ROUNDS, ITERATIONS = 1920, 1080, 50, 3, 5
+W, H, ITERATIONS = 1920, 1080, 5
 SVGF_BYTES, DENOISE_BYTES = 88, 80
 SIGMA_GUIDE = (1.0, 0.3, 0.5)
 
 
-def med(v):
-    return f"{statistics.median(v):.3f} ms [rounds: {' '.join(f'{x:.3f}' for x in v)}]"
-
-
 def main():
-    L = capi.lib()
-    wl = workloads.c3_sponza(W, H, 1)
-    if wl.scene.vertices is None:
-        wl.scene.finalize(capi.pack_vertices)
-    print(f"{wl.name}; library {os.path.relpath(capi.LIB_PATH, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))}")
-    r = HipRenderer()
-    r.setup(0)
-    r.set_scene(wl.scene)
-    integral, _ = r.set_env(wl.env)
-    r.set_sunsky(hd.default_sun_and_sky())
-    r.create((W, H))
-    st = hd.default_rtx_state()
-    st.size[0], st.size[1] = W, H
-    st.maxDepth, st.pbrMode, st.fireflyClampThreshold, st.frame = wl.depth, wl.pbr_mode, 4.0 * integral, 0
-
-    def frame_at(cam):
-        r.set_camera(capi.camera_lookat(cam, W / H, nb_lights=len(wl.scene.lights)))
-        r.capture_guides(7, MISS_DEPTH)
-        r.setPushContants(st)
-        r.run()
-        return r.temporal_params(r.world_to_clip(cam, W / H), 0.05, 0.05, 32.0)
+    wl, r, st = c3_renderer(W, H)
+    L = r._lib
 
     def temporal_ms(p):
-        ms = C.c_float()
-        r._check(L.pt_debug_temporal_time(r._ctx, C.byref(p), REPS, C.byref(ms)))
-        return ms.value
+        return stage_ms(r, "pt_debug_temporal_time", C.byref(p))
 
     def svgf_ms(sp, what):
-        ms = C.c_float()
-        r._check(L.pt_debug_svgf_time(r._ctx, C.byref(sp), what, REPS, C.byref(ms)))
-        return ms.value
+        return stage_ms(r, "pt_debug_svgf_time", C.byref(sp), what)
 
     def denoise_ms(n):
-        ms = C.c_float()
-        dp = hd.DenoiseParams(iterations=n, sigmaColor=1.0, sigmaGuide=SIGMA_GUIDE, flags=0)
-        r._check(L.pt_debug_denoise_time(r._ctx, C.byref(dp), REPS, C.byref(ms)))
-        return ms.value
+        return stage_ms(r, "pt_debug_denoise_time", C.byref(hd.DenoiseParams(iterations=n, sigmaColor=1.0, sigmaGuide=SIGMA_GUIDE, flags=0)))
 
     cam_a, cam_b = wl.scene.camera, moved(wl.scene.camera)
     t = {}
@@ -89,17 +56,17 @@ def main():
         # the temporal kernel after the move, tracking off and on
         for on in (False, True):
             r.track_moments(on)
-            r.temporal_accumulate(frame_at(cam_a), read=False)
-            t.setdefault("k_temporal_m" if on else "k_temporal", []).append(temporal_ms(frame_at(cam_b)))
+            r.temporal_accumulate(frame_at(r, wl, st, cam_a), read=False)
+            t.setdefault("k_temporal_m" if on else "k_temporal", []).append(temporal_ms(frame_at(r, wl, st, cam_b)))
         # tracking is on: a first call (lengths 1), judged short by minTemporal 4 and long by minTemporal 1
         r.temporal_reset()
-        p_a = frame_at(cam_a)
+        p_a = frame_at(r, wl, st, cam_a)
         r.temporal_accumulate(p_a, read=False)
         variance_ms("variance short", r.svgf_params(ITERATIONS, sigma_guide=SIGMA_GUIDE, min_temporal=4.0))
         variance_ms("variance long", r.svgf_params(ITERATIONS, sigma_guide=SIGMA_GUIDE, min_temporal=1.0))
         for _ in range(3):
             r.temporal_accumulate(p_a, read=False)
-        r.temporal_accumulate(frame_at(cam_b), read=False)
+        r.temporal_accumulate(frame_at(r, wl, st, cam_b), read=False)
         sp = r.svgf_params(ITERATIONS, sigma_guide=SIGMA_GUIDE, min_temporal=4.0)
         variance_ms("variance moved", sp)
         long_share = float((r.read_temporal_history()[1] >= 4.0).mean())

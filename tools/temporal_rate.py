@@ -18,86 +18,33 @@ import ctypes as C
 import os
 import statistics
 import sys
-import time
 
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from rate_common import ROUNDS, c3_renderer, frame_at, host_ms, moved, rounds, stage_ms  # noqa: E402
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from vk_raytrace_amd import capi, host_device as hd, workloads  # noqa: E402
-from vk_raytrace_amd.renderer import HipRenderer  # noqa: E402
-from vk_raytrace_amd.scene import Camera  # noqa: E402
-
-W, H, REPS, ROUNDS = 1920, 1080, 50, 3
-MISS_DEPTH = 1.0e4   # finite and far below 1e18: the sky keeps its history under rotation
+W, H = 1920, 1080
 FLOOR_BYTES = 136    # per pixel: the floor the stage was specified against
 KERNEL_BYTES = 120   # ... what k_temporal must move: 48 read (colour, normal, depth planes) + 36 read (history) + 36 written
 
 
-def moved(cam):
-    """the workload's camera after a dolly of 5 % of its focus distance, a strafe of half that and a yaw of 2 degrees"""
-    eye, center = np.array(cam.eye, np.float64), np.array(cam.center, np.float64)
-    fwd = center - eye
-    dist = np.linalg.norm(fwd)
-    fwd /= dist
-    right = np.cross(fwd, np.array(cam.up, np.float64))
-    right /= np.linalg.norm(right)
-    eye2 = eye + 0.05 * dist * fwd + 0.025 * dist * right
-    a = np.radians(2.0)
-    d = center - eye
-    d = np.array([np.cos(a) * d[0] + np.sin(a) * d[2], d[1], -np.sin(a) * d[0] + np.cos(a) * d[2]])
-    return Camera(eye=tuple(eye2), center=tuple(eye2 + d), up=cam.up, fov=cam.fov)
-
-
-def stage_ms(r, p):
-    ms = C.c_float()
-    r._check(capi.lib().pt_debug_temporal_time(r._ctx, C.byref(p), REPS, C.byref(ms)))
-    return ms.value
-
-
-def host_ms(fn, n=10):
-    fn()
-    out = []
-    for _ in range(n):
-        t0 = time.perf_counter()
-        fn()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(out), min(out), max(out)
-
-
 def main():
-    wl = workloads.c3_sponza(W, H, 1)
-    if wl.scene.vertices is None:
-        wl.scene.finalize(capi.pack_vertices)
-    print(f"{wl.name}; library {os.path.relpath(capi.LIB_PATH, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))}")
-    r = HipRenderer()
-    r.setup(0)
-    r.set_scene(wl.scene)
-    integral, _ = r.set_env(wl.env)
-    r.set_sunsky(hd.default_sun_and_sky())
-    r.create((W, H))
-    st = hd.default_rtx_state()
-    st.size[0], st.size[1] = W, H
-    st.maxDepth, st.pbrMode, st.fireflyClampThreshold, st.frame = wl.depth, wl.pbr_mode, 4.0 * integral, 0
+    wl, r, st = c3_renderer(W, H)
 
-    def frame_at(cam):
-        r.set_camera(capi.camera_lookat(cam, W / H, nb_lights=len(wl.scene.lights)))
-        r.capture_guides(7, MISS_DEPTH)
-        r.setPushContants(st)
-        r.run()
-        return r.temporal_params(r.world_to_clip(cam, W / H), 0.05, 0.05, 32.0)
+    def temporal_ms(p):
+        return stage_ms(r, "pt_debug_temporal_time", C.byref(p))
 
     cam_a, cam_b = wl.scene.camera, moved(wl.scene.camera)
     table = {}
     for _ in range(ROUNDS):
         r.temporal_reset()
-        p_a = frame_at(cam_a)
-        table.setdefault("first call (no history)", []).append(stage_ms(r, p_a))
+        p_a = frame_at(r, wl, st, cam_a)
+        table.setdefault("first call (no history)", []).append(temporal_ms(p_a))
         r.temporal_accumulate(p_a, read=False)
-        p_b = frame_at(cam_b)
-        table.setdefault("after the camera move", []).append(stage_ms(r, p_b))
+        p_b = frame_at(r, wl, st, cam_b)
+        table.setdefault("after the camera move", []).append(temporal_ms(p_b))
         r.temporal_accumulate(p_b, read=False)
         _, length = r.read_temporal_history()
-        table.setdefault("static camera", []).append(stage_ms(r, p_b))
+        table.setdefault("static camera", []).append(temporal_ms(p_b))
     peaks = r.measure_peaks()
     copy_rate = peaks["hbmCopyBytesPerSec"]
     floor_ms = FLOOR_BYTES * W * H / copy_rate * 1e3
@@ -106,7 +53,7 @@ def main():
     print(f"after the move {100.0 * float((length > 1).mean()):.1f} % of the pixels found history (length > 1)")
     for name, v in table.items():
         med = statistics.median(v)
-        print(f"k_temporal, {name}: {med:.3f} ms = {med / floor_ms:.2f} x the floor ({med / (floor_ms * KERNEL_BYTES / FLOOR_BYTES):.2f} x the {KERNEL_BYTES} B the kernel must move)   [rounds: {' '.join(f'{x:.3f}' for x in v)}]")
+        print(f"k_temporal, {name}: {med:.3f} ms = {med / floor_ms:.2f} x the floor ({med / (floor_ms * KERNEL_BYTES / FLOOR_BYTES):.2f} x the {KERNEL_BYTES} B the kernel must move)   {rounds(v)}")
     a = host_ms(r.read_accum)
     b = host_ms(lambda: r.temporal_accumulate(p_b))
     c = host_ms(lambda: r.temporal_accumulate(p_b, read=False))

@@ -10,6 +10,7 @@
 #include <cstring>
 #include "pt_context.h"
 #include "pt_scene_records.h"
+#include "pt_stage.h"  // stages_release
 
 static std::string g_createError;
 
@@ -333,8 +334,7 @@ int pt_destroy(pt_context* c)
                    &c->dMean, &c->dMips, &c->dGather, &c->dFullTiles, &c->dFullSlotTile, &c->dTileLocalIndex};
   for(DevBuf* b : all)
     dev_free(*b);
-  denoise_release(c);
-  temporal_release(c);
+  stages_release(c);
   for(auto& fs : c->slots)
   {
     fs.release_paths();
@@ -640,8 +640,7 @@ int pt_resize(pt_context* c, int width, int height)
     return PT_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_all(c));
-  denoise_release(c);  // the denoiser's buffers and the guide planes were sized for the old image
-  temporal_release(c);  // ... and so was the history
+  stages_release(c);  // the denoiser's buffers, the guide planes and the history were sized for the old image
   c->tilesX = (width + PT_TILE - 1) / PT_TILE;
   c->tilesY = (height + PT_TILE - 1) / PT_TILE;
   std::vector<uint32_t> local;

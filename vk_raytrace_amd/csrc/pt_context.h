@@ -186,8 +186,6 @@ int        untile_to_rowmajor(pt_context* c);  // the row-major accumulation ima
 int        display_chain(pt_context* c, int dispW, int dispH, bool chain, hipEvent_t readDone, MipView& mv);  // the display pass's offscreen image and its mip chain, enqueued
 int        display_levels(pt_context* c, const float4* image, int dispW, int dispH, bool chain, MipView& mv);  // ... the part after level 0 (`image`, accumulation size) is chosen
 int        display_finish(pt_context* c, const pt_Tonemapper* tm, MipView& mv, int dispW, int dispH, uint8_t* out);  // ... the tonemap kernel and the copy to `out` (host), enqueued
-void       denoise_release(pt_context* c);  // pt_denoise.hip: frees the denoiser's images and drops the guide planes
-void       temporal_release(pt_context* c);  // pt_temporal.hip: frees the history
 struct TemporalConst;
 struct TemporalMArgs {  // pt_svgf.hip: k_temporal_m, the temporal kernel that also writes the moments -- the arguments of k_temporal and the fourth image
   const float4 *c, *g1, *g2, *hc, *hg;

@@ -2,8 +2,7 @@
 // accumulation image and the display pass.  The per-pixel arithmetic is pt_denoise.h; this unit holds its kernels, their launches and the entry points.
 // No existing kernel is involved: the stage reads the row-major image the display pass already produces (untile_to_rowmajor) and guide planes the
 // caller installed, and writes to buffers of its own.
-#include "pt_context.h"
-#include "pt_denoise.h"
+#include "pt_stage.h"
 
 // One block filters a DN_TX x DN_TY tile of the image, one pixel per lane: a wave covers two rows of 32 pixels, so that adjacent lanes read adjacent
 // 16-byte pixels (512 contiguous bytes per row and plane).
@@ -25,20 +24,18 @@ struct DnArgs {
   DenoiseConst  k;
 };
 
-PT_DN DnPx dn_px(const float4& v) { return DnPx{v.x, v.y, v.z, v.w}; }
-
 // taps read from memory, one 16-byte load per plane
 struct DnGlobal {
   const DnArgs& a;
-  __device__ DnPx colour(int x, int y) const { return dn_px(a.c[size_t(y) * size_t(a.w) + size_t(x)]); }
-  __device__ DnPx guide(int j, int x, int y) const { return dn_px(a.g[j][size_t(y) * size_t(a.w) + size_t(x)]); }
+  __device__ DnPx colour(int x, int y) const { return stage_px(a.c[size_t(y) * size_t(a.w) + size_t(x)]); }
+  __device__ DnPx guide(int j, int x, int y) const { return stage_px(a.g[j][size_t(y) * size_t(a.w) + size_t(x)]); }
 };
 // taps read from the block's tile: plane p (0: colour, 1 + j: guide j) at tile + p * tw * th, pixel (ox, oy) of the image first
 struct DnTile {
   const float4* tile;
   int           ox, oy, tw, planeStride;
-  __device__ DnPx colour(int x, int y) const { return dn_px(tile[(y - oy) * tw + (x - ox)]); }
-  __device__ DnPx guide(int j, int x, int y) const { return dn_px(tile[(1 + j) * planeStride + (y - oy) * tw + (x - ox)]); }
+  __device__ DnPx colour(int x, int y) const { return stage_px(tile[(y - oy) * tw + (x - ox)]); }
+  __device__ DnPx guide(int j, int x, int y) const { return stage_px(tile[(1 + j) * planeStride + (y - oy) * tw + (x - ox)]); }
 };
 
 // S > 0: the iteration of step S with its tile in LDS ((DN_TX + 4 S) x (DN_TY + 4 S) pixels per plane; a plane whose term is off is neither loaded
@@ -85,13 +82,13 @@ __global__ void __launch_bounds__(256) k_modulate(const float4* __restrict__ alb
   const size_t i = size_t(blockIdx.x) * 256u + threadIdx.x;
   if(i >= n)
     return;
-  const DnPx r = REMOD ? denoise_remodulate(dn_px(c[i]), dn_px(albedo[i])) : denoise_demodulate(dn_px(c[i]), dn_px(albedo[i]));
+  const DnPx r = REMOD ? denoise_remodulate(stage_px(c[i]), stage_px(albedo[i])) : denoise_demodulate(stage_px(c[i]), stage_px(albedo[i]));
   out[i]       = make_float4(r.x, r.y, r.z, r.w);
 }
 
 static void launch_iteration(hipStream_t stream, const DnArgs& a, int ldsMaxStep)
 {
-  const dim3 grid((a.w + DN_TX - 1) / DN_TX, (a.h + DN_TY - 1) / DN_TY), block(DN_TX, DN_TY);
+  const dim3 grid = stage_grid(a.w, a.h, DN_TX, DN_TY), block(DN_TX, DN_TY);
   const int  step = 1 << a.iteration;
   if(step == 1 && ldsMaxStep >= 1)
     k_denoise<1><<<grid, block, 0, stream>>>(a);
@@ -101,45 +98,25 @@ static void launch_iteration(hipStream_t stream, const DnArgs& a, int ldsMaxStep
     k_denoise<0><<<grid, block, 0, stream>>>(a);
 }
 
-static uint32_t planes_set(const pt_context* c)
-{
-  uint32_t m = 0;
-  for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
-    m |= c->dGuide[j].p ? 1u << j : 0u;
-  return m;
-}
-
-void denoise_release(pt_context* c)
-{
-  for(DevBuf& b : c->dDenoise)
-    dev_free(b);
-  for(DevBuf& b : c->dGuide)
-    dev_free(b);
-}
-
 // Everything the entry points check, then the row-major accumulation image enqueued on the context's stream behind the frames rendered so far
 // (untile == false: the caller filters another image, the history of pt_temporal.hip, and the accumulation image is not asked for)
 static int prepare_denoise(pt_context* c, const char* who, const pt_DenoiseParams* p, DenoiseConst& k, bool untile = true)
 {
-  if(c->width == 0)
-    return c->fail(PT_ERR_STATE, "%s before pt_resize", who);
+  STAGE_TRY(stage_need_image(c, who));
   const char* why = "";
-  int         rc  = denoise_constants(p, planes_set(c), &k, &why);
+  const int   rc  = denoise_constants(p, guide_planes_set(c), &k, &why);
   if(rc != PT_OK)
     return c->fail(rc, "%s: %s", who, why);
-  if(c->nranks > 1 && !c->haveFull)
-    return c->fail(PT_ERR_STATE, "%s: rank %d of %d holds only its own tiles; gather the image first", who, c->rank, c->nranks);
+  STAGE_TRY(stage_need_full_image(c, who));
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t n = size_t(c->width) * size_t(c->height);
   for(DevBuf& b : c->dDenoise)
-    if((rc = dev_alloc(c, b, sizeof(float4) * n)) != PT_OK)
-      return rc;
+    STAGE_TRY(dev_alloc(c, b, sizeof(float4) * stage_pixels(c)));
   return untile ? untile_to_rowmajor(c) : PT_OK;
 }
 // The filter over the row-major image `src`, enqueued on the context's stream; returns the filtered row-major image (one of the denoiser's two, valid until the next call)
 static const float4* enqueue_filter(pt_context* c, const float4* src, const pt_DenoiseParams* p, const DenoiseConst& k)
 {
-  const size_t  n      = size_t(c->width) * size_t(c->height);
+  const size_t  n      = stage_pixels(c);
   float4* const buf[2] = {(float4*)c->dDenoise[0].p, (float4*)c->dDenoise[1].p};
   const float4* cur    = src;
   const bool    demod  = (p->flags & PT_DENOISE_DEMODULATE) != 0u;
@@ -155,7 +132,7 @@ static const float4* enqueue_filter(pt_context* c, const float4* src, const pt_D
   a.w = c->width;
   a.h = c->height;
   a.k = k;
-  const int ldsMaxStep = c->denoiseLdsMaxStep < 0 ? DN_LDS_DEFAULT_STEP : c->denoiseLdsMaxStep;
+  const int ldsMaxStep = stage_lds_step(c->denoiseLdsMaxStep, DN_LDS_DEFAULT_STEP);
   for(int i = 0; i < p->iterations; ++i)
   {
     a.c         = cur;
@@ -171,9 +148,7 @@ static const float4* enqueue_filter(pt_context* c, const float4* src, const pt_D
 static int enqueue_denoise(pt_context* c, const char* who, const pt_DenoiseParams* p, const float4*& result)
 {
   DenoiseConst k;
-  const int    rc = prepare_denoise(c, who, p, k);
-  if(rc != PT_OK)
-    return rc;
+  STAGE_TRY(prepare_denoise(c, who, p, k));
   result = enqueue_filter(c, (const float4*)c->dRowMajor.p, p, k);
   HIP_TRY(c, hipGetLastError());
   return PT_OK;
@@ -182,10 +157,8 @@ static int enqueue_denoise(pt_context* c, const char* who, const pt_DenoiseParam
 // history itself.  Reads the history and the current guide planes; writes the denoiser's own images only.
 static int enqueue_denoise_history(pt_context* c, const char* who, const pt_DenoiseParams* p, const float4*& result)
 {
-  if(c->width == 0)
-    return c->fail(PT_ERR_STATE, "%s before pt_resize", who);
-  if(!c->haveHistory)
-    return c->fail(PT_ERR_STATE, "%s: there is no history (no pt_temporal_accumulate since pt_resize / pt_temporal_reset)", who);
+  STAGE_TRY(stage_need_image(c, who));
+  STAGE_TRY(stage_need_history(c, who, false));
   const float4* hist = (const float4*)c->dHistColour[c->histSet].p;
   if(!p)
   {
@@ -194,9 +167,7 @@ static int enqueue_denoise_history(pt_context* c, const char* who, const pt_Deno
     return PT_OK;
   }
   DenoiseConst k;
-  const int    rc = prepare_denoise(c, who, p, k, false);
-  if(rc != PT_OK)
-    return rc;
+  STAGE_TRY(prepare_denoise(c, who, p, k, false));
   result = enqueue_filter(c, hist, p, k);
   HIP_TRY(c, hipGetLastError());
   return PT_OK;
@@ -209,10 +180,9 @@ int pt_set_denoise_guides(pt_context* c, const float* const planes[PT_DENOISE_GU
   CTX_CHECK(c);
   if(!planes)
     return c->fail(PT_ERR_INVALID, "pt_set_denoise_guides: null");
-  if(c->width == 0)
-    return c->fail(PT_ERR_STATE, "pt_set_denoise_guides before pt_resize");
+  STAGE_TRY(stage_need_image(c, "pt_set_denoise_guides"));
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t bytes = sizeof(float4) * size_t(c->width) * size_t(c->height);
+  const size_t bytes = sizeof(float4) * stage_pixels(c);
   for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
   {
     if(!planes[j])
@@ -220,9 +190,7 @@ int pt_set_denoise_guides(pt_context* c, const float* const planes[PT_DENOISE_GU
       dev_free(c->dGuide[j]);
       continue;
     }
-    int rc = dev_alloc(c, c->dGuide[j], bytes);
-    if(rc != PT_OK)
-      return rc;
+    STAGE_TRY(dev_alloc(c, c->dGuide[j], bytes));
     HIP_TRY(c, hipMemcpyAsync(c->dGuide[j].p, planes[j], bytes, hipMemcpyHostToDevice, c->stream));
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -235,12 +203,8 @@ int pt_denoise(pt_context* c, const pt_DenoiseParams* p, float* out)
   if(!p || !out)
     return c->fail(PT_ERR_INVALID, "pt_denoise: null");
   const float4* img = nullptr;
-  int           rc  = enqueue_denoise(c, "pt_denoise", p, img);
-  if(rc != PT_OK)
-    return rc;
-  HIP_TRY(c, hipMemcpyAsync(out, img, sizeof(float4) * size_t(c->width) * size_t(c->height), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, sync_all(c));
-  return check_traversal(c);
+  STAGE_TRY(enqueue_denoise(c, "pt_denoise", p, img));
+  return stage_read(c, {{out, img, sizeof(float4) * stage_pixels(c)}});
 }
 
 int pt_tonemap_denoised(pt_context* c, const pt_DenoiseParams* p, const pt_Tonemapper* tm, uint8_t* out)
@@ -249,14 +213,8 @@ int pt_tonemap_denoised(pt_context* c, const pt_DenoiseParams* p, const pt_Tonem
   if(!p || !tm || !out)
     return c->fail(PT_ERR_INVALID, "pt_tonemap_denoised: null");
   const float4* img = nullptr;
-  int           rc  = enqueue_denoise(c, "pt_tonemap_denoised", p, img);
-  if(rc != PT_OK)
-    return rc;
-  MipView mv{};
-  if((rc = display_levels(c, img, c->width, c->height, (tm->autoExposure & 1) != 0, mv)) != PT_OK || (rc = display_finish(c, tm, mv, c->width, c->height, out)) != PT_OK)
-    return rc;
-  HIP_TRY(c, sync_all(c));
-  return check_traversal(c);
+  STAGE_TRY(enqueue_denoise(c, "pt_tonemap_denoised", p, img));
+  return stage_show(c, tm, img, out);
 }
 
 int pt_denoise_history(pt_context* c, const pt_DenoiseParams* p, float* out)
@@ -265,12 +223,8 @@ int pt_denoise_history(pt_context* c, const pt_DenoiseParams* p, float* out)
   if(!p || !out)
     return c->fail(PT_ERR_INVALID, "pt_denoise_history: null");
   const float4* img = nullptr;
-  int           rc  = enqueue_denoise_history(c, "pt_denoise_history", p, img);
-  if(rc != PT_OK)
-    return rc;
-  HIP_TRY(c, hipMemcpyAsync(out, img, sizeof(float4) * size_t(c->width) * size_t(c->height), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, sync_all(c));
-  return check_traversal(c);
+  STAGE_TRY(enqueue_denoise_history(c, "pt_denoise_history", p, img));
+  return stage_read(c, {{out, img, sizeof(float4) * stage_pixels(c)}});
 }
 
 int pt_tonemap_history(pt_context* c, const pt_DenoiseParams* p, const pt_Tonemapper* tm, uint8_t* out)
@@ -279,14 +233,8 @@ int pt_tonemap_history(pt_context* c, const pt_DenoiseParams* p, const pt_Tonema
   if(!tm || !out)
     return c->fail(PT_ERR_INVALID, "pt_tonemap_history: null");
   const float4* img = nullptr;
-  int           rc  = enqueue_denoise_history(c, "pt_tonemap_history", p, img);
-  if(rc != PT_OK)
-    return rc;
-  MipView mv{};
-  if((rc = display_levels(c, img, c->width, c->height, (tm->autoExposure & 1) != 0, mv)) != PT_OK || (rc = display_finish(c, tm, mv, c->width, c->height, out)) != PT_OK)
-    return rc;
-  HIP_TRY(c, sync_all(c));
-  return check_traversal(c);
+  STAGE_TRY(enqueue_denoise_history(c, "pt_tonemap_history", p, img));
+  return stage_show(c, tm, img, out);
 }
 
 // Test and measurement access (not part of pt_api.h): the largest step whose iteration stages its tile in LDS, 0 .. DN_LDS_MAX_STEP (0: every
@@ -294,10 +242,9 @@ int pt_tonemap_history(pt_context* c, const pt_DenoiseParams* p, const pt_Tonema
 __attribute__((visibility("default"))) int pt_debug_denoise_lds(pt_context* c, int maxStep)
 {
   CTX_CHECK(c);
-  c->denoiseLdsMaxStep = maxStep < 0 ? -1 : maxStep > DN_LDS_MAX_STEP ? DN_LDS_MAX_STEP : maxStep;
-  return c->denoiseLdsMaxStep < 0 ? DN_LDS_DEFAULT_STEP : c->denoiseLdsMaxStep;
+  c->denoiseLdsMaxStep = stage_lds_clamp(maxStep, DN_LDS_MAX_STEP);
+  return stage_lds_step(c->denoiseLdsMaxStep, DN_LDS_DEFAULT_STEP);
 }
-
 
 // Measurement access (not part of pt_api.h; tools/denoise_rate.py): the filter of pt_denoise enqueued `reps` times between two events on the context's
 // stream, after one untimed run -- milliseconds per run in *ms_out, without the untile pass before it and without any copy.  Synchronous.
@@ -307,31 +254,8 @@ __attribute__((visibility("default"))) int pt_debug_denoise_time(pt_context* c, 
   if(!ms_out || reps < 1)
     return c->fail(PT_ERR_INVALID, "pt_debug_denoise_time: null or reps < 1");
   DenoiseConst k;
-  int          rc = prepare_denoise(c, "pt_debug_denoise_time", p, k);
-  if(rc != PT_OK)
-    return rc;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  HIP_TRY(c, hipEventCreate(&ev[0]));
-  if(hipEventCreate(&ev[1]) != hipSuccess)
-  {
-    (void)hipEventDestroy(ev[0]);
-    return c->fail(PT_ERR_HIP, "pt_debug_denoise_time: hipEventCreate");
-  }
-  (void)enqueue_filter(c, (const float4*)c->dRowMajor.p, p, k);
-  hipError_t e = hipEventRecord(ev[0], c->stream);
-  for(int i = 0; i < reps && e == hipSuccess; ++i)
-    (void)enqueue_filter(c, (const float4*)c->dRowMajor.p, p, k);
-  if(e == hipSuccess) e = hipGetLastError();
-  if(e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  if(e == hipSuccess) e = sync_all(c);
-  float ms = 0.0f;
-  if(e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
-  if(e != hipSuccess)
-    return c->fail(PT_ERR_HIP, "pt_debug_denoise_time: %s", hipGetErrorString(e));
-  *ms_out = ms / float(reps);
-  return check_traversal(c);
+  STAGE_TRY(prepare_denoise(c, "pt_debug_denoise_time", p, k));
+  return stage_time(c, "pt_debug_denoise_time", reps, ms_out, [&] { (void)enqueue_filter(c, (const float4*)c->dRowMajor.p, p, k); });
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // pt_render_guides / pt_read_denoise_guides (include/pt_api.h): the denoiser's guide planes rendered on the device in one first-hit pass.  The
 // per-pixel body is pt_guides.h; this unit holds its kernel, the launch and the entry points.  No existing kernel is involved: the pass walks the
 // structures the frames walk, with the functions the frames' kernels are made of, and writes only the context's guide planes.
-#include "pt_context.h"
+#include "pt_stage.h"
 #include "pt_guides.h"
 
 // Waves per SIMD the kernel is compiled for, flat / two-level: k_query's (pt_query.hip), kept after timing the neighbours -- flat 4 / 5 / 6 waves
@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_GUIDES_WAVES_TWO : PT_GU
 
 static void launch_guides(pt_context* c, const GuideArgs& a)
 {
-  const dim3 grid((a.w + GUIDES_TILE - 1) / GUIDES_TILE, (a.h + GUIDES_TILE - 1) / GUIDES_TILE);
+  const dim3 grid = stage_grid(a.w, a.h, GUIDES_TILE, GUIDES_TILE);
   if(c->scene.twoLevel)
     k_guides<true><<<grid, TRACE_BLOCK, 0, c->stream>>>(c->scene, a, (Counters*)c->dCounters.p);
   else
@@ -61,15 +61,12 @@ static int prepare_guides(pt_context* c, const char* who, uint32_t planes, float
     return c->fail(PT_ERR_STATE, "%s before pt_set_scene / pt_build_accel", who);
   if(!c->haveCamera)
     return c->fail(PT_ERR_STATE, "%s before pt_set_camera", who);
-  if(c->width == 0)
-    return c->fail(PT_ERR_STATE, "%s before pt_resize", who);
+  STAGE_TRY(stage_need_image(c, who));
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t bytes = sizeof(float4) * size_t(c->width) * size_t(c->height);
   for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
   {
-    int rc;
-    if((planes & (1u << j)) && (rc = dev_alloc(c, c->dGuide[j], bytes)) != PT_OK)
-      return rc;
+    if(planes & (1u << j))
+      STAGE_TRY(dev_alloc(c, c->dGuide[j], sizeof(float4) * stage_pixels(c)));
     a.plane[j] = (float4*)c->dGuide[j].p;
   }
   a.w         = c->width;
@@ -85,9 +82,7 @@ int pt_render_guides(pt_context* c, uint32_t planes, float miss_depth)
 {
   CTX_CHECK(c);
   GuideArgs a;
-  const int rc = prepare_guides(c, "pt_render_guides", planes, miss_depth, a);
-  if(rc != PT_OK)
-    return rc;
+  STAGE_TRY(prepare_guides(c, "pt_render_guides", planes, miss_depth, a));
   // frames handed to pt_render_frame stay pending and frames in flight keep running on their slots' streams: the pass shares nothing with them
   // but the scene, which it only reads, and the overflow counter, which both only add to
   launch_guides(c, a);
@@ -100,18 +95,14 @@ int pt_read_denoise_guides(pt_context* c, float* const planes_out[PT_DENOISE_GUI
   CTX_CHECK(c);
   if(!planes_out)
     return c->fail(PT_ERR_INVALID, "pt_read_denoise_guides: null");
-  if(c->width == 0)
-    return c->fail(PT_ERR_STATE, "pt_read_denoise_guides before pt_resize");
+  STAGE_TRY(stage_need_image(c, "pt_read_denoise_guides"));
   for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
     if(planes_out[j] && !c->dGuide[j].p)
       return c->fail(PT_ERR_STATE, "pt_read_denoise_guides: guide plane %d is not installed", j);
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t bytes = sizeof(float4) * size_t(c->width) * size_t(c->height);
-  for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
-    if(planes_out[j])
-      HIP_TRY(c, hipMemcpyAsync(planes_out[j], c->dGuide[j].p, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, sync_all(c));
-  return check_traversal(c);
+  const size_t bytes = sizeof(float4) * stage_pixels(c);
+  static_assert(PT_DENOISE_GUIDES == 3, "one copy per plane");
+  return stage_read(c, {{planes_out[0], c->dGuide[0].p, bytes}, {planes_out[1], c->dGuide[1].p, bytes}, {planes_out[2], c->dGuide[2].p, bytes}});
 }
 
 // Measurement access (not part of pt_api.h; tools/guides_rate.py): the pass of pt_render_guides enqueued `reps` times between two events on the
@@ -122,31 +113,8 @@ __attribute__((visibility("default"))) int pt_debug_guides_time(pt_context* c, u
   if(!ms_out || reps < 1)
     return c->fail(PT_ERR_INVALID, "pt_debug_guides_time: null or reps < 1");
   GuideArgs a;
-  const int rc = prepare_guides(c, "pt_debug_guides_time", planes, miss_depth, a);
-  if(rc != PT_OK)
-    return rc;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  HIP_TRY(c, hipEventCreate(&ev[0]));
-  if(hipEventCreate(&ev[1]) != hipSuccess)
-  {
-    (void)hipEventDestroy(ev[0]);
-    return c->fail(PT_ERR_HIP, "pt_debug_guides_time: hipEventCreate");
-  }
-  launch_guides(c, a);
-  hipError_t e = hipEventRecord(ev[0], c->stream);
-  for(int i = 0; i < reps && e == hipSuccess; ++i)
-    launch_guides(c, a);
-  if(e == hipSuccess) e = hipGetLastError();
-  if(e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  if(e == hipSuccess) e = sync_all(c);
-  float ms = 0.0f;
-  if(e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
-  if(e != hipSuccess)
-    return c->fail(PT_ERR_HIP, "pt_debug_guides_time: %s", hipGetErrorString(e));
-  *ms_out = ms / float(reps);
-  return check_traversal(c);
+  STAGE_TRY(prepare_guides(c, "pt_debug_guides_time", planes, miss_depth, a));
+  return stage_time(c, "pt_debug_guides_time", reps, ms_out, [&] { launch_guides(c, a); });
 }
 
 }  // extern "C"

@@ -3,10 +3,8 @@
 // initial variance and the filter iteration -- their launches and the entry points.  No existing kernel is involved and none is compiled from other
 // text than before: the stage reads the history pt_temporal.hip keeps and the current guide planes, and writes the denoiser's two images and two
 // variance planes of its own.
-#include "pt_context.h"
+#include "pt_stage.h"
 #include "pt_svgf.h"
-
-PT_DN DnPx sv_px(const float4& v) { return DnPx{v.x, v.y, v.z, v.w}; }
 
 // ---- the temporal step with moments --------------------------------------------------------------------------------------------------------------------
 // The 32 x 8 tile of k_temporal (pt_temporal.hip), one pixel per lane; temporal_pixel as it stands, with a probe on the lane's stack that svgf_moments
@@ -21,11 +19,11 @@ struct SvTemporalArgs {
 struct SvTemporalGlobal {
   const TemporalMArgs& a;
   __device__ size_t at(int x, int y) const { return size_t(y) * size_t(a.w) + size_t(x); }
-  __device__ DnPx   colour(int x, int y) const { return sv_px(a.c[at(x, y)]); }
-  __device__ DnPx   normal(int x, int y) const { return sv_px(a.g1[at(x, y)]); }
-  __device__ DnPx   depth(int x, int y) const { return sv_px(a.g2[at(x, y)]); }
-  __device__ DnPx   histColour(int x, int y) const { return sv_px(a.hc[at(x, y)]); }
-  __device__ DnPx   histGuide(int x, int y) const { return sv_px(a.hg[at(x, y)]); }
+  __device__ DnPx   colour(int x, int y) const { return stage_px(a.c[at(x, y)]); }
+  __device__ DnPx   normal(int x, int y) const { return stage_px(a.g1[at(x, y)]); }
+  __device__ DnPx   depth(int x, int y) const { return stage_px(a.g2[at(x, y)]); }
+  __device__ DnPx   histColour(int x, int y) const { return stage_px(a.hc[at(x, y)]); }
+  __device__ DnPx   histGuide(int x, int y) const { return stage_px(a.hg[at(x, y)]); }
   __device__ float  histLength(int x, int y) const { return a.hn[at(x, y)]; }
   __device__ SvM    histMoments(int x, int y) const
   {
@@ -52,8 +50,7 @@ __global__ void __launch_bounds__(SVT_TX * SVT_TY) k_temporal_m(SvTemporalArgs a
 
 void launch_temporal_m(hipStream_t stream, const TemporalMArgs& a, const TemporalConst& k)
 {
-  const dim3 grid((a.w + SVT_TX - 1) / SVT_TX, (a.h + SVT_TY - 1) / SVT_TY), block(SVT_TX, SVT_TY);
-  k_temporal_m<<<grid, block, 0, stream>>>(SvTemporalArgs{a, k});
+  k_temporal_m<<<stage_grid(a.w, a.h, SVT_TX, SVT_TY), dim3(SVT_TX, SVT_TY), 0, stream>>>(SvTemporalArgs{a, k});
 }
 
 // ---- initial variance and the filter iteration ---------------------------------------------------------------------------------------------------------
@@ -83,8 +80,8 @@ struct SvArgs {
 struct SvGlobal {
   const SvArgs& a;
   __device__ size_t at(int x, int y) const { return size_t(y) * size_t(a.w) + size_t(x); }
-  __device__ DnPx   colour(int x, int y) const { return sv_px(a.c[at(x, y)]); }
-  __device__ DnPx   guide(int j, int x, int y) const { return sv_px(a.g[j][at(x, y)]); }
+  __device__ DnPx   colour(int x, int y) const { return stage_px(a.c[at(x, y)]); }
+  __device__ DnPx   guide(int j, int x, int y) const { return stage_px(a.g[j][at(x, y)]); }
   __device__ float  variance(int x, int y) const { return a.v[at(x, y)]; }
   __device__ float  length(int x, int y) const { return a.hn[at(x, y)]; }
   __device__ SvM    moments(int x, int y) const
@@ -98,8 +95,8 @@ struct SvTile {
   const float4* tile;
   const float*  var;
   int           ox, oy, tw, planeStride;
-  __device__ DnPx  colour(int x, int y) const { return sv_px(tile[(y - oy) * tw + (x - ox)]); }
-  __device__ DnPx  guide(int j, int x, int y) const { return sv_px(tile[(1 + j) * planeStride + (y - oy) * tw + (x - ox)]); }
+  __device__ DnPx  colour(int x, int y) const { return stage_px(tile[(y - oy) * tw + (x - ox)]); }
+  __device__ DnPx  guide(int j, int x, int y) const { return stage_px(tile[(1 + j) * planeStride + (y - oy) * tw + (x - ox)]); }
   __device__ float variance(int x, int y) const { return var[(y - oy) * tw + (x - ox)]; }
 };
 
@@ -113,7 +110,7 @@ struct SvVarTile {
   int           ox, oy, tw, planeStride;
   __device__ int   at(int x, int y) const { return (y - oy) * tw + (x - ox); }
   __device__ DnPx  colour(int x, int y) const { return DnPx{fin[at(x, y)], 0.0f, 0.0f, 0.0f}; }
-  __device__ DnPx  guide(int j, int x, int y) const { return sv_px(g[j * planeStride + at(x, y)]); }
+  __device__ DnPx  guide(int j, int x, int y) const { return stage_px(g[j * planeStride + at(x, y)]); }
   __device__ float length(int x, int y) const { return n[at(x, y)]; }
   __device__ SvM   moments(int x, int y) const
   {
@@ -149,7 +146,7 @@ __global__ void __launch_bounds__(SV_BLOCK) k_svgf_variance(SvArgs a)
         const size_t at = size_t(gy) * size_t(a.w) + size_t(gx);
         tm[t] = a.hm[at];
         tn[t] = a.hn[at];
-        tf[t] = dn_finite3(sv_px(a.c[at])) ? 0.0f : ptf_nan();
+        tf[t] = dn_finite3(stage_px(a.c[at])) ? 0.0f : ptf_nan();
         for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
           if(a.k.terms & (2u << j))
             tg[j * TW * TH + t] = a.g[j][at];
@@ -207,7 +204,7 @@ __global__ void __launch_bounds__(SV_BLOCK) k_svgf(SvArgs a)
   }
 }
 
-static dim3 sv_grid(const SvArgs& a) { return dim3((a.w + SV_TX - 1) / SV_TX, (a.h + SV_TY - 1) / SV_TY); }
+static dim3 sv_grid(const SvArgs& a) { return stage_grid(a.w, a.h, SV_TX, SV_TY); }
 
 static void launch_svgf_iteration(hipStream_t stream, const SvArgs& a, int ldsMaxStep)
 {
@@ -224,24 +221,18 @@ static void launch_svgf_iteration(hipStream_t stream, const SvArgs& a, int ldsMa
 // Everything the entry points check, then the filter's buffers; the arguments every kernel of the call shares in `a`.  Nothing is launched here.
 static int prepare_svgf(pt_context* c, const char* who, const pt_SvgfParams* p, SvArgs& a)
 {
-  if(c->width == 0)
-    return c->fail(PT_ERR_STATE, "%s before pt_resize", who);
-  if(!c->haveHistory)
-    return c->fail(PT_ERR_STATE, "%s: there is no history (no pt_temporal_accumulate since pt_resize / pt_temporal_reset)", who);
-  if(!c->histHasMoments)
-    return c->fail(PT_ERR_STATE, "%s: the history was made without moments (pt_temporal_track_moments)", who);
-  uint32_t planes = 0;
-  for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
-    planes |= c->dGuide[j].p ? 1u << j : 0u;
+  STAGE_TRY(stage_need_image(c, who));
+  STAGE_TRY(stage_need_history(c, who, true));
   const char* why = "";
-  int         rc  = svgf_constants(p, planes, &a.k, &why);
+  const int   rc  = svgf_constants(p, guide_planes_set(c), &a.k, &why);
   if(rc != PT_OK)
     return c->fail(rc, "%s: %s", who, why);
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t n = size_t(c->width) * size_t(c->height);
   for(int s = 0; s < 2; ++s)
-    if((rc = dev_alloc(c, c->dDenoise[s], sizeof(float4) * n)) != PT_OK || (rc = dev_alloc(c, c->dSvgfVar[s], sizeof(float) * n)) != PT_OK)
-      return rc;
+  {
+    STAGE_TRY(dev_alloc(c, c->dDenoise[s], sizeof(float4) * stage_pixels(c)));
+    STAGE_TRY(dev_alloc(c, c->dSvgfVar[s], sizeof(float) * stage_pixels(c)));
+  }
   for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
     a.g[j] = (const float4*)c->dGuide[j].p;
   a.c         = (const float4*)c->dHistColour[c->histSet].p;
@@ -270,7 +261,7 @@ static void enqueue_iterations(pt_context* c, SvArgs a, int iterations, const fl
 {
   float4* const cb[2]      = {(float4*)c->dDenoise[0].p, (float4*)c->dDenoise[1].p};
   float* const  vb[2]      = {(float*)c->dSvgfVar[0].p, (float*)c->dSvgfVar[1].p};
-  const int     ldsMaxStep = c->svgfLdsMaxStep < 0 ? SV_LDS_DEFAULT_STEP : c->svgfLdsMaxStep;
+  const int     ldsMaxStep = stage_lds_step(c->svgfLdsMaxStep, SV_LDS_DEFAULT_STEP);
   for(int i = 0; i < iterations; ++i)
   {
     a.v         = vb[i & 1];
@@ -285,10 +276,8 @@ static void enqueue_iterations(pt_context* c, SvArgs a, int iterations, const fl
 }
 static int enqueue_svgf(pt_context* c, const char* who, const pt_SvgfParams* p, const float4*& colour, const float*& variance)
 {
-  SvArgs    a;
-  const int rc = prepare_svgf(c, who, p, a);
-  if(rc != PT_OK)
-    return rc;
+  SvArgs a;
+  STAGE_TRY(prepare_svgf(c, who, p, a));
   enqueue_variance(c, a);
   enqueue_iterations(c, a, p->iterations, colour, variance);
   HIP_TRY(c, hipGetLastError());
@@ -302,14 +291,9 @@ int pt_read_temporal_moments(pt_context* c, float* m_out)
   CTX_CHECK(c);
   if(!m_out)
     return c->fail(PT_ERR_INVALID, "pt_read_temporal_moments: null");
-  if(!c->haveHistory)
-    return c->fail(PT_ERR_STATE, "pt_read_temporal_moments: there is no history (no pt_temporal_accumulate since pt_resize / pt_temporal_reset)");
-  if(!c->histHasMoments)
-    return c->fail(PT_ERR_STATE, "pt_read_temporal_moments: the history was made without moments (pt_temporal_track_moments)");
+  STAGE_TRY(stage_need_history(c, "pt_read_temporal_moments", true));
   HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipMemcpyAsync(m_out, c->dHistMoments[c->histSet].p, sizeof(float2) * size_t(c->width) * size_t(c->height), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, sync_all(c));
-  return check_traversal(c);
+  return stage_read(c, {{m_out, c->dHistMoments[c->histSet].p, sizeof(float2) * stage_pixels(c)}});
 }
 
 int pt_svgf_variance(pt_context* c, const pt_SvgfParams* p, float* variance_out)
@@ -318,14 +302,10 @@ int pt_svgf_variance(pt_context* c, const pt_SvgfParams* p, float* variance_out)
   if(!p || !variance_out)
     return c->fail(PT_ERR_INVALID, "pt_svgf_variance: null");
   SvArgs a;
-  int    rc = prepare_svgf(c, "pt_svgf_variance", p, a);
-  if(rc != PT_OK)
-    return rc;
+  STAGE_TRY(prepare_svgf(c, "pt_svgf_variance", p, a));
   enqueue_variance(c, a);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(variance_out, c->dSvgfVar[0].p, sizeof(float) * size_t(c->width) * size_t(c->height), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, sync_all(c));
-  return check_traversal(c);
+  return stage_read(c, {{variance_out, c->dSvgfVar[0].p, sizeof(float) * stage_pixels(c)}});
 }
 
 int pt_svgf_history(pt_context* c, const pt_SvgfParams* p, float* out, float* variance_out)
@@ -335,15 +315,8 @@ int pt_svgf_history(pt_context* c, const pt_SvgfParams* p, float* out, float* va
     return c->fail(PT_ERR_INVALID, "pt_svgf_history: null");
   const float4* img = nullptr;
   const float*  var = nullptr;
-  int           rc  = enqueue_svgf(c, "pt_svgf_history", p, img, var);
-  if(rc != PT_OK)
-    return rc;
-  const size_t n = size_t(c->width) * size_t(c->height);
-  HIP_TRY(c, hipMemcpyAsync(out, img, sizeof(float4) * n, hipMemcpyDeviceToHost, c->stream));
-  if(variance_out)
-    HIP_TRY(c, hipMemcpyAsync(variance_out, var, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, sync_all(c));
-  return check_traversal(c);
+  STAGE_TRY(enqueue_svgf(c, "pt_svgf_history", p, img, var));
+  return stage_read(c, {{out, img, sizeof(float4) * stage_pixels(c)}, {variance_out, var, sizeof(float) * stage_pixels(c)}});
 }
 
 int pt_tonemap_svgf(pt_context* c, const pt_SvgfParams* p, const pt_Tonemapper* tm, uint8_t* out)
@@ -353,14 +326,8 @@ int pt_tonemap_svgf(pt_context* c, const pt_SvgfParams* p, const pt_Tonemapper* 
     return c->fail(PT_ERR_INVALID, "pt_tonemap_svgf: null");
   const float4* img = nullptr;
   const float*  var = nullptr;
-  int           rc  = enqueue_svgf(c, "pt_tonemap_svgf", p, img, var);
-  if(rc != PT_OK)
-    return rc;
-  MipView mv{};
-  if((rc = display_levels(c, img, c->width, c->height, (tm->autoExposure & 1) != 0, mv)) != PT_OK || (rc = display_finish(c, tm, mv, c->width, c->height, out)) != PT_OK)
-    return rc;
-  HIP_TRY(c, sync_all(c));
-  return check_traversal(c);
+  STAGE_TRY(enqueue_svgf(c, "pt_tonemap_svgf", p, img, var));
+  return stage_show(c, tm, img, out);
 }
 
 // Test and measurement access (not part of pt_api.h): the largest step whose iteration stages its tile in LDS, 0 .. SV_LDS_MAX_STEP (0: every iteration
@@ -368,8 +335,8 @@ int pt_tonemap_svgf(pt_context* c, const pt_SvgfParams* p, const pt_Tonemapper* 
 __attribute__((visibility("default"))) int pt_debug_svgf_lds(pt_context* c, int maxStep)
 {
   CTX_CHECK(c);
-  c->svgfLdsMaxStep = maxStep < 0 ? -1 : maxStep > SV_LDS_MAX_STEP ? SV_LDS_MAX_STEP : maxStep;
-  return c->svgfLdsMaxStep < 0 ? SV_LDS_DEFAULT_STEP : c->svgfLdsMaxStep;
+  c->svgfLdsMaxStep = stage_lds_clamp(maxStep, SV_LDS_MAX_STEP);
+  return stage_lds_step(c->svgfLdsMaxStep, SV_LDS_DEFAULT_STEP);
 }
 
 // Measurement access (not part of pt_api.h; tools/svgf_rate.py): one part of pt_svgf_history enqueued `reps` times between two events on the context's
@@ -382,54 +349,35 @@ __attribute__((visibility("default"))) int pt_debug_svgf_time(pt_context* c, con
   if(!p || !ms_out || reps < 1 || what < -2 || what >= PT_SVGF_MAX_ITERATIONS)
     return c->fail(PT_ERR_INVALID, "pt_debug_svgf_time: null, reps < 1 or no such part");
   SvArgs a;
-  int    rc = prepare_svgf(c, "pt_debug_svgf_time", p, a);
-  if(rc != PT_OK)
-    return rc;
+  STAGE_TRY(prepare_svgf(c, "pt_debug_svgf_time", p, a));
   if(what >= p->iterations)
     return c->fail(PT_ERR_INVALID, "pt_debug_svgf_time: iteration %d of %d", what, p->iterations);
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  HIP_TRY(c, hipEventCreate(&ev[0]));
-  if(hipEventCreate(&ev[1]) != hipSuccess)
-  {
-    (void)hipEventDestroy(ev[0]);
-    return c->fail(PT_ERR_HIP, "pt_debug_svgf_time: hipEventCreate");
-  }
   const float4* img = nullptr;
   const float*  var = nullptr;
-  const int     ldsMaxStep = c->svgfLdsMaxStep < 0 ? SV_LDS_DEFAULT_STEP : c->svgfLdsMaxStep;
-  enqueue_variance(c, a);
-  enqueue_iterations(c, a, p->iterations, img, var);
-  SvArgs one    = a;  // a single iteration: in from the history and plane 0, out to the denoiser's image 1 and plane 1
+  const int     ldsMaxStep = stage_lds_step(c->svgfLdsMaxStep, SV_LDS_DEFAULT_STEP);
+  SvArgs        one        = a;  // a single iteration: in from the history and plane 0, out to the denoiser's image 1 and plane 1
   one.v         = (const float*)c->dSvgfVar[0].p;
   one.vOut      = (float*)c->dSvgfVar[1].p;
   one.out       = (float4*)c->dDenoise[1].p;
   one.iteration = what < 0 ? 0 : what;
-  if(what >= 0)
-    enqueue_variance(c, a);  // plane 0 holds V0 again
-  hipError_t e  = hipEventRecord(ev[0], c->stream);
-  for(int i = 0; i < reps && e == hipSuccess; ++i)
-  {
+  const auto whole = [&] {
+    enqueue_variance(c, a);
+    enqueue_iterations(c, a, p->iterations, img, var);
+  };
+  const auto part = [&] {
     if(what == -2)
-    {
-      enqueue_variance(c, a);
-      enqueue_iterations(c, a, p->iterations, img, var);
-    }
+      whole();
     else if(what == -1)
       enqueue_variance(c, a);
     else
       launch_svgf_iteration(c->stream, one, ldsMaxStep);
-  }
-  if(e == hipSuccess) e = hipGetLastError();
-  if(e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  if(e == hipSuccess) e = sync_all(c);
-  float ms = 0.0f;
-  if(e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
-  if(e != hipSuccess)
-    return c->fail(PT_ERR_HIP, "pt_debug_svgf_time: %s", hipGetErrorString(e));
-  *ms_out = ms / float(reps);
-  return check_traversal(c);
+  };
+  // untimed: the whole filter, and before single iterations V0 again, which plane 0 then holds
+  return stage_time(c, "pt_debug_svgf_time", reps, ms_out, part, [&] {
+    whole();
+    if(what >= 0)
+      enqueue_variance(c, a);
+  });
 }
 
 }  // extern "C"

@@ -56,6 +56,28 @@ PT_DN int temporal_constants(const pt_TemporalParams* p, const char** why)
   return PT_OK;
 }
 
+// The constants of one call: the current camera's two inverses, the camera the history was made with (worldToClipH[16] and eyeH[3]; both NULL: there is
+// no history and the fields stay zero) and parameters temporal_constants accepted.  The one place that fills a TemporalConst, for the device path
+// (pt_temporal.hip) and the host builds (tests/cpp/temporal_host.cpp, svgf_host.cpp) alike; words are copied as they are.
+PT_DN TemporalConst temporal_const(const float* viewInverse, const float* projInverse, const float* worldToClipH, const float* eyeH, const pt_TemporalParams* p)
+{
+  TemporalConst k{};
+  for(int i = 0; i < 16; ++i)
+  {
+    k.viewInverse[i] = viewInverse[i];
+    k.projInverse[i] = projInverse[i];
+    if(worldToClipH)
+      k.worldToClipH[i] = worldToClipH[i];
+  }
+  for(int i = 0; i < 3 && eyeH; ++i)
+    k.eyeH[i] = eyeH[i];
+  k.haveHistory = worldToClipH && eyeH ? 1 : 0;
+  k.depthTol    = p->depthTol;
+  k.normalDist2 = p->normalDist2;
+  k.maxHistory  = p->maxHistory;
+  return k;
+}
+
 // row r of mat4_mul (pt_shade.h): ((c0 * v.x + c1 * v.y) + c2 * v.z) + c3 * v.w for the column-major m
 PT_DN float tp_mat4_row(const float* m, int r, float x, float y, float z, float w) { return ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r] * w; }
 PT_DN float tp_dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }  // dot3 of pt_math.h

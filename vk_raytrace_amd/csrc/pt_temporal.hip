@@ -2,7 +2,7 @@
 // (DESIGN.md section 5.3).  The per-pixel arithmetic is pt_temporal.h; this unit holds its kernel, the launch, the history the context keeps and the
 // entry points.  No existing kernel is involved: the stage reads the row-major image the display pass already produces (untile_to_rowmajor), guide
 // planes 1 and 2 and the camera, and writes only the history.
-#include "pt_context.h"
+#include "pt_stage.h"
 #include "pt_temporal.h"
 
 // One block covers a TP_TX x TP_TY tile of the image, one pixel per lane: a wave covers two rows of 32 pixels, so that adjacent lanes read and write
@@ -22,16 +22,14 @@ struct TpArgs {
   TemporalConst k;
 };
 
-PT_DN DnPx tp_px(const float4& v) { return DnPx{v.x, v.y, v.z, v.w}; }
-
 struct TpGlobal {
   const TpArgs& a;
   __device__ size_t at(int x, int y) const { return size_t(y) * size_t(a.w) + size_t(x); }
-  __device__ DnPx   colour(int x, int y) const { return tp_px(a.c[at(x, y)]); }
-  __device__ DnPx   normal(int x, int y) const { return tp_px(a.g1[at(x, y)]); }
-  __device__ DnPx   depth(int x, int y) const { return tp_px(a.g2[at(x, y)]); }
-  __device__ DnPx   histColour(int x, int y) const { return tp_px(a.hc[at(x, y)]); }
-  __device__ DnPx   histGuide(int x, int y) const { return tp_px(a.hg[at(x, y)]); }
+  __device__ DnPx   colour(int x, int y) const { return stage_px(a.c[at(x, y)]); }
+  __device__ DnPx   normal(int x, int y) const { return stage_px(a.g1[at(x, y)]); }
+  __device__ DnPx   depth(int x, int y) const { return stage_px(a.g2[at(x, y)]); }
+  __device__ DnPx   histColour(int x, int y) const { return stage_px(a.hc[at(x, y)]); }
+  __device__ DnPx   histGuide(int x, int y) const { return stage_px(a.hg[at(x, y)]); }
   __device__ float  histLength(int x, int y) const { return a.hn[at(x, y)]; }
 };
 
@@ -57,51 +55,35 @@ static void launch_temporal(const pt_context* c, const TpArgs& a)
                                                 (float2*)c->dHistMoments[r ^ 1].p, a.w, a.h}, a.k);
     return;
   }
-  const dim3 grid((a.w + TP_TX - 1) / TP_TX, (a.h + TP_TY - 1) / TP_TY), block(TP_TX, TP_TY);
-  k_temporal<<<grid, block, 0, c->stream>>>(a);
-}
-
-void temporal_release(pt_context* c)
-{
-  for(int s = 0; s < 2; ++s)
-  {
-    dev_free(c->dHistColour[s]);
-    dev_free(c->dHistGuide[s]);
-    dev_free(c->dHistLength[s]);
-    dev_free(c->dHistMoments[s]);
-    dev_free(c->dSvgfVar[s]);
-  }
-  c->haveHistory = c->histHasMoments = false;
+  k_temporal<<<stage_grid(a.w, a.h, TP_TX, TP_TY), dim3(TP_TX, TP_TY), 0, c->stream>>>(a);
 }
 
 // Everything pt_temporal_accumulate checks, then both history sets allocated and the row-major accumulation image enqueued on the context's stream
 // behind the frames rendered so far; the kernel's arguments in `a`.  Nothing of the history changes here.
 static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalParams* p, TpArgs& a)
 {
-  if(c->width == 0)
-    return c->fail(PT_ERR_STATE, "%s before pt_resize", who);
+  STAGE_TRY(stage_need_image(c, who));
   if(!c->haveCamera)
     return c->fail(PT_ERR_STATE, "%s before pt_set_camera", who);
   if(!c->dGuide[1].p || !c->dGuide[2].p)
     return c->fail(PT_ERR_STATE, "%s: guide planes 1 (normal) and 2 (depth) must be installed (pt_render_guides or pt_set_denoise_guides)", who);
-  if(c->nranks > 1 && !c->haveFull)
-    return c->fail(PT_ERR_STATE, "%s: rank %d of %d holds only its own tiles; gather the image first", who, c->rank, c->nranks);
+  STAGE_TRY(stage_need_full_image(c, who));
   const char* why = "";
-  int         rc  = temporal_constants(p, &why);
+  const int   rc  = temporal_constants(p, &why);
   if(rc != PT_OK)
     return c->fail(rc, "%s: %s", who, why);
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t n = size_t(c->width) * size_t(c->height);
+  const size_t n = stage_pixels(c);
   for(int s = 0; s < 2; ++s)
-    if((rc = dev_alloc(c, c->dHistColour[s], sizeof(float4) * n)) != PT_OK || (rc = dev_alloc(c, c->dHistGuide[s], sizeof(float4) * n)) != PT_OK
-       || (rc = dev_alloc(c, c->dHistLength[s], sizeof(float) * n)) != PT_OK)
-      return rc;
+  {
+    STAGE_TRY(dev_alloc(c, c->dHistColour[s], sizeof(float4) * n));
+    STAGE_TRY(dev_alloc(c, c->dHistGuide[s], sizeof(float4) * n));
+    STAGE_TRY(dev_alloc(c, c->dHistLength[s], sizeof(float) * n));
+  }
   if(c->trackMoments)
     for(int s = 0; s < 2; ++s)
-      if((rc = dev_alloc(c, c->dHistMoments[s], sizeof(float2) * n)) != PT_OK)
-        return rc;
-  if((rc = untile_to_rowmajor(c)) != PT_OK)
-    return rc;
+      STAGE_TRY(dev_alloc(c, c->dHistMoments[s], sizeof(float2) * n));
+  STAGE_TRY(untile_to_rowmajor(c));
   const int r = c->histSet, wr = r ^ 1;
   a.c     = (const float4*)c->dRowMajor.p;
   a.g1    = (const float4*)c->dGuide[1].p;
@@ -114,18 +96,8 @@ static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalPar
   a.hnOut = (float*)c->dHistLength[wr].p;
   a.w     = c->width;
   a.h     = c->height;
-  for(int i = 0; i < 16; ++i)
-  {
-    a.k.viewInverse[i]  = c->scene.camera.viewInverse[i];
-    a.k.projInverse[i]  = c->scene.camera.projInverse[i];
-    a.k.worldToClipH[i] = c->histWorldToClip[i];
-  }
-  for(int i = 0; i < 3; ++i)
-    a.k.eyeH[i] = c->histEye[i];
-  a.k.haveHistory = c->haveHistory ? 1 : 0;
-  a.k.depthTol    = p->depthTol;
-  a.k.normalDist2 = p->normalDist2;
-  a.k.maxHistory  = p->maxHistory;
+  a.k     = temporal_const(c->scene.camera.viewInverse, c->scene.camera.projInverse, c->haveHistory ? c->histWorldToClip : nullptr,
+                           c->haveHistory ? c->histEye : nullptr, p);
   return PT_OK;
 }
 
@@ -135,13 +107,11 @@ int pt_temporal_accumulate(pt_context* c, const pt_TemporalParams* p, float* out
 {
   CTX_CHECK(c);
   TpArgs a;
-  int    rc = prepare_temporal(c, "pt_temporal_accumulate", p, a);
-  if(rc != PT_OK)
-    return rc;
+  STAGE_TRY(prepare_temporal(c, "pt_temporal_accumulate", p, a));
   launch_temporal(c, a);
   HIP_TRY(c, hipGetLastError());
   if(out)
-    HIP_TRY(c, hipMemcpyAsync(out, a.hcOut, sizeof(float4) * size_t(c->width) * size_t(c->height), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, a.hcOut, sizeof(float4) * stage_pixels(c), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, sync_all(c));
   // the set just written is the history now, made with the current camera
   for(int i = 0; i < 16; ++i)
@@ -177,16 +147,10 @@ int pt_temporal_track_moments(pt_context* c, int on)
 int pt_read_temporal_history(pt_context* c, float* rgba32f_out, float* length_out)
 {
   CTX_CHECK(c);
-  if(!c->haveHistory)
-    return c->fail(PT_ERR_STATE, "pt_read_temporal_history: there is no history (no pt_temporal_accumulate since pt_resize / pt_temporal_reset)");
+  STAGE_TRY(stage_need_history(c, "pt_read_temporal_history", false));
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t n = size_t(c->width) * size_t(c->height);
-  if(rgba32f_out)
-    HIP_TRY(c, hipMemcpyAsync(rgba32f_out, c->dHistColour[c->histSet].p, sizeof(float4) * n, hipMemcpyDeviceToHost, c->stream));
-  if(length_out)
-    HIP_TRY(c, hipMemcpyAsync(length_out, c->dHistLength[c->histSet].p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, sync_all(c));
-  return check_traversal(c);
+  const size_t n = stage_pixels(c);
+  return stage_read(c, {{rgba32f_out, c->dHistColour[c->histSet].p, sizeof(float4) * n}, {length_out, c->dHistLength[c->histSet].p, sizeof(float) * n}});
 }
 
 // Measurement access (not part of pt_api.h; tools/temporal_rate.py): the kernel of pt_temporal_accumulate enqueued `reps` times between two events on
@@ -198,31 +162,8 @@ __attribute__((visibility("default"))) int pt_debug_temporal_time(pt_context* c,
   if(!ms_out || reps < 1)
     return c->fail(PT_ERR_INVALID, "pt_debug_temporal_time: null or reps < 1");
   TpArgs a;
-  int    rc = prepare_temporal(c, "pt_debug_temporal_time", p, a);
-  if(rc != PT_OK)
-    return rc;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  HIP_TRY(c, hipEventCreate(&ev[0]));
-  if(hipEventCreate(&ev[1]) != hipSuccess)
-  {
-    (void)hipEventDestroy(ev[0]);
-    return c->fail(PT_ERR_HIP, "pt_debug_temporal_time: hipEventCreate");
-  }
-  launch_temporal(c, a);  // (the kernel the setting of pt_temporal_track_moments selects)
-  hipError_t e = hipEventRecord(ev[0], c->stream);
-  for(int i = 0; i < reps && e == hipSuccess; ++i)
-    launch_temporal(c, a);
-  if(e == hipSuccess) e = hipGetLastError();
-  if(e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  if(e == hipSuccess) e = sync_all(c);
-  float ms = 0.0f;
-  if(e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
-  if(e != hipSuccess)
-    return c->fail(PT_ERR_HIP, "pt_debug_temporal_time: %s", hipGetErrorString(e));
-  *ms_out = ms / float(reps);
-  return check_traversal(c);
+  STAGE_TRY(prepare_temporal(c, "pt_debug_temporal_time", p, a));
+  return stage_time(c, "pt_debug_temporal_time", reps, ms_out, [&] { launch_temporal(c, a); });  // (the kernel the setting of pt_temporal_track_moments selects)
 }
 
 }  // extern "C"
