@@ -19,6 +19,8 @@ Functions (tests/test_float_kat.py holds oracle, compiled reference, the product
   EnvSample's sun-disk direction        shaders/env_sampling.glsl:111-125
   linearTosRGB, sRGBToLinear, toneMapUncharted, toneMapHejlRichard, toneMapACES, toneMap   shaders/tonemapping.glsl:29-105
   rand                                  shaders/random.glsl:59-65, 98-102 (through gen_kat)
+sun_and_sky (shaders/sun_and_sky.glsl) has a generator of its own, gen_sky_kat.py, which takes its sphere directions from sky_dirs() here; EnvSample's sun branch
+as the path loop runs it is in gen_path_kat.py (configurations sky3, sky0).
 The shading state is the 22-float material vector + frame of the function-level probes (oracle/pt_oracle.cpp orc_fill_state): ffnormal = normal.
 
 Conditioning filter, decided by the model alone (never by the code under test): a state is KEPT when the model's float32 evaluation is within
@@ -1008,6 +1010,11 @@ def vec_grid(n, salt, extra):
 AXES = [[1, 0, 0], [0, 1, 0], [0, 0, 1], [-1, 0, 0], [0, -1, 0], [0, 0, -1]]
 
 
+def sky_dirs():
+    """the 1508 directions of the sun & sky probes (gen_sky_kat.py builds its sphere class from them)"""
+    return vec_grid(1500, 13, AXES + [[0.70710678, 0.70710678, 0], [0, -0.70710678, -0.70710678]])
+
+
 def simple_inputs():
     """(name, function, rows, names of the hand-made rows at the end)"""
     # (unit-vector outputs -- the tangent frame, reflect / refract of a unit vector -- are compared by absolute error like the sampled L: a component
@@ -1133,7 +1140,7 @@ def main(path=None):
     rows, hand = tonemap_inputs()
     for name in TONEMAPS:
         out.update(mint(name, wrap(k_tonemap(name)), rows, 0, None, hand, in_key="tonemap_in"))
-    out["sky_dirs"] = vec_grid(1500, 13, AXES + [[0.70710678, 0.70710678, 0], [0, -0.70710678, -0.70710678]])
+    out["sky_dirs"] = sky_dirs()
     path = path or os.path.join(os.path.dirname(os.path.abspath(__file__)), "float_kat.npz")
     with zipfile.ZipFile(path, "w") as z:  # like np.savez_compressed, with a fixed timestamp: the same bytes on every run
         for k, v in out.items():

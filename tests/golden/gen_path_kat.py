@@ -6,7 +6,7 @@ between them: a numpy path tracer for tiny scenes, vectorised over the pixels of
     pathtrace.glsl:97-188              DirectLight: pSelect, light pick, punctual lights, EnvSample, the MIS weight
     pathtrace.glsl:193-343             PathTrace: miss, debug exits, unlit, absorption, emission, NEE, BSDF sample, roulette, OffsetRay, shadow ray
     pathtrace.glsl:348-387             samplePixel: jitter, camera ray, depth of field, firefly clamp
-    env_sampling.glsl:126-134          EnvSample's three draws and the hdrMultiplier
+    env_sampling.glsl:126-134          EnvSample's three draws and the hdrMultiplier; :111-125 its sun branch
     common.glsl:98-113                 OffsetRay (gen_kat.offset_ray: an integer rule on the float32 bits, applied to the float32 rounding of the position)
     random.glsl:34-53, 59-65, 98-102   tea, initRandom, pcg, rand (gen_kat)
 It imports numpy, the standard library and the other generators of this directory only; nothing of oracle/, tests/orc.py, tests/ref.py or vk_raytrace_amd/.
@@ -19,7 +19,11 @@ BSDFs are gen_float_kat's, the environment lookup is gen_tex_kat's footprint and
 The environment's alias table is an INPUT: recorded once from the compiled reference's createEnvironmentAccel (measure_path_kat.py --table ->
 path_kat_env.npz, which holds the environment and the table for the tests too; path_kat.npz does not repeat them).  The camera matrices are inputs too: lookAt / perspectiveRH_ZO with the y flip (src/scene.cpp:629-640),
 inverted in float64 and rounded to float32 here; every leg is given these words.
-Sun & sky stays out of this model: in_use = 0 everywhere.
+Sun & sky: the configurations sky3 and sky0 run with in_use = 1 on the SunAndSky words of sunsky().  The model restates the miss branch (pathtrace.glsl:219-227)
+and EnvSample's sun branch (env_sampling.glsl:111-125, 133: CreateCoordinateSystem on the RAW sun_direction, two draws in one quadrant, pdf = 0.5, the
+hdrMultiplier, the MIS weight against that constant pdf) and calls gen_sky_kat.sun_and_sky for the colour; every branch of that function is a decision of
+the pixel, and a pixel is kept only where gen_sky_kat's conditioning rules hold for every sky colour that feeds it (sky_eval).  Their 24 images are written
+to path_kat_sky.npz with the words; the 39 images without sun & sky stay in path_kat.npz.
 
 Shader quirks the model follows as written (the pixels stay kept: the behaviour is deterministic): a directional light's lightDist is length(-direction) = 1,
 so its shadow ray ends one unit away (pathtrace.glsl:127-136); absorption is set again by the refraction that LEAVES the slab and only zeroed at the next
@@ -37,7 +41,7 @@ Caps asserted here and again by the test: at most 10 % of the pixels of any imag
 
 BREAK: the rules tests/test_path_model.py's docstring lists as broken one at a time to prove that the check can fail (main(path, brk)).
 
-Run:  python tests/golden/gen_path_kat.py   (rewrites path_kat.npz; deterministic, byte-identical on every run)
+Run:  python tests/golden/gen_path_kat.py   (rewrites path_kat.npz and path_kat_sky.npz; deterministic, byte-identical on every run)
 """
 import os
 import sys
@@ -47,12 +51,14 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import gen_float_kat as fk  # noqa: E402
+import gen_sky_kat as sk  # noqa: E402
 import gen_surface_kat as gs  # noqa: E402
 import gen_tex_kat as tk  # noqa: E402
 from gen_kat import offset_ray, tea  # noqa: E402
 
 SPREAD = fk.SPREAD
 EDGE, SEP, TZERO = 1e-4, 1e-4, 2e-6
+SKY_SPREAD = sk.SPREADS["glow"]   # a sky colour inside a path: the widest spread gen_sky_kat needs for a class the sun samples land in (glow, rise)
 W, H = 46, 30            # not a multiple of the 8 x 8 block or the 32-pixel tile
 FRAMES = 3
 INF = 1e32               # globals.glsl:29
@@ -60,13 +66,16 @@ E_RADIANCE, E_WEIGHT, E_RAYDIR = 9, 10, 11   # host_device.h:88-102
 DIRECTIONAL, POINT, SPOT = 0, 1, 2           # host_device.h:211-213
 DEBUG_MODES = (("radiance", E_RADIANCE), ("weight", E_WEIGHT), ("raydir", E_RAYDIR))
 BREAK = ("mis_dropped", "mis_swapped", "pselect_ignored", "env_pdf_one", "nee_no_throughput", "absorb_sign", "absorb_before_emission", "rr_no_eta2", "rr_001", "rr_095",
-         "rr_no_divide", "rr_draw_missing", "clamp_weights", "lerp_1_over_frame", "jitter_frame0", "tea_swapped", "seed_unscaled", "offset_no_flip")
+         "rr_no_divide", "rr_draw_missing", "clamp_weights", "lerp_1_over_frame", "jitter_frame0", "tea_swapped", "seed_unscaled", "offset_no_flip",
+         "sun_pdf_one", "sun_no_hdr", "sun_three_draws", "sun_normalised", "sky_miss_no_throughput")
 TAGS = ("point light", "spot light", "directional light", "nbLights 1", "nbLights 3", "pSelect 0.5, light chosen", "pSelect 1", "environment NEE with MIS",
         "light behind the surface: no shadow ray", "shadow ray occluded", "shadow ray clear", "bounded lightDist", "absorption set on entry",
         "absorption applied inside", "absorption zeroed", "thin-walled sheet", "emissive at depth 0", "emissive at depth > 0", "unlit", "metal", "pbrMode 0",
         "pbrMode 1", "miss at depth 0", "miss later", "pdf <= 0 break", "roulette death after a shadow ray", "roulette death without a shadow ray",
         "maxDepth reached", "maxDepth 0", "frame 0", "frame > 0", "aperture 0", "aperture > 0", "maxSamples 1", "maxSamples 2, ray query", "maxSamples 2, RTX",
-        "clamp engaged", "clamp not engaged")
+        "clamp engaged", "clamp not engaged",
+        "sky at a miss at depth 0", "sky at a later miss", "miss below the horizon (ground blend)", "sun NEE with a clear shadow ray", "sun NEE occluded",
+        "sun NEE behind the surface", "sun NEE inside the disc", "sun NEE in the glow", "sun NEE outside the radius", "nbLights 0")
 TAG = {name: np.uint64(1) << np.uint64(k) for k, name in enumerate(TAGS)}
 
 LIGHT_DTYPE = np.dtype([("direction", "<f4", 3), ("range", "<f4"), ("color", "<f4", 3), ("intensity", "<f4"), ("position", "<f4", 3), ("innerConeCos", "<f4"),
@@ -79,7 +88,20 @@ CONFIGS = {
     "gltf1": dict(nb=1, hdr=0.0, pbr=1, depth=3, aperture=0.06, ms=2, variant=0, firefly=1.0e9, debug=(1, 2, 3)),
     "rtx3": dict(nb=3, hdr=0.75, pbr=1, depth=3, aperture=0.0, ms=2, variant=1, firefly=3.0, debug=(1, 2, 3)),
     "depth0": dict(nb=3, hdr=1.0, pbr=0, depth=0, aperture=0.0, ms=1, variant=0, firefly=2.0, debug=()),   # (a debug frame sets maxDepth itself: it would be disney3's)
+    # Sun & sky in use (sunsky() below) instead of the environment map.  Their images go to path_kat_sky.npz: one file would pass the size limit
+    "sky3": dict(nb=3, hdr=0.8, pbr=0, depth=3, aperture=0.0, ms=1, variant=0, firefly=4.0, debug=(1, 2, 3), sky=True),
+    "sky0": dict(nb=0, hdr=1.0, pbr=1, depth=3, aperture=0.0, ms=1, variant=0, firefly=1.0e9, debug=(1, 2, 3), sky=True),   # no lights: no pSelect draw, every bounce samples the sun
 }
+SKY_CONFIGS = tuple(k for k, c in CONFIGS.items() if c.get("sky"))
+
+
+def sunsky():
+    """the fixture's SunAndSky words (host_device.h:258-281).  sun_direction is NOT a unit vector (EnvSample builds its frame on the raw one, sun_and_sky
+    normalises it) and its rays enter through the ceiling's opening, so both shadow verdicts occur; physically_scaled_sun 0: the physically scaled disc sits
+    at 1.2e-4 in float32 by itself (gen_sky_kat.SPREADS); sun_disk_scale 16 makes the sun 0.74 rad wide: the smoothstep's rise, 1.6 % of the sun draws,
+    is then well-conditioned often enough for its tag, and x * x + y * y of :120 can pass 1 (z = 0); horizon_height 4 puts the horizon at 0.4 above the level, so that rays leaving through the opening
+    end on both sides of it"""
+    return sk.words_of(dict(sun_direction=(0.45, 0.9, 0.25), physically_scaled_sun=0, horizon_height=4.0, horizon_blur=1.5, haze=1.0, sun_disk_scale=16.0))
 
 
 # ---- the fixture scene: 32 triangles ---------------------------------------------------------------------------------------------------------------------
@@ -301,8 +323,53 @@ def make_state(o, V, L, seed, ft):
     return s
 
 
+def sky_eval(S, dirs, mask, rec, ft):
+    """sun_and_sky(_sunAndSky, dir) on the lanes of `mask` (gen_sky_kat's model) -> (colour, gen_sky_kat's branch bits).  Every branch of the function is a
+    decision of the pixel; the pixel is kept only where the function is well-conditioned by gen_sky_kat's two rules: the ray is not within DOT_MARGIN of the
+    sun, and moving the cosines by DOT_NUDGE moves the colour by no more than SPREAD"""
+    n = len(dirs)
+    words = np.ascontiguousarray(np.broadcast_to(S["sunsky"], (n, 24)), np.float32)
+    d = np.where(mask[:, None] & np.isfinite(dirs).all(1)[:, None], dirs, ft(0) + np.array([0.0, 1.0, 0.0], dirs.dtype))
+    with np.errstate(all="ignore"):
+        res, dec, _, cosv = sk.sun_and_sky(words, d, ft)
+        for v in dec.list:
+            rec.decide(mask, v)
+        if ft is np.float64:
+            moved = np.zeros(n)
+            for nudge in (-sk.DOT_NUDGE, sk.DOT_NUDGE):
+                m = sk.measure(sk.sun_and_sky(words, d, ft, None, nudge)[0], res)
+                moved = np.maximum(moved, np.where(np.isnan(m), np.inf, m))
+            rec.need(mask, moved <= SKY_SPREAD, "sky conditioning")
+            rec.need(mask, ~(cosv > 1 - sk.DOT_MARGIN), "ray at the sun")
+        else:
+            rec.need(mask, ~(cosv > 1), "ray at the sun")
+    return res, dec.bits
+
+
+def sun_sample(S, c, rng, env, rec, ft, brk):
+    """EnvSample's sun branch, env_sampling.glsl:111-125, 133 -> (lightDir, radiance, pdf, gen_sky_kat's branch bits)"""
+    n = len(env)
+    ss = S["sunsky"]
+    sd = ss[sk.W_SUN:sk.W_SUN + 3][None]                                                        # :116 the RAW sun_direction: not normalised
+    if brk == "sun_normalised":
+        sd = fk.f32_unit(sd)
+    radius = ft(np.float32(0.00465) * np.float32(10.0)) * ft(ss[sk.W_DISK_S])                   # :114
+    tb = fk.coordinate_system(np.broadcast_to(sd, (n, 3)), ft)                                  # :115-116
+    x = rng.rand(env) * radius                                                                  # :118-120: two draws, one quadrant of the disc's square
+    y = rng.rand(env) * radius
+    if brk == "sun_three_draws":
+        rng.rand(env)
+    z = np.sqrt(np.maximum(ft(0), ft(1) - x * x - y * y))
+    with np.errstate(all="ignore"):
+        light = fk.normalize(tb[:, 0:3] * x[:, None] + tb[:, 3:6] * y[:, None] + sd.astype(ft) * z[:, None])   # :122
+    rad, bits = sky_eval(S, light, env, rec, ft)                                                # :123
+    if brk != "sun_no_hdr":
+        rad = rad * ft(c["hdr"])                                                                # :133
+    return light, rad, ft(1.0 if brk == "sun_pdf_one" else 0.5), bits                           # :124
+
+
 def direct_light(S, c, st, o, d, rng, alive, rec, ft, brk):
-    """pathtrace.glsl:97-188 -> (radiance, lightDir, lightDist, visible)"""
+    """pathtrace.glsl:97-188 -> (radiance, lightDir, lightDist, visible, the lanes that sampled the sun)"""
     n = len(d)
     nb = c["nb"]
     ffn, pos = o[:, 6:9], o[:, 0:3]
@@ -339,19 +406,24 @@ def direct_light(S, c, st, o, d, rng, alive, rec, ft, brk):
             rec.tag(is_light & (typ == t), name)
         rec.tag(is_light, "nbLights 1" if nb == 1 else "nbLights 3")
     env = alive & ~is_light                                                                     # :155-160, env_sampling.glsl:126-134
-    xi = np.stack([rng.rand(env), rng.rand(env), rng.rand(env)], 1)
-    rows = np.zeros((n, 40), np.float32)
-    rows[:, 0:3], rows[:, 3], rows[:, 4] = xi, S["env"].shape[1], S["env"].shape[0]
-    rows[:, 8:40] = S["env_table"].reshape(-1)
-    es, (_, alias, margin) = fk.env_sample(rows, ft)
-    rec.need(env, margin >= SPREAD, "alias choice")
-    size = S["env"].shape[0] * S["env"].shape[1]
-    xs = xi[:, 0].astype(np.float64) * size
-    rec.need(env, np.abs(xs - np.rint(xs)) >= SPREAD, "alias texel")
-    rec.decide(env, alias)
-    erad = env_lookup(S["env"], es[:, 4:6], ft) * ft(c["hdr"])
-    light_dir, contrib = np.where(env[:, None], es[:, 0:3], light_dir), np.where(env[:, None], erad, contrib)
-    light_pdf = np.where(env, ft(1.0) if brk == "env_pdf_one" else es[:, 3], light_pdf)
+    if c.get("sky"):
+        rec.tag(alive & (nb == 0), "nbLights 0")
+        sdir, erad, spdf, sky_bits = sun_sample(S, c, rng, env, rec, ft, brk)
+        light_dir, contrib, light_pdf = np.where(env[:, None], sdir, light_dir), np.where(env[:, None], erad, contrib), np.where(env, spdf, light_pdf)
+    else:
+        xi = np.stack([rng.rand(env), rng.rand(env), rng.rand(env)], 1)
+        rows = np.zeros((n, 40), np.float32)
+        rows[:, 0:3], rows[:, 3], rows[:, 4] = xi, S["env"].shape[1], S["env"].shape[0]
+        rows[:, 8:40] = S["env_table"].reshape(-1)
+        es, (_, alias, margin) = fk.env_sample(rows, ft)
+        rec.need(env, margin >= SPREAD, "alias choice")
+        size = S["env"].shape[0] * S["env"].shape[1]
+        xs = xi[:, 0].astype(np.float64) * size
+        rec.need(env, np.abs(xs - np.rint(xs)) >= SPREAD, "alias texel")
+        rec.decide(env, alias)
+        erad = env_lookup(S["env"], es[:, 4:6], ft) * ft(c["hdr"])
+        light_dir, contrib = np.where(env[:, None], es[:, 0:3], light_dir), np.where(env[:, None], erad, contrib)
+        light_pdf = np.where(env, ft(1.0) if brk == "env_pdf_one" else es[:, 3], light_pdf)
     cosl = fk.dot(light_dir, ffn)
     visible = alive & (cosl > 0)                                                                # :162 (isSubsurface is false: :245)
     rec.need(alive, np.abs(cosl.astype(np.float64)) >= SPREAD, "light side")
@@ -365,8 +437,15 @@ def direct_light(S, c, st, o, d, rng, alive, rec, ft, brk):
         mis = np.maximum(ft(0), a * a / (b * b + a * a))                                         # :176, pbr_disney.glsl:224-229
         mis = np.where(is_light, ft(1), ft(1) if brk == "mis_dropped" else mis)
         li = (mis * np.abs(cosl))[:, None] * f * contrib / light_pdf[:, None]                    # :178
-    rec.tag(visible & env, "environment NEE with MIS")
-    return np.where(visible[:, None], li, ft(0)), light_dir, dist, visible
+    if c.get("sky"):
+        bit = lambda name: (sky_bits & sk.BIT[name]) != 0  # noqa: E731
+        rec.tag(alive & env & ~visible, "sun NEE behind the surface")
+        rec.tag(visible & env & bit("inside the sun radius") & ~bit("smoothstep 0"), "sun NEE inside the disc")
+        rec.tag(visible & env & bit("inside the sun radius") & bit("smoothstep 0"), "sun NEE in the glow")
+        rec.tag(visible & env & bit("outside the sun radius"), "sun NEE outside the radius")
+    else:
+        rec.tag(visible & env, "environment NEE with MIS")
+    return np.where(visible[:, None], li, ft(0)), light_dir, dist, visible, env & bool(c.get("sky"))
 
 
 def path_trace(S, c, org, dirs, rng, rec, ft, debug, max_depth, brk):
@@ -388,6 +467,11 @@ def path_trace(S, c, org, dirs, rng, rec, ft, debug, max_depth, brk):
         miss = alive & (tri < 0)                                                                           # :204-228
         if debug:
             val = {E_RADIANCE: radiance, E_WEIGHT: thr, E_RAYDIR: (d_ray + ft(1)) * ft(0.5)}[debug] if last else np.zeros((n, 3), ft)
+        elif c.get("sky"):                                                                                 # :219-220, :227
+            env, sky_bits = sky_eval(S, d_ray, miss, rec, ft)
+            val = radiance + env * ft(c["hdr"]) * (ft(1) if brk == "sky_miss_no_throughput" else thr)
+            rec.tag(miss, "sky at a miss at depth 0" if depth == 0 else "sky at a later miss")
+            rec.tag(miss & ((sky_bits & sk.BIT["below the horizon: ground blend"]) != 0), "miss below the horizon (ground blend)")
         else:
             env = env_lookup(S["env"], fk.spherical_uv(d_ray, ft), ft)
             val = radiance + env * ft(c["hdr"]) * thr
@@ -419,7 +503,7 @@ def path_trace(S, c, org, dirs, rng, rec, ft, debug, max_depth, brk):
             thr = np.where(alive[:, None], thr * np.exp(sign * absorb * t.astype(ft)[:, None]), thr)       # :274
         rec.tag(alive & (absorb != 0).any(1), "absorption applied inside")
         st = make_state(o, -d_ray, -d_ray, rng.s, ft)
-        vrad, ldir, ldist, visible = direct_light(S, c, st, o, d_ray, rng, alive, rec, ft, brk)       # :277
+        vrad, ldir, ldist, visible, sun_nee = direct_light(S, c, st, o, d_ray, rng, alive, rec, ft, brk)       # :277
         if brk != "nee_no_throughput":
             vrad = vrad * thr                                                                              # :278
         st.seed = rng.s
@@ -468,6 +552,8 @@ def path_trace(S, c, org, dirs, rng, rec, ft, debug, max_depth, brk):
         rec.decide(shadow, lit)
         rec.tag(shadow & ~lit, "shadow ray occluded")
         rec.tag(lit, "shadow ray clear")
+        rec.tag(shadow & ~lit & sun_nee, "sun NEE occluded")
+        rec.tag(lit & sun_nee, "sun NEE with a clear shadow ray")
         rec.tag(shadow & (ldist < ft(1e30)), "bounded lightDist")
         radiance = np.where(lit[:, None], radiance + vrad, radiance)
         draw = alive & visible if brk == "rr_draw_missing" else alive                                      # :335-337
@@ -568,7 +654,7 @@ def load_env_table():
 def mint(brk=None):
     scene = build_scene()
     table = load_env_table()
-    S = dict(scene=scene, lights=lights(), env=environment(), env_table=table, geometry={ft: Geometry(scene, ft) for ft in (np.float64, np.float32)})
+    S = dict(scene=scene, lights=lights(), env=environment(), env_table=table, sunsky=sunsky(), geometry={ft: Geometry(scene, ft) for ft in (np.float64, np.float32)})
     vi, pi, fd = camera(W / H)
     cam = dict(viewInverse=vi, projInverse=pi, focalDist=fd)
     out = dict(scene)
@@ -593,7 +679,21 @@ def mint(brk=None):
                 out["img_" + name], out["kept_" + name], out["tags_" + name] = v64.reshape(H, W, 3), (ok & close(v32, v64)).reshape(H, W), tg.reshape(H, W)
                 names.append(name)
     out["image_names"] = np.array(names)
+    out["sunsky"] = S["sunsky"]
     return out
+
+
+def split(out):
+    """-> (what path_kat.npz holds, what path_kat_sky.npz holds: the images of SKY_CONFIGS, their cfg_ words and the SunAndSky words).  tests/path_kat_io.py
+    load() puts them together again"""
+    is_sky = lambda k: k.split("_", 1)[-1].split("_")[0] in SKY_CONFIGS and k.split("_", 1)[0] in ("img", "kept", "tags", "cfg")  # noqa: E731
+    base = {k: v for k, v in out.items() if not is_sky(k) and k != "sunsky"}
+    sky = {k: v for k, v in out.items() if is_sky(k)}
+    base["image_names"] = np.array([n for n in out["image_names"] if n.split("_")[0] not in SKY_CONFIGS])
+    base["config_names"] = np.array([n for n in out["config_names"] if n not in SKY_CONFIGS])
+    sky["sky_image_names"] = np.array([n for n in out["image_names"] if n.split("_")[0] in SKY_CONFIGS])
+    sky["sky_config_names"], sky["sunsky"] = np.array(SKY_CONFIGS), out["sunsky"]
+    return base, sky
 
 
 def check_caps(out, report=False):
@@ -622,8 +722,9 @@ def main(path=None, brk=None, caps=True):
         worst, counts = check_caps(out, report=True)
         print(f"worst image drops {worst:.2%}; fewest kept pixels of a branch class: {TAGS[int(counts.argmin())]} {counts.min()}")
     path = path or os.path.join(HERE, "path_kat.npz")
-    gs.write_npz(path, out)
-    print("wrote", path, os.path.getsize(path), "bytes,", len(out["image_names"]), "images of", W, "x", H)
+    for p, part in zip((path, path[:-4] + "_sky.npz"), split(out)):
+        gs.write_npz(p, part)
+        print("wrote", p, os.path.getsize(p), "bytes,", sum(k.startswith("img_") for k in part), "images of", W, "x", H)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@
       the model of gen_path_kat.py takes it as an input.
   python tests/golden/measure_path_kat.py            (after gen_path_kat.py)
       runs oracle/_ref/libref.so (pathtrace.comp / pathtrace.rgen compiled by oracle/ref_glue/; needs the reference tree) on every configuration of
-      tests/golden/path_kat.npz and writes, per image, the maximum over the KEPT pixels of |ref - f64| / max(1, |f64|) into tests/golden/path_kat_tol.json, with
+      tests/golden/path_kat.npz and path_kat_sky.npz (the sun & sky configurations) and writes, per image, the maximum over the KEPT pixels of |ref - f64| / max(1, |f64|) into tests/golden/path_kat_tol.json, with
       the pixel counts and the date.  The test's bound for every leg is 4 x that maximum (the factor of the other model tests: the legs differ from the reference
       by the rounding of libm against ocml, a few ulps per call, not by a rule); an image the reference reproduces exactly is held to equality.  Guard rail (the
       project's parity bar, bench.py's per-pixel L2 of 1e-3): a recorded maximum above 1e-3 rejects the fixture.  Never taken from the product.

@@ -21,11 +21,15 @@ def generator():
 
 
 def load(path=None):
-    """the fixture, with the environment and its recorded alias table (path_kat_env.npz: env, env_table, env_integral, env_average)"""
+    """the fixture: path_kat.npz and path_kat_sky.npz as one (image_names and config_names list both), with the environment and its recorded alias table
+    (path_kat_env.npz: env, env_table, env_integral, env_average)"""
     out = {}
-    for p in (os.path.join(GOLDEN, "path_kat_env.npz"), path or os.path.join(GOLDEN, "path_kat.npz")):
+    path = path or os.path.join(GOLDEN, "path_kat.npz")
+    for p in (os.path.join(GOLDEN, "path_kat_env.npz"), path, path[:-4] + "_sky.npz"):   # (_sky: the images of the sun & sky configurations, and the SunAndSky words)
         with np.load(p) as z:
             out.update({k: z[k] for k in z.files})
+    out["image_names"] = np.concatenate([out["image_names"], out["sky_image_names"]])
+    out["config_names"] = np.concatenate([out["config_names"], out["sky_config_names"]])
     return out
 
 
@@ -47,8 +51,12 @@ def config(kat, name, debug=0, depth=None):
     from tests.common import Config
     nb, hdr, pbr, cdepth, aperture, ms, variant, firefly = (float(x) for x in kat["cfg_" + name])
     w, h = (int(x) for x in kat["size"])
-    sun = hd.default_sun_and_sky()
-    sun.in_use = 0
+    if name in kat["sky_config_names"]:   # sun & sky in use: the fixture's words, to every leg
+        sun = hd.SunAndSky.from_buffer_copy(np.ascontiguousarray(kat["sunsky"], np.float32).tobytes())
+        assert sun.in_use == 1
+    else:
+        sun = hd.default_sun_and_sky()
+        sun.in_use = 0
     cfg = Config(fixture_scene(kat, int(nb)), kat["env"], w, h, depth=int(cdepth) if depth is None else depth, pbr=int(pbr), sunsky=sun, debug=debug,
                  max_samples=int(ms), hdr_multiplier=hdr, firefly=firefly, variant=int(variant))
     cam = hd.SceneCamera()

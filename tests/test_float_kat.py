@@ -23,7 +23,7 @@ Oracle and reference only, because the product has no such FUNCTION (the entry a
   * EnvSample's sun-disk direction (env_sampling.glsl:111-125): written inline in shade_path (pt_shade.h); reached through the sun & sky frames of
     tests/test_trace_host.py / tests/test_gpu_parity.py, bit-identical to the oracle, which IS held to the model here.  (The rest of DirectLight -- pSelect, the
     light pick, the punctual lights, the environment NEE, lightPdf and the MIS weight -- has a per-pixel expectation of its own: tests/golden/gen_path_kat.py,
-    tests/test_path_model.py, tests/test_path_gpu.py.  Sun & sky stays out of that model too.)
+    tests/test_path_model.py, tests/test_path_gpu.py -- whose sky3 and sky0 configurations run with sun & sky in use and hold this inline code to the model.)
   * step, clamp, sign, fract, mod, atan(y, x), roundEven: all in ref_glue/glsl_compat.h (what the reference's shaders run on), step and clamp in
     oracle/glsl_math.h.  The oracle and the product write the others inline where the shaders call them -- floor / fract in the texture and environment
     filters (orc_scene.h sample_texture / sample_env, pt_surface.h:51-115), sign / mod / atan inside sun_and_sky and GetSphericalUv (pt_atan2) -- so their
@@ -34,8 +34,9 @@ Oracle and reference only, because the product has no such FUNCTION (the entry a
 The shaders use no transpose(), inverse() or mat3(mat4): no side defines them, there is nothing to probe.
 The intersection arithmetic (tri_test, world_tri, the box tests, enter_instance: csrc/pt_trace.h) is not shading math and is OUT OF SCOPE here: it has an exact
 rational model of its own, tests/golden/gen_trace_kat.py, held by tests/test_trace_model.py and tests/test_trace_gpu.py.
-sun_and_sky.glsl (603 lines of tables) is OUT OF SCOPE for the float64 model: it gets the bit-identity probes only (host build == oracle, device == host
-build, six variants x 1508 directions).
+sun_and_sky.glsl has a float64 model of its own, tests/golden/gen_sky_kat.py, held by tests/test_sky_model.py and tests/test_sky_gpu.py on 23 settings rows
+(every branch of the function) x sphere, horizon, sun-fan and at-the-sun directions; the bit-identity probes here (host build == oracle, device == host build,
+six variants x 1508 directions) are rows of that fixture too.
 "Thin-walled from inside" (dot(ffnormal, normal) < 0 -> F = 0, discriminant = 0 in DisneySample / PbrSample) is UNREACHABLE through the function-level
 probes: they all set ffnormal = normal, as the existing orc_ / ref_bsdf_sample do; the edge rows of that name vary eta and the thin-walled flag only.  That
 branch is covered by whole frames alone (thin-walled materials of synth.feature_box, bit-identical across the legs).

@@ -1,4 +1,4 @@
-"""The device's path loop against the fixture of tests/golden/gen_path_kat.py (see tests/test_path_model.py): all 39 images of 46 x 30 pixels rendered by the
+"""The device's path loop against the fixture of tests/golden/gen_path_kat.py (see tests/test_path_model.py): all 63 images of 46 x 30 pixels (the 24 of sky3 and sky0 with sun & sky in use) rendered by the
 default launch policy (k_tail at this size) and by the staged chain k_generate -> k_closest_* -> k_shade -> k_shadow_p -> k_accumulate (PT_TUNE tail=0), flat and
 two-level.  Every image is bit-identical to the product's host build on every pixel and within the model's bound (4 x the compiled reference's recorded error)
 on the kept pixels.  Only the committed fixture is read here; the model does not run."""

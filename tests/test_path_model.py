@@ -1,7 +1,13 @@
 """The path loop -- camera_ray, shade_path after the material resolve, finish_bounce_core, accumulate_pixel -- held to the independent float64 model of
-tests/golden/gen_path_kat.py, pixel by pixel, through whole frames: 39 images of 46 x 30 pixels of a 32-triangle box.  Each of the three configurations that trace a bounce (disney3, gltf1, rtx3) has twelve:
+tests/golden/gen_path_kat.py, pixel by pixel, through whole frames: 63 images of 46 x 30 pixels of a 32-triangle box.  Each of the five configurations that trace a bounce (disney3, gltf1, rtx3, and
+with sun & sky in use sky3 and sky0) has twelve:
 the accumulation after 1, 2 and 3 frames and single frames in the last-bounce debug modes eRadiance, eWeight, eRayDir at maxDepth 1, 2, 3.  depth0 (maxDepth 0)
 has the three accumulation images only: a debug frame sets maxDepth itself.
+sky3 (three lights, hdrMultiplier 0.8, pSelect 0.5) and sky0 (nbLights 0: no pSelect draw, every bounce samples the sun, with two draws where the HDR takes
+three) run with SunAndSky::in_use = 1 on the fixture's own SunAndSky words (path_kat_sky.npz holds them and the 24 images): the miss branch
+(pathtrace.glsl:219-227), EnvSample's sun branch (env_sampling.glsl:111-125, 133: frame on the RAW sun_direction, one quadrant, pdf 0.5, hdrMultiplier) and the
+MIS weight against that constant pdf, all through the sky model of gen_sky_kat.py (tests/test_sky_model.py).  This is what reaches the sun-disk code that
+shade_path writes inline.
 
 Legs: the CPU oracle, the compiled reference (pathtrace.comp / pathtrace.rgen), the product's host build flat and two-level.  Each is within 4 x the error the
 compiled reference shows against the model (tests/golden/path_kat_tol.json, written by measure_path_kat.py, never taken from the product) on the kept pixels, and
@@ -27,13 +33,24 @@ it; the bound is 4 x the recorded maximum, at most 3.8e-5.  Largest error of the
     tea arguments swapped                                          1.10e+01 gltf1_acc1 (36 of 39 images fail)
     seed not scaled by maxSamples                                  5.48e+00 gltf1_acc2 (2 of 39 images fail)
     offset normal not flipped for transmitted rays                 9.31e+00 gltf1_acc1 (27 of 39 images fail)
+and, on the 24 images of sky3 and sky0 (bounds at most 2.2e-4):
+    sun pdf 1 for 0.5                                              9.67e-01 sky0_radiance3 (20 of 24 sun & sky images fail)
+    sun NEE without hdrMultiplier                                  2.00e-01 sky3_radiance1 (10 of 24 sun & sky images fail: sky0 has hdrMultiplier 1)
+    three draws for the sun sample instead of two                  1.50e+02 sky0_acc3 (24 of 24 sun & sky images fail)
+    sun_direction normalised before the frame                      1.62e+00 sky0_acc1 (20 of 24 sun & sky images fail)
+    sky at a miss without throughput                               2.92e+00 sky3_acc1 (6 of 24 sun & sky images fail: the accumulation images; a debug frame returns no sky)
 (The glass slab is emissive so that an emission add occurs while absorption is pending: without that, applying the absorption before the add moves no image.)
 The same breaks planted in the product's csrc/pt_shade.h (host build only, scratch copy) against the committed fixture:
     MIS weight dropped                                             4.83e+00 disney3_radiance1 (20 of 39 images fail)
     roulette without eta * eta                                     7.70e+00 gltf1_acc1 (27 of 39 images fail)
     offset normal not flipped for transmitted rays                 1.26e+01 gltf1_acc1 (27 of 39 images fail)
     RNG state not written back at the last-bounce debug exit       6.77e+00 gltf1_weight2 (18 of 39 images fail)
-The last one is the bug these tests found in shade_path: the exit returned without storing the seed, so the second sample of a frame continued from the seed
+    sun pdf 1 for 0.5                                              4.94e-01 sky0_radiance3 (20 of 24 sun & sky images fail)
+    sun NEE without hdrMultiplier                                  2.50e-01 sky3_radiance1 (10 of 24 sun & sky images fail)
+    sun_direction normalised before the frame                      1.00e+00 sky0_acc1 (20 of 24 sun & sky images fail)
+    sky at a miss without throughput                               1.22e+00 sky3_acc1 (6 of 24 sun & sky images fail)
+The sun & sky images found nothing in the product: every leg is within its bound on them and all are bit-identical.
+"RNG state not written back" is the bug these tests found in shade_path: the exit returned without storing the seed, so the second sample of a frame continued from the seed
 the bounce began with (host build and device alike; oracle and reference were right).  All eighteen debug images of the two maxSamples = 2 configurations,
 ray query and RTX, fail on it, and the host build differs from the oracle on 774 of 1380 pixels of rtx3_radiance1.  pt_shade.h now stores the seed there.
 """
@@ -83,13 +100,18 @@ def host_out(kat):
 def test_generator_is_independent_and_deterministic(tmp_path, gen):
     src = open(os.path.join(io.GOLDEN, "gen_path_kat.py")).read()
     imports = re.findall(r"^\s*(?:from|import)\s+([\w.]+)", src, re.M)
-    assert set(imports) <= {"os", "sys", "numpy", "gen_kat", "gen_float_kat", "gen_surface_kat", "gen_tex_kat"}, imports   # nothing of oracle/, tests/, vk_raytrace_amd/
+    assert set(imports) <= {"os", "sys", "numpy", "gen_kat", "gen_float_kat", "gen_sky_kat", "gen_surface_kat", "gen_tex_kat"}, imports   # nothing of oracle/, tests/, vk_raytrace_amd/
     assert len(re.findall(r"#.*?:\d+(-\d+)?", src)) >= 30   # shader lines cited per rule
     out = str(tmp_path / "again.npz")
     gen.main(out)
-    assert open(out, "rb").read() == open(os.path.join(io.GOLDEN, "path_kat.npz"), "rb").read()
-    largest = max(os.path.getsize(os.path.join(io.GOLDEN, f)) for f in os.listdir(io.GOLDEN) if f != "path_kat.npz")
-    assert os.path.getsize(out) <= largest
+    # both files: the 39 images without sun & sky (expectations and kept masks as they were before sky3 and sky0 joined) and the 24 with it
+    # (When sky3 and sky0 were added, the arrays of the re-minted path_kat.npz were compared once with those of the file committed before: all 142 are equal byte
+    # for byte except tag_names, which grew from 38 to 48 entries; the 39 entries of path_kat_tol.json did not change either.)
+    mine = ("path_kat.npz", "path_kat_sky.npz")
+    largest = 974864   # bytes of display_kat.npz, the largest file of tests/golden/ before the sun & sky fixtures were added
+    for again, committed in zip((out, out[:-4] + "_sky.npz"), mine):
+        assert open(again, "rb").read() == open(os.path.join(io.GOLDEN, committed), "rb").read(), committed
+        assert os.path.getsize(again) <= largest
 
 
 def test_fixture_meets_the_caps(kat, gen, tol):
@@ -99,7 +121,9 @@ def test_fixture_meets_the_caps(kat, gen, tol):
     assert worst <= 0.10 and (counts >= 50).all()
     assert list(kat["tag_names"]) == list(gen.TAGS)
     assert np.array_equal(kat["env"], gen.environment()) and kat["env_table"].shape == (kat["env"].shape[0] * kat["env"].shape[1], 4)
-    for cn in ("disney3", "gltf1", "rtx3"):   # every configuration that traces a bounce has all twelve observables
+    assert np.array_equal(kat["sunsky"], gen.sunsky()) and kat["sunsky"].view(np.int32)[23] == 1 and list(kat["sky_config_names"]) == list(gen.SKY_CONFIGS)
+    assert kat["cfg_sky0"][0] == 0 and kat["cfg_sky3"][0] == 3 and kat["cfg_sky3"][1] > 0 and len(kat["image_names"]) == 63
+    for cn in ("disney3", "gltf1", "rtx3", "sky3", "sky0"):   # every configuration that traces a bounce has all twelve observables
         assert {f"{cn}_acc{k}" for k in (1, 2, 3)} | {f"{cn}_{m}{k}" for m in ("radiance", "weight", "raydir") for k in (1, 2, 3)} <= set(kat["image_names"])
     for name in kat["image_names"]:
         assert np.isfinite(kat["img_" + name][kat["kept_" + name]]).all()
