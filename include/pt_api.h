@@ -302,6 +302,42 @@ int pt_svgf_history(pt_context* ctx, const pt_SvgfParams* params, float* rgba32f
  * form.) */
 int pt_tonemap_svgf(pt_context* ctx, const pt_SvgfParams* params, const pt_Tonemapper* tm, uint8_t* rgba8_out);
 
+/* ---- motion of moving instances (no reference counterpart) -------------------------------------------------------------------------------------
+ * pt_temporal_accumulate reprojects as if the world stood still.  After pt_update_instances a surface that slides or turns within itself passes its
+ * depth and normal tests at the same pixel and blends the history of another surface point.  These entry points close that: a per-pixel instance
+ * plane (the node index of the first hit), the instance transforms the history was made with, kept by the context, and a form of the temporal step
+ * that sends the current point and normal of a moved instance back to where they were before it reprojects them.  DESIGN.md section 5.5 has the
+ * definition, csrc/pt_motion.h the one fp32 operation sequence host and device share.  Typical use per frame of a moving scene:
+ * pt_update_instances, pt_set_camera, pt_render_instance_plane (in place of pt_render_guides), pt_render_frame (frame 0),
+ * pt_temporal_accumulate_moving, pt_tonemap_svgf.  No render kernel captures anything for it. */
+
+#define PT_INSTANCE_NONE 0xffffffffu /* instance plane: the pixel's first camera ray hits nothing */
+
+/* No reference counterpart.  pt_render_guides with the instance plane written besides: one first-hit pass of a kernel of its own that writes, per
+ * pixel, the node index of the hit of pt_render_guides' ray (what pt_RayHit::instanceID reports for it; PT_INSTANCE_NONE for a miss) into the
+ * context's instance plane and the guide planes selected by guide_planes, bit for bit what pt_render_guides writes there.  guide_planes may be 0:
+ * only the instance plane.  Asynchronous, side effects and errors as pt_render_guides, except that a mask of 0 is legal. */
+int pt_render_instance_plane(pt_context* ctx, uint32_t guide_planes, float miss_depth);
+
+/* No reference counterpart.  Installs a caller-supplied instance plane: width * height words, row-major, copied before the call returns; any bit
+ * pattern is legal (a word that is no node index means "no instance").  ids == NULL drops the plane.  PT_ERR_STATE before pt_resize; a pt_resize to
+ * another size drops the plane. */
+int pt_set_instance_plane(pt_context* ctx, const uint32_t* ids);
+
+/* No reference counterpart.  Copies the instance plane (width * height words) out, whether pt_render_instance_plane or pt_set_instance_plane put it
+ * there.  Synchronous like pt_read_denoise_guides.  PT_ERR_STATE: before pt_resize; no plane is installed.  ids_out == NULL: PT_ERR_INVALID. */
+int pt_read_instance_plane(pt_context* ctx, uint32_t* ids_out);
+
+/* No reference counterpart.  pt_temporal_accumulate for a scene whose nodes moved since the history was made (pt_update_instances): a pixel whose
+ * instance plane entry names a node whose world matrix changed takes its point and its normal through that node's motion (history transform o inverse
+ * of the current one; the inverse transpose for the normal) before the reprojection and the tap tests; every other pixel, and everything that is
+ * stored, is pt_temporal_accumulate's.  With no node moved the result is pt_temporal_accumulate's bit for bit.  Both forms leave the instance
+ * transforms with the history, and either may follow the other; pt_temporal_track_moments applies to both.  Errors: everything
+ * pt_temporal_accumulate refuses, and PT_ERR_STATE without an instance plane, without a scene, and when the history was made with another number of
+ * instances than the scene has (the scene was replaced: pt_temporal_reset).  On every refusal nothing is launched and the history is untouched.
+ * (Not provided: deforming meshes, moving lights or materials, motion seen through reflection or refraction.) */
+int pt_temporal_accumulate_moving(pt_context* ctx, const pt_TemporalParams* params, float* rgba32f_out);
+
 /* Test access to the image the display pass samples: builds the offscreen image of a disp_width x disp_height viewport and its full mip chain exactly
  * as pt_tonemap_zoom does with auto-exposure on, and copies level `level` (RGBA32F, row-major) to rgba32f_out, its extent to *width / *height (each may
  * be NULL).  Returns the number of levels (>= 1), or a negative pt_Result. */

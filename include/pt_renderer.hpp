@@ -141,6 +141,16 @@ public:
   bool temporalAccumulate(const pt_TemporalParams& p, float* rgba32f = nullptr) { return check(pt_temporal_accumulate(m_ctx, &p, rgba32f)); }
   bool temporalReset() { return check(pt_temporal_reset(m_ctx)); }
   bool readTemporalHistory(float* rgba32f, float* length) { return check(pt_read_temporal_history(m_ctx, rgba32f, length)); }
+  // motion of moving instances (no reference counterpart): after updateInstances, renderInstancePlane in place of renderGuides
+  // (the same pass; guidePlanes may be 0) and temporalAccumulateMoving in place of temporalAccumulate -- pixels of a node that moved take their point and
+  // normal through its motion before they are reprojected.  The plane holds node indices (width * height words; PT_INSTANCE_NONE: nothing hit).
+  bool renderInstancePlane(uint32_t guidePlanes = PT_GUIDES_BASECOLOR | PT_GUIDES_NORMAL | PT_GUIDES_DEPTH, float missDepth = 1.0e30f)
+  {
+    return check(pt_render_instance_plane(m_ctx, guidePlanes, missDepth));
+  }
+  bool setInstancePlane(const uint32_t* ids) { return check(pt_set_instance_plane(m_ctx, ids)); }
+  bool readInstancePlane(uint32_t* ids) { return check(pt_read_instance_plane(m_ctx, ids)); }
+  bool temporalAccumulateMoving(const pt_TemporalParams& p, float* rgba32f = nullptr) { return check(pt_temporal_accumulate_moving(m_ctx, &p, rgba32f)); }
   // variance-guided filter of the history (no reference counterpart): with trackMoments(true) temporalAccumulate also keeps the
   // luminance moments, from which svgfVariance estimates a per-pixel variance and svgfHistory / tonemapSvgf filter the history with a luminance stop
   // measured in standard deviations.  A change of trackMoments drops the history.

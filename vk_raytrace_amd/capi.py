@@ -21,6 +21,7 @@ PT_QUERY_CHUNK = 1 << 20  # records per staging buffer of the host-pointer path
 PT_DENOISE_GUIDES = 3  # guide planes of the denoiser (include/pt_types.h)
 PT_DENOISE_DEMODULATE = 1  # pt_DenoiseParams.flags
 PT_GUIDES_BASECOLOR, PT_GUIDES_NORMAL, PT_GUIDES_DEPTH = 1, 2, 4  # pt_render_guides plane mask (include/pt_api.h): planes 0, 1, 2
+PT_INSTANCE_NONE = 0xFFFFFFFF  # instance plane (pt_render_instance_plane): the pixel's first camera ray hits nothing
 PT_DISPLAY_RING = 8  # images pt_tonemap_begin may have pending (include/pt_api.h)
 PT_FN = {"sin": 0, "cos": 1, "tan": 2, "asin": 3, "acos": 4, "atan2": 5, "exp": 6, "log": 7, "pow": 8}
 PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_ERR_STATE, PT_ERR_OOM, PT_ERR_UNAVAILABLE = 0, -1, -2, -3, -4, -5, -6
@@ -72,6 +73,10 @@ API = [
     ("pt_svgf_variance", C.c_int, [_P, C.POINTER(hd.SvgfParams), _P]),
     ("pt_svgf_history", C.c_int, [_P, C.POINTER(hd.SvgfParams), _P, _P]),
     ("pt_tonemap_svgf", C.c_int, [_P, C.POINTER(hd.SvgfParams), C.POINTER(hd.Tonemapper), _P]),
+    ("pt_render_instance_plane", C.c_int, [_P, C.c_uint32, C.c_float]),
+    ("pt_set_instance_plane", C.c_int, [_P, _P]),
+    ("pt_read_instance_plane", C.c_int, [_P, _P]),
+    ("pt_temporal_accumulate_moving", C.c_int, [_P, C.POINTER(hd.TemporalParams), _P]),
     ("pt_debug_display_level", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_local_shard", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_scatter_shards", C.c_int, [_P, _P, C.c_int]),
@@ -116,6 +121,7 @@ DEBUG_API = [
     ("pt_debug_denoise_time", C.c_int, [_P, C.POINTER(hd.DenoiseParams), C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_denoise.hip: (ctx, params, reps, ms per run out): the filter alone, device events
     ("pt_debug_guides_time", C.c_int, [_P, C.c_uint32, C.c_float, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_guides.hip: (ctx, planes, miss_depth, reps, ms per run out): the guide pass alone, device events
     ("pt_debug_temporal_time", C.c_int, [_P, C.POINTER(hd.TemporalParams), C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_temporal.hip: (ctx, params, reps, ms per run out): the temporal kernel alone, device events
+    ("pt_debug_motion_time", C.c_int, [_P, C.POINTER(hd.TemporalParams), C.c_int, C.c_uint32, C.c_float, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_temporal.hip: (ctx, params, part (0 instance pass, 1 moving temporal kernel), guide planes, miss_depth, reps, ms per run out), device events
     ("pt_debug_svgf_lds", C.c_int, [_P, C.c_int]),  # csrc/pt_svgf.hip: (ctx, largest step staged in LDS; negative: the default) -> the value in force
     ("pt_debug_svgf_time", C.c_int, [_P, C.POINTER(hd.SvgfParams), C.c_int, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_svgf.hip: (ctx, params, part (-2 whole, -1 variance, i: iteration i), reps, ms per run out), device events
     ("pt_debug_bounce_counts", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[max_bounces][16], max_bounces) -> staged bounces of the newest finished launch sequence

@@ -130,6 +130,11 @@ struct pt_context {
   int      histSet     = 0;      // the set that holds the history (the next call reads it and writes the other)
   bool     haveHistory = false;
   float    histWorldToClip[16] = {0}, histEye[3] = {0, 0, 0};
+  // motion of moving instances (pt_motion.hip): the instance plane (one word per pixel; pt_resize and pt_destroy free it), the
+  // objectToWorld and worldToObject words of every instance as they were when the history was made (24 per instance, stored by every accumulate call) and
+  // the motion table of the call in flight
+  DevBuf   dInstPlane, dMotionTable;
+  std::vector<float> histInst;
   // variance-guided filter (pt_svgf.hip): with trackMoments the history has a fourth image, the luminance moments (float2, twice like the others);
   // histHasMoments: the history that is held was made while tracking was on.  dSvgfVar: the filter's two variance planes, allocated on first use.
   DevBuf   dHistMoments[2], dSvgfVar[2];
@@ -197,6 +202,10 @@ struct TemporalMArgs {  // pt_svgf.hip: k_temporal_m, the temporal kernel that a
   int           w, h;
 };
 void       launch_temporal_m(hipStream_t stream, const TemporalMArgs& a, const TemporalConst& k);
+struct MotionRec;
+// pt_motion.hip: the temporal kernels of pt_temporal_accumulate_moving (a.hm == NULL: the one without the moments image) and the timing of its instance pass
+void       launch_temporal_moving(hipStream_t stream, const TemporalMArgs& a, const TemporalConst& k, const uint32_t* ids, const MotionRec* table, uint32_t numInstances);
+int        debug_instances_time(pt_context* c, uint32_t planes, float missDepth, int reps, float* ms_out);
 void       refresh_scene_ptrs(pt_context* c);
 int        upload_instances(pt_context* c);
 std::vector<InstanceRec> effective_instances(const pt_context* c);  // the instance records as the kernels see them

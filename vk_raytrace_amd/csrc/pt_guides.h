@@ -105,11 +105,9 @@ struct GuidePixel {
 // planes: PT_GUIDES_* mask of the planes wanted (the surface is only reconstructed for base colour or normal).  A hit gives (albedo, 1),
 // ((normal + 1) / 2, 1) -- the eNormal encoding -- and (t, 0, 0, 0); a miss (0, 0, 0, 1) twice, what a debug frame with maxDepth >= 2 accumulates,
 // and (missDepth, 0, 0, 0).  No clamp, no accumulation, no environment, no BSDF.
-template <bool TWO>
-PT_DEV void guide_pixel(const DeviceScene& S, int W, int H, int px, int py, uint32_t planes, float missDepth, uint32_t* stack, Counters* counters, GuidePixel& out)
+PT_DEV void guide_planes(const DeviceScene& S, const GuideRay& g, uint32_t planes, float missDepth, GuidePixel& out)
 {
-  const GuideRay g   = guide_ray<TWO>(S, W, H, px, py, stack, counters);
-  const bool     hit = __float_as_uint(g.hit.y) != BVH_NONE;
+  const bool hit = __float_as_uint(g.hit.y) != BVH_NONE;
   if(planes & PT_GUIDES_DEPTH)
     out.plane[2] = make_float4(hit ? g.hit.x : missDepth, 0.0f, 0.0f, 0.0f);
   if(!(planes & (PT_GUIDES_BASECOLOR | PT_GUIDES_NORMAL)))
@@ -126,4 +124,34 @@ PT_DEV void guide_pixel(const DeviceScene& S, int W, int H, int px, int py, uint
     out.plane[0] = make_float4(albedo.x, albedo.y, albedo.z, 1.0f);
   if(planes & PT_GUIDES_NORMAL)
     out.plane[1] = make_float4(normal.x, normal.y, normal.z, 1.0f);
+}
+template <bool TWO>
+PT_DEV void guide_pixel(const DeviceScene& S, int W, int H, int px, int py, uint32_t planes, float missDepth, uint32_t* stack, Counters* counters, GuidePixel& out)
+{
+  const GuideRay g = guide_ray<TWO>(S, W, H, px, py, stack, counters);
+  guide_planes(S, g, planes, missDepth, out);
+}
+
+// The instance plane of DESIGN.md section 5.5: the node index of the hit guide_ray found -- guide_surface's hitInst, what pt_RayHit::instanceID reports for
+// the same ray -- or PT_INSTANCE_NONE for a miss.  This restates the first lines of guide_surface for the instance alone (two-level: the world triangle's;
+// flat: the slot's shading line when the structure carries them, its TriRec otherwise): sharing them as a function of their own changes the device code
+// of k_guides (tools/device_code_diff.sh), and tests/test_instances_host.py holds both to the oracle on the same rays.
+PT_DEV uint32_t guide_instance(const DeviceScene& S, const float4& hit)
+{
+  const uint32_t ref = __float_as_uint(hit.y);
+  if(ref == BVH_NONE)
+    return PT_INSTANCE_NONE;
+  if(S.twoLevel)
+    return instance_of_world_tri(S, ref);
+  if(S.shadeTris)
+    return __float_as_uint(S.shadeTris[size_t(ref) * PT_SHADE_REC_QUADS + 6].x);
+  return __float_as_uint(S.tris[ref].e1n.w);
+}
+// One pixel of pt_render_instance_plane: guide_pixel's walk and planes (`planes` may be 0), and the instance plane's entry returned
+template <bool TWO>
+PT_DEV uint32_t instance_pixel(const DeviceScene& S, int W, int H, int px, int py, uint32_t planes, float missDepth, uint32_t* stack, Counters* counters, GuidePixel& out)
+{
+  const GuideRay g = guide_ray<TWO>(S, W, H, px, py, stack, counters);
+  guide_planes(S, g, planes, missDepth, out);
+  return guide_instance(S, g.hit);
 }

@@ -56,6 +56,8 @@ static inline void stages_release(pt_context* c)
     dev_free(b);
   for(DevBuf& b : c->dGuide)
     dev_free(b);
+  dev_free(c->dInstPlane);
+  dev_free(c->dMotionTable);
   for(int s = 0; s < 2; ++s)
   {
     dev_free(c->dHistColour[s]);

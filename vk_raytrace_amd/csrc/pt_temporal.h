@@ -83,30 +83,40 @@ PT_DN float tp_mat4_row(const float* m, int r, float x, float y, float z, float 
 PT_DN float tp_dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }  // dot3 of pt_math.h
 PT_DN float tp_mix(float a, float b, float t) { return a * (1.0f - t) + b * t; }                                        // lerp of pt_math.h (GLSL mix)
 
-// Pixel (px, py) of a W x H image.  src.colour / src.normal / src.depth are the accumulation image and guide planes 1 and 2 at the pixel itself;
-// src.histColour / src.histGuide / src.histLength are the history set that is READ, asked only for positions inside the image and only when
-// k.haveHistory is set.  Every index formed here lies inside the image for every input bit pattern: the range tests of step 2 are float comparisons
-// that a NaN fails and run before the conversion to int, and each tap is tested against the image again.
-template <class Src>
-PT_DN TemporalOut temporal_pixel(const Src& src, const TemporalConst& k, int px, int py, int w, int h, TemporalProbe* probe)
-{
-  const DnPx  c = src.colour(px, py), g1 = src.normal(px, py);
-  const float t = src.depth(px, py).x;
+// the point steps 2 and 3 run on
+struct TemporalPoint {
+  float Px, Py, Pz;
+};
 
-  // step 1: the pinhole half of camera_ray (pt_shade.h), jitter (0.5, 0.5), no lens
-  const float cx = float(px) + 0.5f, cy = float(py) + 0.5f;
-  const float ux = cx / float(w), uy = cy / float(h);
-  const float dx = ux * 2.0f - 1.0f, dy = uy * 2.0f - 1.0f;
-  const float ox = tp_mat4_row(k.viewInverse, 0, 0.0f, 0.0f, 0.0f, 1.0f), oy = tp_mat4_row(k.viewInverse, 1, 0.0f, 0.0f, 0.0f, 1.0f),
-              oz = tp_mat4_row(k.viewInverse, 2, 0.0f, 0.0f, 0.0f, 1.0f);
-  const float tx = tp_mat4_row(k.projInverse, 0, dx, dy, 1.0f, 1.0f), ty = tp_mat4_row(k.projInverse, 1, dx, dy, 1.0f, 1.0f),
-              tz = tp_mat4_row(k.projInverse, 2, dx, dy, 1.0f, 1.0f);
-  const float tinv = 1.0f / sqrtf(tp_dot3(tx, ty, tz, tx, ty, tz));  // unit()
-  const float nx = tx * tinv, ny = ty * tinv, nz = tz * tinv;
-  const float rx = tp_mat4_row(k.viewInverse, 0, nx, ny, nz, 0.0f), ry = tp_mat4_row(k.viewInverse, 1, nx, ny, nz, 0.0f),
-              rz = tp_mat4_row(k.viewInverse, 2, nx, ny, nz, 0.0f);
-  const float rinv = 1.0f / sqrtf(tp_dot3(rx, ry, rz, rx, ry, rz));
+// Step 1 for pixel (px, py) of a w x h image whose depth plane holds t there, as a statement sequence over the names k, px, py, w, h and t that leaves
+// the current eye in ox, oy, oz and the current point in Px, Py, Pz.  Stated once and expanded in temporal_pixel below and in temporal_pixel_moving
+// (pt_motion.h).  A macro and not a function: with step 1 in a function of its own -- by value, by reference, returning the point or writing it -- the
+// kernels of pt_temporal.hip and pt_svgf.hip compile to other device code than before (the vectoriser pairs step 1's products differently: 151
+// differing lines of assembly in k_temporal), whereas the expansion leaves every line of them as it was (tools/device_code_diff.sh).
+#define PT_TEMPORAL_STEP_1 \
+  /* step 1: the pinhole half of camera_ray (pt_shade.h), jitter (0.5, 0.5), no lens */                                                \
+  const float cx = float(px) + 0.5f, cy = float(py) + 0.5f;                                                                            \
+  const float ux = cx / float(w), uy = cy / float(h);                                                                                  \
+  const float dx = ux * 2.0f - 1.0f, dy = uy * 2.0f - 1.0f;                                                                            \
+  const float ox = tp_mat4_row(k.viewInverse, 0, 0.0f, 0.0f, 0.0f, 1.0f), oy = tp_mat4_row(k.viewInverse, 1, 0.0f, 0.0f, 0.0f, 1.0f),  \
+              oz = tp_mat4_row(k.viewInverse, 2, 0.0f, 0.0f, 0.0f, 1.0f);                                                              \
+  const float tx = tp_mat4_row(k.projInverse, 0, dx, dy, 1.0f, 1.0f), ty = tp_mat4_row(k.projInverse, 1, dx, dy, 1.0f, 1.0f),          \
+              tz = tp_mat4_row(k.projInverse, 2, dx, dy, 1.0f, 1.0f);                                                                  \
+  const float tinv = 1.0f / sqrtf(tp_dot3(tx, ty, tz, tx, ty, tz)); /* unit() */                                                       \
+  const float nx = tx * tinv, ny = ty * tinv, nz = tz * tinv;                                                                          \
+  const float rx = tp_mat4_row(k.viewInverse, 0, nx, ny, nz, 0.0f), ry = tp_mat4_row(k.viewInverse, 1, nx, ny, nz, 0.0f),              \
+              rz = tp_mat4_row(k.viewInverse, 2, nx, ny, nz, 0.0f);                                                                    \
+  const float rinv = 1.0f / sqrtf(tp_dot3(rx, ry, rz, rx, ry, rz));                                                                    \
   const float Px = ox + (rx * rinv) * t, Py = oy + (ry * rinv) * t, Pz = oz + (rz * rinv) * t;
+
+// Steps 2 to 4 for a pixel whose own values are c, g1 and t: `q` is the point steps 2 and 3 run on (step 1's, or what the motion table of section 5.5
+// made of it: pt_motion.h) and gn the encoded normal the taps are tested against (g1, or the one sent through the table); step 4 and the stored guide
+// take c, g1 and t as they are.  (ox, oy, oz): the current eye, which no step after the first reads.
+template <class Src>
+PT_DN void temporal_resolve(const Src& src, const TemporalConst& k, const DnPx& c, const DnPx& g1, float t, float ox, float oy, float oz, const TemporalPoint& q,
+                                   const DnPx& gn, int w, int h, TemporalProbe* probe, TemporalOut& o)
+{
+  const float Px = q.Px, Py = q.Py, Pz = q.Pz;
 
   bool  history = false;
   float hr = 0.0f, hg = 0.0f, hb = 0.0f, N = 0.0f;
@@ -158,7 +168,7 @@ PT_DN TemporalOut temporal_pixel(const Src& src, const TemporalConst& k, int px,
               verdict = 4;
             else if(!(ptf_abs(hq.w - tExp) <= k.depthTol * tExp))
               verdict = 5;
-            else if(!(dn_dist2(g1, hq) <= k.normalDist2))
+            else if(!(dn_dist2(gn, hq) <= k.normalDist2))
               verdict = 6;
             else
             {
@@ -188,7 +198,6 @@ PT_DN TemporalOut temporal_pixel(const Src& src, const TemporalConst& k, int px,
 
   // step 4
   const bool  fin = dn_finite3(c);
-  TemporalOut o;
   o.colour = c;  // alpha is the current pixel's in every case
   o.guide  = DnPx{g1.x, g1.y, g1.z, t};
   int outcome;
@@ -221,6 +230,21 @@ PT_DN TemporalOut temporal_pixel(const Src& src, const TemporalConst& k, int px,
   }
   if(probe)
     probe->outcome = outcome;
+}
+
+// Pixel (px, py) of a W x H image.  src.colour / src.normal / src.depth are the accumulation image and guide planes 1 and 2 at the pixel itself;
+// src.histColour / src.histGuide / src.histLength are the history set that is READ, asked only for positions inside the image and only when
+// k.haveHistory is set.  Every index formed here lies inside the image for every input bit pattern: the range tests of step 2 are float comparisons
+// that a NaN fails and run before the conversion to int, and each tap is tested against the image again.
+// Step 1 and steps 2 to 4 composed: the stage as section 5.3 defines it.
+template <class Src>
+PT_DN TemporalOut temporal_pixel(const Src& src, const TemporalConst& k, int px, int py, int w, int h, TemporalProbe* probe)
+{
+  const DnPx  c = src.colour(px, py), g1 = src.normal(px, py);
+  const float t = src.depth(px, py).x;
+  PT_TEMPORAL_STEP_1
+  TemporalOut o;
+  temporal_resolve(src, k, c, g1, t, ox, oy, oz, TemporalPoint{Px, Py, Pz}, g1, w, h, probe, o);
   return o;
 }
 

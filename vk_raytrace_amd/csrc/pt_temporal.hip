@@ -3,7 +3,7 @@
 // entry points.  No existing kernel is involved: the stage reads the row-major image the display pass already produces (untile_to_rowmajor), guide
 // planes 1 and 2 and the camera, and writes only the history.
 #include "pt_stage.h"
-#include "pt_temporal.h"
+#include "pt_motion.h"  // (pt_temporal.h) the motion table of pt_temporal_accumulate_moving; its kernels are pt_motion.hip's
 
 // One block covers a TP_TX x TP_TY tile of the image, one pixel per lane: a wave covers two rows of 32 pixels, so that adjacent lanes read and write
 // adjacent 16-byte pixels (512 contiguous bytes per row and plane) and the 4-byte length plane in 128-byte runs.  The gather is data dependent but
@@ -45,22 +45,38 @@ __global__ void __launch_bounds__(TP_BLOCK) k_temporal(TpArgs a)
   a.hnOut[at]          = o.length;
 }
 
-// with tracking on (pt_temporal_track_moments) the kernel of pt_svgf.hip runs instead: the same pixel function, and the moments image besides
-static void launch_temporal(const pt_context* c, const TpArgs& a)
+// with tracking on (pt_temporal_track_moments) the kernel of pt_svgf.hip runs instead: the same pixel function, and the moments image besides.
+// moving: the kernels of pt_motion.hip (section 5.5), over the instance plane and the table prepare_temporal uploaded (none without a history).
+static void launch_temporal(const pt_context* c, const TpArgs& a, bool moving = false)
 {
-  if(c->trackMoments)
+  if(c->trackMoments || moving)
   {
-    const int r = c->histSet;
-    launch_temporal_m(c->stream, TemporalMArgs{a.c, a.g1, a.g2, a.hc, a.hg, a.hn, (const float2*)c->dHistMoments[r].p, a.hcOut, a.hgOut, a.hnOut,
-                                                (float2*)c->dHistMoments[r ^ 1].p, a.w, a.h}, a.k);
+    const int           r = c->histSet;
+    const TemporalMArgs m{a.c, a.g1, a.g2, a.hc, a.hg, a.hn, c->trackMoments ? (const float2*)c->dHistMoments[r].p : nullptr, a.hcOut, a.hgOut, a.hnOut,
+                          c->trackMoments ? (float2*)c->dHistMoments[r ^ 1].p : nullptr, a.w, a.h};
+    if(moving)
+      launch_temporal_moving(c->stream, m, a.k, (const uint32_t*)c->dInstPlane.p, (const MotionRec*)c->dMotionTable.p, c->haveHistory ? uint32_t(c->hInstances.size()) : 0u);
+    else
+      launch_temporal_m(c->stream, m, a.k);
     return;
   }
   k_temporal<<<stage_grid(a.w, a.h, TP_TX, TP_TY), dim3(TP_TX, TP_TY), 0, c->stream>>>(a);
 }
 
+// the objectToWorld and worldToObject words of the scene's instances as they stand (none without a scene): what a call leaves with its history
+static std::vector<float> instance_words(const pt_context* c)
+{
+  static_assert(sizeof(Affine) == 12 * sizeof(float) && offsetof(InstanceRec, worldToObject) == sizeof(Affine), "PT_MOTION_INSTANCE_WORDS words from the record's start");
+  std::vector<float> words(c->haveScene ? c->hInstances.size() * PT_MOTION_INSTANCE_WORDS : 0);
+  for(size_t i = 0; i * PT_MOTION_INSTANCE_WORDS < words.size(); ++i)
+    std::memcpy(&words[i * PT_MOTION_INSTANCE_WORDS], &c->hInstances[i], PT_MOTION_INSTANCE_WORDS * sizeof(float));
+  return words;
+}
+
 // Everything pt_temporal_accumulate checks, then both history sets allocated and the row-major accumulation image enqueued on the context's stream
-// behind the frames rendered so far; the kernel's arguments in `a`.  Nothing of the history changes here.
-static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalParams* p, TpArgs& a)
+// behind the frames rendered so far; the kernel's arguments in `a`.  Nothing of the history changes here.  moving: what the moving form needs besides,
+// and its motion table made from the transforms kept with the history and the scene's current ones, on the device.
+static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalParams* p, TpArgs& a, bool moving = false)
 {
   STAGE_TRY(stage_need_image(c, who));
   if(!c->haveCamera)
@@ -72,7 +88,24 @@ static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalPar
   const int   rc  = temporal_constants(p, &why);
   if(rc != PT_OK)
     return c->fail(rc, "%s: %s", who, why);
+  if(moving)
+  {
+    if(!c->dInstPlane.p)
+      return c->fail(PT_ERR_STATE, "%s: no instance plane is installed (pt_render_instance_plane or pt_set_instance_plane)", who);
+    if(!c->haveScene)
+      return c->fail(PT_ERR_STATE, "%s before pt_set_scene", who);
+    if(c->haveHistory && c->histInst.size() != c->hInstances.size() * PT_MOTION_INSTANCE_WORDS)
+      return c->fail(PT_ERR_STATE, "%s: the history was made with %zu instances, the scene has %zu (pt_temporal_reset)", who, c->histInst.size() / PT_MOTION_INSTANCE_WORDS,
+                     c->hInstances.size());
+  }
   HIP_TRY(c, hipSetDevice(c->device));
+  if(moving && c->haveHistory)
+  {
+    const std::vector<float> cur = instance_words(c);
+    std::vector<MotionRec>   table(c->hInstances.size());
+    motion_table(c->histInst.data(), cur.data(), uint32_t(table.size()), table.data());
+    STAGE_TRY(upload(c, c->dMotionTable, table.data(), sizeof(MotionRec) * table.size()));
+  }
   const size_t n = stage_pixels(c);
   for(int s = 0; s < 2; ++s)
   {
@@ -101,14 +134,12 @@ static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalPar
   return PT_OK;
 }
 
-extern "C" {
-
-int pt_temporal_accumulate(pt_context* c, const pt_TemporalParams* p, float* out)
+// one call of either form
+static int temporal_accumulate(pt_context* c, const char* who, const pt_TemporalParams* p, float* out, bool moving)
 {
-  CTX_CHECK(c);
   TpArgs a;
-  STAGE_TRY(prepare_temporal(c, "pt_temporal_accumulate", p, a));
-  launch_temporal(c, a);
+  STAGE_TRY(prepare_temporal(c, who, p, a, moving));
+  launch_temporal(c, a, moving);
   HIP_TRY(c, hipGetLastError());
   if(out)
     HIP_TRY(c, hipMemcpyAsync(out, a.hcOut, sizeof(float4) * stage_pixels(c), hipMemcpyDeviceToHost, c->stream));
@@ -121,7 +152,22 @@ int pt_temporal_accumulate(pt_context* c, const pt_TemporalParams* p, float* out
   c->histSet ^= 1;
   c->haveHistory    = true;
   c->histHasMoments = c->trackMoments;
+  c->histInst       = instance_words(c);  // ... and the current instance transforms (section 5.5)
   return check_traversal(c);
+}
+
+extern "C" {
+
+int pt_temporal_accumulate(pt_context* c, const pt_TemporalParams* p, float* out)
+{
+  CTX_CHECK(c);
+  return temporal_accumulate(c, "pt_temporal_accumulate", p, out, false);
+}
+
+int pt_temporal_accumulate_moving(pt_context* c, const pt_TemporalParams* p, float* out)
+{
+  CTX_CHECK(c);
+  return temporal_accumulate(c, "pt_temporal_accumulate_moving", p, out, true);
 }
 
 int pt_temporal_reset(pt_context* c)
@@ -164,6 +210,21 @@ __attribute__((visibility("default"))) int pt_debug_temporal_time(pt_context* c,
   TpArgs a;
   STAGE_TRY(prepare_temporal(c, "pt_debug_temporal_time", p, a));
   return stage_time(c, "pt_debug_temporal_time", reps, ms_out, [&] { launch_temporal(c, a); });  // (the kernel the setting of pt_temporal_track_moments selects)
+}
+
+// Measurement access (not part of pt_api.h; tools/motion_rate.py).  what = 0: the pass of pt_render_instance_plane(planes, miss_depth), timed as
+// pt_debug_guides_time times the guide pass (params is not read); what = 1: the kernel of pt_temporal_accumulate_moving, timed as pt_debug_temporal_time
+// times pt_temporal_accumulate's, with the motion table of the current instance transforms against the history's.  Synchronous.
+__attribute__((visibility("default"))) int pt_debug_motion_time(pt_context* c, const pt_TemporalParams* p, int what, uint32_t planes, float miss_depth, int reps, float* ms_out)
+{
+  CTX_CHECK(c);
+  if(!ms_out || reps < 1 || (what != 0 && what != 1))
+    return c->fail(PT_ERR_INVALID, "pt_debug_motion_time: null, reps < 1 or no such part");
+  if(what == 0)
+    return debug_instances_time(c, planes, miss_depth, reps, ms_out);
+  TpArgs a;
+  STAGE_TRY(prepare_temporal(c, "pt_debug_motion_time", p, a, true));
+  return stage_time(c, "pt_debug_motion_time", reps, ms_out, [&] { launch_temporal(c, a, true); });
 }
 
 }  // extern "C"

@@ -330,6 +330,39 @@ class HipRenderer(Renderer):
         self._check(self._lib.pt_tonemap_history(self._ctx, None if params is None else C.byref(params), C.byref(tm), out.ctypes.data))
         return out
 
+    # -- motion of moving instances (no reference counterpart) -----------------------------------------
+    def render_instance_plane(self, guide_planes=7, miss_depth=1.0e30):
+        """pt_render_instance_plane: capture_guides(guide_planes, miss_depth) -- the mask may be 0 here -- with the instance plane written besides by
+        the same first-hit pass: per pixel the node index of the hit, capi.PT_INSTANCE_NONE for a miss.  Asynchronous like run()."""
+        self._check(self._lib.pt_render_instance_plane(self._ctx, int(guide_planes), float(miss_depth)))
+
+    def set_instance_plane(self, ids):
+        """pt_set_instance_plane: an (H, W) uint32 plane of node indices (any other word: no instance), or None to drop the plane"""
+        if ids is None:
+            self._check(self._lib.pt_set_instance_plane(self._ctx, None))
+            return
+        w, h = self.size
+        ids = np.ascontiguousarray(ids, np.uint32)
+        if ids.shape != (h, w):
+            raise ValueError(f"set_instance_plane: a plane of shape {ids.shape}, the image is {(h, w)}")
+        self._check(self._lib.pt_set_instance_plane(self._ctx, ids.ctypes.data))
+
+    def read_instance_plane(self):
+        """pt_read_instance_plane: the installed instance plane, (H, W) uint32"""
+        w, h = self.size
+        out = np.empty((h, w), np.uint32)
+        self._check(self._lib.pt_read_instance_plane(self._ctx, out.ctypes.data))
+        return out
+
+    def temporal_accumulate_moving(self, params: hd.TemporalParams, read=True):
+        """pt_temporal_accumulate_moving: temporal_accumulate() for a scene whose nodes moved since the history was made (update_instances); pixels of
+        a moved node take their point and normal through its motion before they are reprojected.  Needs the instance plane besides guide planes 1
+        and 2 (render_instance_plane).  Returns the new history colour ((H, W, 4) float32), or None with read=False."""
+        w, h = self.size
+        out = np.empty((h, w, 4), np.float32) if read else None
+        self._check(self._lib.pt_temporal_accumulate_moving(self._ctx, C.byref(params), None if out is None else out.ctypes.data))
+        return out
+
     # -- variance-guided filter of the history (no reference counterpart) ------------------------------
     @staticmethod
     def svgf_params(iterations=5, sigma_lum=4.0, lum_floor=1.0e-4, sigma_guide=(1.0, 0.3, 0.5), min_temporal=4.0):
