@@ -242,7 +242,8 @@ int pt_read_denoise_guides(pt_context* ctx, float* const planes_out[PT_DENOISE_G
  * the pixel simply has no history.  PT_ERR_STATE: before pt_resize; before pt_set_camera; without guide planes 1 and 2 installed (pt_render_guides or
  * pt_set_denoise_guides); nranks > 1 without a gathered image.  PT_ERR_INVALID, with nothing launched and the history untouched: null parameters, a
  * worldToClip entry that is not finite, depthTol not positive and finite, normalDist2 negative or not finite, maxHistory below 1 or not finite, any
- * flag bit. */
+ * flag bit.  With pt_temporal_demodulate on: the pixel's own colour is divided by guide plane 0 as it is read, the history and rgba32f_out hold
+ * illumination, and guide plane 0 is needed as well (PT_ERR_STATE without it). */
 int pt_temporal_accumulate(pt_context* ctx, const pt_TemporalParams* params, float* rgba32f_out);
 
 /* No reference counterpart.  Drops the history (a scene change, a cut): the next pt_temporal_accumulate behaves as a first call.  No error besides a
@@ -250,18 +251,22 @@ int pt_temporal_accumulate(pt_context* ctx, const pt_TemporalParams* params, flo
 int pt_temporal_reset(pt_context* ctx);
 
 /* No reference counterpart.  Copies the history's colour image (width * height * 4 floats) and its length plane (width * height floats) out; either
- * pointer may be NULL.  Synchronous.  PT_ERR_STATE: there is no history. */
+ * pointer may be NULL; the colour as it is stored -- illumination, if the history was made with pt_temporal_demodulate on.  Synchronous.  PT_ERR_STATE:
+ * there is no history. */
 int pt_read_temporal_history(pt_context* ctx, float* rgba32f_out, float* length_out);
 
 /* No reference counterpart.  pt_denoise with the history's colour image in place of the accumulation image: the same filter, the current guide planes,
  * the same parameter checks.  Read-only with respect to the history.  PT_ERR_STATE: before pt_resize; there is no history; PT_DENOISE_DEMODULATE
- * without guide plane 0.  PT_ERR_INVALID as pt_denoise. */
+ * without guide plane 0.  PT_ERR_INVALID as pt_denoise.  On a demodulated history (pt_temporal_demodulate) the filter runs on the illumination and the
+ * image after the last iteration is multiplied by guide plane 0, once; PT_ERR_STATE then without guide plane 0, and with PT_DENOISE_DEMODULATE (the
+ * history is already demodulated). */
 int pt_denoise_history(pt_context* ctx, const pt_DenoiseParams* params, float* rgba32f_out);
 
 /* No reference counterpart.  pt_tonemap_denoised with the history's colour image in place of the accumulation image; params == NULL: no spatial
  * filter, and the bytes are those of pt_tonemap on a context whose accumulation image was replaced by the history with pt_write_accum.  Read-only
  * with respect to the history.  Errors as pt_denoise_history (params != NULL) and pt_tonemap; tm or rgba8_out NULL: PT_ERR_INVALID.  (Not provided:
- * pt_tonemap_zoom of the history and a begin / end form.) */
+ * pt_tonemap_zoom of the history and a begin / end form.)  On a demodulated history (pt_temporal_demodulate) the image that is shown -- the filtered one,
+ * or the history itself for params == NULL -- is multiplied by guide plane 0 first, as pt_denoise_history does, with its refusals. */
 int pt_tonemap_history(pt_context* ctx, const pt_DenoiseParams* params, const pt_Tonemapper* tm, uint8_t* rgba8_out);
 
 /* ---- variance-guided filtering of the history (no reference counterpart) -----------------------------------------------------------------------
@@ -293,13 +298,15 @@ int pt_svgf_variance(pt_context* ctx, const pt_SvgfParams* params, float* varian
 
 /* No reference counterpart.  The history's colour image after params->iterations iterations of the variance-guided filter (width * height * 4
  * floats, alpha copied), and in variance_out (may be NULL; width * height floats) the variance after the last iteration.  Guides must be finite (the
- * result is unspecified otherwise; reads stay in bounds).  Synchronous; read-only as pt_svgf_variance; errors as pt_svgf_variance. */
+ * result is unspecified otherwise; reads stay in bounds).  Synchronous; read-only as pt_svgf_variance; errors as pt_svgf_variance.  On a demodulated
+ * history (pt_temporal_demodulate) the filter runs on the illumination, whose scale the moments share, and the image after the last iteration is
+ * multiplied by guide plane 0, once (PT_ERR_STATE without it, nothing launched); variance_out and pt_svgf_variance stay in demodulated units. */
 int pt_svgf_history(pt_context* ctx, const pt_SvgfParams* params, float* rgba32f_out, float* variance_out);
 
 /* No reference counterpart.  pt_tonemap (viewport = accumulation size) with pt_svgf_history's image as level 0 of the offscreen image: the bytes are
  * those of pt_tonemap on a context whose accumulation image was replaced by pt_svgf_history's output with pt_write_accum.  Synchronous; errors as
  * pt_svgf_history and pt_tonemap; tm or rgba8_out NULL: PT_ERR_INVALID.  (Not provided: pt_tonemap_zoom of the filtered history and a begin / end
- * form.) */
+ * form.)  On a demodulated history that output, and so the bytes, are of the remodulated image. */
 int pt_tonemap_svgf(pt_context* ctx, const pt_SvgfParams* params, const pt_Tonemapper* tm, uint8_t* rgba8_out);
 
 /* ---- motion of moving instances (no reference counterpart) -------------------------------------------------------------------------------------
@@ -335,8 +342,29 @@ int pt_read_instance_plane(pt_context* ctx, uint32_t* ids_out);
  * transforms with the history, and either may follow the other; pt_temporal_track_moments applies to both.  Errors: everything
  * pt_temporal_accumulate refuses, and PT_ERR_STATE without an instance plane, without a scene, and when the history was made with another number of
  * instances than the scene has (the scene was replaced: pt_temporal_reset).  On every refusal nothing is launched and the history is untouched.
+ * pt_temporal_demodulate applies as it does to pt_temporal_accumulate.
  * (Not provided: deforming meshes, moving lights or materials, motion seen through reflection or refraction.) */
 int pt_temporal_accumulate_moving(pt_context* ctx, const pt_TemporalParams* params, float* rgba32f_out);
+
+/* ---- demodulated history (no reference counterpart) ------------------------------------------------------------------------------------------------
+ * The temporal step and the filters above work on the product albedo x illumination: on a textured surface they either stop at every texel edge and
+ * leave the noise in, or average across texels and erase the texture.  With this setting on the history holds illumination instead -- the pixel's own
+ * colour divided by guide plane 0 as the temporal step reads it -- so that the blend, the moments, every variance and the filters see a signal
+ * without the texture, and the consumers of the history multiply their final image by guide plane 0 again.  DESIGN.md section 5.6 has the definition,
+ * csrc/pt_albedo.h the one fp32 operation sequence host and device share.  Typical use: pt_temporal_demodulate(1) and pt_temporal_track_moments(1)
+ * once, then per frame pt_set_camera, pt_render_guides (all three planes), pt_render_frame (frame 0), pt_temporal_accumulate[_moving],
+ * pt_tonemap_svgf.  With the setting off every entry point behaves bit for bit as it does without this section. */
+
+/* No reference counterpart.  on = 1: pt_temporal_accumulate and pt_temporal_accumulate_moving read the pixel's own colour c as
+ * c.rgb / max(g0.rgb, 0.001) per channel (g0: guide plane 0 at the pixel; a channel that is not finite passes through; alpha untouched -- the
+ * division of PT_DENOISE_DEMODULATE), and everything after that read -- the finiteness test (a finite colour whose quotient overflows counts as not
+ * finite), the blend, the stored colour, the moments -- is applied to the quotient; the history's taps are read as they are.  They need guide plane 0
+ * then: PT_ERR_STATE without it, nothing launched, the history untouched.  rgba32f_out and pt_read_temporal_history return the colour as stored,
+ * i.e. illumination.  pt_svgf_history, pt_tonemap_svgf, pt_denoise_history and pt_tonemap_history multiply their final image by
+ * max(g0.rgb, 0.001), with the guide plane 0 installed at the time of that call.  on = 0 (the default): none of this.  A change of the value drops
+ * the history as pt_temporal_reset does; the setting survives pt_resize and is independent of pt_temporal_track_moments.  PT_ERR_INVALID: on is
+ * neither 0 nor 1. */
+int pt_temporal_demodulate(pt_context* ctx, int on);
 
 /* Test access to the image the display pass samples: builds the offscreen image of a disp_width x disp_height viewport and its full mip chain exactly
  * as pt_tonemap_zoom does with auto-exposure on, and copies level `level` (RGBA32F, row-major) to rgba32f_out, its extent to *width / *height (each may

@@ -159,6 +159,11 @@ public:
   bool svgfVariance(const pt_SvgfParams& p, float* variance) { return check(pt_svgf_variance(m_ctx, &p, variance)); }
   bool svgfHistory(const pt_SvgfParams& p, float* rgba32f, float* variance = nullptr) { return check(pt_svgf_history(m_ctx, &p, rgba32f, variance)); }
   bool tonemapSvgf(const pt_SvgfParams& p, const pt_Tonemapper& tm, uint8_t* rgba8) { return check(pt_tonemap_svgf(m_ctx, &p, &tm, rgba8)); }
+  // demodulated history (no reference counterpart): with temporalDemodulate(true) temporalAccumulate[Moving] divide the pixel's
+  // own colour by guide plane 0 (the albedo) as they read it -- the history, its moments and the filters work on illumination -- and svgfHistory,
+  // tonemapSvgf, denoiseHistory and tonemapHistory multiply their final image by guide plane 0 again.  All of them need guide plane 0 then.  A change
+  // drops the history.
+  bool temporalDemodulate(bool on) { return check(pt_temporal_demodulate(m_ctx, on ? 1 : 0)); }
   bool denoiseHistory(const pt_DenoiseParams& p, float* rgba32f) { return check(pt_denoise_history(m_ctx, &p, rgba32f)); }
   // dp == nullptr: no spatial filter
   bool tonemapHistory(const pt_DenoiseParams* dp, const pt_Tonemapper& tm, uint8_t* rgba8) { return check(pt_tonemap_history(m_ctx, dp, &tm, rgba8)); }

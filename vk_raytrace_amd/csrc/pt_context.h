@@ -140,6 +140,9 @@ struct pt_context {
   DevBuf   dHistMoments[2], dSvgfVar[2];
   bool     trackMoments = false, histHasMoments = false;
   int      svgfLdsMaxStep = -1;  // largest step whose iteration stages its tile in LDS (-1: the measured default; pt_debug_svgf_lds)
+  // demodulated history (pt_albedo.hip): with demodulate the temporal step divides the pixel's own colour by guide plane 0;
+  // histDemodulated: the history that is held was made that way, and its consumers multiply their final image by guide plane 0
+  bool     demodulate = false, histDemodulated = false;
   bool     haveFull = false;
   // pipelined display (pt_tonemap_begin / pt_tonemap_end): a ring of pinned host images, each with the event that says its copy has landed
   // and the event after which the accumulation image may be written again (the untile pass has read it)
@@ -206,6 +209,12 @@ struct MotionRec;
 // pt_motion.hip: the temporal kernels of pt_temporal_accumulate_moving (a.hm == NULL: the one without the moments image) and the timing of its instance pass
 void       launch_temporal_moving(hipStream_t stream, const TemporalMArgs& a, const TemporalConst& k, const uint32_t* ids, const MotionRec* table, uint32_t numInstances);
 int        debug_instances_time(pt_context* c, uint32_t planes, float missDepth, int reps, float* ms_out);
+// pt_albedo.hip: the temporal kernels of a context with pt_temporal_demodulate on (a.hm == NULL: without the moments image; ids / table / numInstances
+// are read by the moving form only), the remodulation of n pixels (out may be c) and the timing of that pass
+void       launch_temporal_d(hipStream_t stream, const TemporalMArgs& a, const TemporalConst& k, const float4* albedo, bool moving, const uint32_t* ids, const MotionRec* table,
+                             uint32_t numInstances);
+void       launch_remodulate(hipStream_t stream, const float4* albedo, const float4* c, float4* out, size_t n);
+int        debug_remodulate_time(pt_context* c, int reps, float* ms_out);
 void       refresh_scene_ptrs(pt_context* c);
 int        upload_instances(pt_context* c);
 std::vector<InstanceRec> effective_instances(const pt_context* c);  // the instance records as the kernels see them

@@ -160,15 +160,32 @@ static int enqueue_denoise_history(pt_context* c, const char* who, const pt_Deno
   STAGE_TRY(stage_need_image(c, who));
   STAGE_TRY(stage_need_history(c, who, false));
   const float4* hist = (const float4*)c->dHistColour[c->histSet].p;
+  // a demodulated history: the final image is multiplied by guide plane 0 -- the filtered one in place (it is one of the
+  // denoiser's two: iterations >= 1), the history itself into the denoiser's first image
+  const bool    remod  = c->histDemodulated;
+  const float4* albedo = (const float4*)c->dGuide[0].p;
+  STAGE_TRY(stage_need_albedo(c, who));
+  const char* why = "";
+  if(p && albedo_denoise_flags(remod, p->flags, &why) != PT_OK)
+    return c->fail(PT_ERR_STATE, "%s: %s", who, why);
   if(!p)
   {
     HIP_TRY(c, hipSetDevice(c->device));
     result = hist;
+    if(remod)
+    {
+      STAGE_TRY(dev_alloc(c, c->dDenoise[0], sizeof(float4) * stage_pixels(c)));
+      launch_remodulate(c->stream, albedo, hist, (float4*)c->dDenoise[0].p, stage_pixels(c));
+      HIP_TRY(c, hipGetLastError());
+      result = (const float4*)c->dDenoise[0].p;
+    }
     return PT_OK;
   }
   DenoiseConst k;
   STAGE_TRY(prepare_denoise(c, who, p, k, false));
   result = enqueue_filter(c, hist, p, k);
+  if(remod)
+    launch_remodulate(c->stream, albedo, result, const_cast<float4*>(result), stage_pixels(c));
   HIP_TRY(c, hipGetLastError());
   return PT_OK;
 }

@@ -5,6 +5,7 @@
 #include <initializer_list>
 #include "pt_context.h"
 #include "pt_denoise.h"  // DnPx
+#include "pt_albedo.h"   // what a demodulated history refuses, with the texts
 
 #define STAGE_TRY(call)    \
   do                       \
@@ -32,6 +33,15 @@ static inline int stage_need_history(pt_context* c, const char* who, bool moment
   if(moments && !c->histHasMoments)
     return c->fail(PT_ERR_STATE, "%s: the history was made without moments (pt_temporal_track_moments)", who);
   return PT_OK;
+}
+
+static inline uint32_t guide_planes_set(const pt_context* c);  // (under "small things")
+// a consumer of the history: this history is demodulated and guide plane 0, which its final image is multiplied by, is missing
+static inline int stage_need_albedo(pt_context* c, const char* who)
+{
+  const char* why = "";
+  const int   rc  = albedo_need_plane(c->histDemodulated, guide_planes_set(c), &why);
+  return rc != PT_OK ? c->fail(rc, "%s: %s", who, why) : PT_OK;
 }
 
 // ---- small things -----------------------------------------------------------------------------------------------------------------------------------------
@@ -66,7 +76,7 @@ static inline void stages_release(pt_context* c)
     dev_free(c->dHistMoments[s]);
     dev_free(c->dSvgfVar[s]);
   }
-  c->haveHistory = c->histHasMoments = false;
+  c->haveHistory = c->histHasMoments = c->histDemodulated = false;
 }
 
 // ---- handing results back -----------------------------------------------------------------------------------------------------------------------------------

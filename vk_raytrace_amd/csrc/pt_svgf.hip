@@ -274,12 +274,17 @@ static void enqueue_iterations(pt_context* c, SvArgs a, int iterations, const fl
   colour   = a.c;
   variance = a.vOut;
 }
+// On a demodulated history (section 5.6) the image after the last iteration is multiplied by guide plane 0, in place: it is one of the denoiser's two
+// (iterations >= 1).  The variance stays in demodulated units.
 static int enqueue_svgf(pt_context* c, const char* who, const pt_SvgfParams* p, const float4*& colour, const float*& variance)
 {
   SvArgs a;
+  STAGE_TRY(stage_need_albedo(c, who));  // (no history: not demodulated, and prepare_svgf says so)
   STAGE_TRY(prepare_svgf(c, who, p, a));
   enqueue_variance(c, a);
   enqueue_iterations(c, a, p->iterations, colour, variance);
+  if(c->histDemodulated)
+    launch_remodulate(c->stream, a.g[0], colour, const_cast<float4*>(colour), stage_pixels(c));
   HIP_TRY(c, hipGetLastError());
   return PT_OK;
 }

@@ -47,14 +47,18 @@ __global__ void __launch_bounds__(TP_BLOCK) k_temporal(TpArgs a)
 
 // with tracking on (pt_temporal_track_moments) the kernel of pt_svgf.hip runs instead: the same pixel function, and the moments image besides.
 // moving: the kernels of pt_motion.hip (section 5.5), over the instance plane and the table prepare_temporal uploaded (none without a history).
+// demodulating (pt_temporal_demodulate): the kernels of pt_albedo.hip (section 5.6), which read guide plane 0 besides -- prepare_temporal saw to it.
 static void launch_temporal(const pt_context* c, const TpArgs& a, bool moving = false)
 {
-  if(c->trackMoments || moving)
+  if(c->trackMoments || moving || c->demodulate)
   {
     const int           r = c->histSet;
     const TemporalMArgs m{a.c, a.g1, a.g2, a.hc, a.hg, a.hn, c->trackMoments ? (const float2*)c->dHistMoments[r].p : nullptr, a.hcOut, a.hgOut, a.hnOut,
                           c->trackMoments ? (float2*)c->dHistMoments[r ^ 1].p : nullptr, a.w, a.h};
-    if(moving)
+    if(c->demodulate)
+      launch_temporal_d(c->stream, m, a.k, (const float4*)c->dGuide[0].p, moving, (const uint32_t*)c->dInstPlane.p, (const MotionRec*)c->dMotionTable.p,
+                        moving && c->haveHistory ? uint32_t(c->hInstances.size()) : 0u);
+    else if(moving)
       launch_temporal_moving(c->stream, m, a.k, (const uint32_t*)c->dInstPlane.p, (const MotionRec*)c->dMotionTable.p, c->haveHistory ? uint32_t(c->hInstances.size()) : 0u);
     else
       launch_temporal_m(c->stream, m, a.k);
@@ -83,6 +87,9 @@ static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalPar
     return c->fail(PT_ERR_STATE, "%s before pt_set_camera", who);
   if(!c->dGuide[1].p || !c->dGuide[2].p)
     return c->fail(PT_ERR_STATE, "%s: guide planes 1 (normal) and 2 (depth) must be installed (pt_render_guides or pt_set_denoise_guides)", who);
+  const char* needs = "";
+  if(albedo_step_needs_plane(c->demodulate, guide_planes_set(c), &needs) != PT_OK)
+    return c->fail(PT_ERR_STATE, "%s: %s", who, needs);
   STAGE_TRY(stage_need_full_image(c, who));
   const char* why = "";
   const int   rc  = temporal_constants(p, &why);
@@ -150,9 +157,10 @@ static int temporal_accumulate(pt_context* c, const char* who, const pt_Temporal
   for(int i = 0; i < 3; ++i)
     c->histEye[i] = c->scene.camera.viewInverse[12 + i];
   c->histSet ^= 1;
-  c->haveHistory    = true;
-  c->histHasMoments = c->trackMoments;
-  c->histInst       = instance_words(c);  // ... and the current instance transforms (section 5.5)
+  c->haveHistory     = true;
+  c->histHasMoments  = c->trackMoments;
+  c->histDemodulated = c->demodulate;      // what rgba32f_out and the history hold is illumination then (section 5.6)
+  c->histInst        = instance_words(c);  // ... and the current instance transforms (section 5.5)
   return check_traversal(c);
 }
 
@@ -173,7 +181,7 @@ int pt_temporal_accumulate_moving(pt_context* c, const pt_TemporalParams* p, flo
 int pt_temporal_reset(pt_context* c)
 {
   CTX_CHECK(c);
-  c->haveHistory = c->histHasMoments = false;  // the buffers stay for the next call; pt_resize and pt_destroy free them
+  c->haveHistory = c->histHasMoments = c->histDemodulated = false;  // the buffers stay for the next call; pt_resize and pt_destroy free them
   return PT_OK;
 }
 
@@ -185,7 +193,21 @@ int pt_temporal_track_moments(pt_context* c, int on)
   if((on != 0) != c->trackMoments)
   {
     c->trackMoments = on != 0;
-    c->haveHistory = c->histHasMoments = false;  // a history without moments cannot be continued with them, and the other way round
+    c->haveHistory = c->histHasMoments = c->histDemodulated = false;  // a history without moments cannot be continued with them, and the other way round
+  }
+  return PT_OK;
+}
+
+int pt_temporal_demodulate(pt_context* c, int on)
+{
+  CTX_CHECK(c);
+  const char* why = "";
+  if(albedo_setting(on, &why) != PT_OK)
+    return c->fail(PT_ERR_INVALID, "pt_temporal_demodulate: %s", why);
+  if((on != 0) != c->demodulate)
+  {
+    c->demodulate = on != 0;
+    c->haveHistory = c->histHasMoments = c->histDemodulated = false;  // a history of colour cannot be continued with illumination, and the other way round
   }
   return PT_OK;
 }
@@ -225,6 +247,23 @@ __attribute__((visibility("default"))) int pt_debug_motion_time(pt_context* c, c
   TpArgs a;
   STAGE_TRY(prepare_temporal(c, "pt_debug_motion_time", p, a, true));
   return stage_time(c, "pt_debug_motion_time", reps, ms_out, [&] { launch_temporal(c, a, true); });
+}
+
+// Measurement access (not part of pt_api.h; tools/albedo_rate.py).  what = 0: the demodulating temporal kernel the settings select (pt_temporal_demodulate
+// must be on; the static form, with or without the moments as pt_temporal_track_moments says), timed as pt_debug_temporal_time times
+// pt_temporal_accumulate's; what = 1: the remodulation pass over one image (params is not read).  Synchronous.
+__attribute__((visibility("default"))) int pt_debug_albedo_time(pt_context* c, const pt_TemporalParams* p, int what, int reps, float* ms_out)
+{
+  CTX_CHECK(c);
+  if(!ms_out || reps < 1 || (what != 0 && what != 1))
+    return c->fail(PT_ERR_INVALID, "pt_debug_albedo_time: null, reps < 1 or no such part");
+  if(what == 1)
+    return debug_remodulate_time(c, reps, ms_out);
+  if(!c->demodulate)
+    return c->fail(PT_ERR_STATE, "pt_debug_albedo_time: pt_temporal_demodulate is off");
+  TpArgs a;
+  STAGE_TRY(prepare_temporal(c, "pt_debug_albedo_time", p, a));
+  return stage_time(c, "pt_debug_albedo_time", reps, ms_out, [&] { launch_temporal(c, a); });
 }
 
 }  // extern "C"

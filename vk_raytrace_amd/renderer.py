@@ -363,6 +363,13 @@ class HipRenderer(Renderer):
         self._check(self._lib.pt_temporal_accumulate_moving(self._ctx, C.byref(params), None if out is None else out.ctypes.data))
         return out
 
+    # -- demodulated history (no reference counterpart) ------------------------------------------------
+    def temporal_demodulate(self, on=True):
+        """pt_temporal_demodulate: the temporal step divides the pixel's own colour by guide plane 0 (the albedo) as it reads it, so that the history,
+        its moments and the filters work on illumination, and svgf_history / tonemap_svgf / denoise_history / tonemap_history multiply their final
+        image by guide plane 0 again.  temporal_accumulate[_moving] and read_temporal_history return illumination then.  A change drops the history."""
+        self._check(self._lib.pt_temporal_demodulate(self._ctx, int(on)))
+
     # -- variance-guided filter of the history (no reference counterpart) ------------------------------
     @staticmethod
     def svgf_params(iterations=5, sigma_lum=4.0, lum_floor=1.0e-4, sigma_guide=(1.0, 0.3, 0.5), min_temporal=4.0):
