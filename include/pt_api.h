@@ -366,6 +366,31 @@ int pt_temporal_accumulate_moving(pt_context* ctx, const pt_TemporalParams* para
  * neither 0 nor 1. */
 int pt_temporal_demodulate(pt_context* ctx, int on);
 
+/* ---- responsive history (no reference counterpart) --------------------------------------------------------------------------------------------------
+ * The history above follows the camera and moved instances, but not a change the guides cannot see: a moved sun, a changed emitter, another
+ * environment map, the shadow of a moved box.  Depth and normal agree there, every tap counts, and with maxHistory = 32 the display still shows 78 % of
+ * the old lighting eight frames later.  With this setting on a second, short history is kept beside the long one (ReLAX: "fast history"), the long one
+ * is clamped to the short one's local mean +- sigmaScale standard deviations, and the history length is cut to maxFast where the clamp moved a
+ * channel ("anti-lag").  DESIGN.md section 5.7 has the definition, csrc/pt_fast.h the one fp32 operation sequence host and device share.  With the
+ * setting off every entry point behaves bit for bit as it does without this section. */
+
+/* No reference counterpart.  params != NULL: pt_temporal_accumulate and pt_temporal_accumulate_moving run their step a second time over the fast
+ * history (colour and length; the guide image is shared) with maxFast in the place of maxHistory and without moments, then clamp the long history
+ * they have just written: per pixel and channel to mean +- sigmaScale * standard deviation of the new fast colour over the (2 radius + 1)^2 window
+ * (taps outside the image, with a fast length below 1 or a colour that is not finite are left out; fewer than 2 taps, a pixel whose own length is
+ * below 1 or whose colour is not finite, or bounds that are not finite: the pixel is left as it is; alpha and the moments are never touched), and
+ * where a channel moved the pixel's history length becomes min(length, maxFast).  rgba32f_out, pt_read_temporal_history and every consumer of the
+ * history see the clamped colour and the lowered length.  params == NULL (the default): none of this.  Going from off to on or from on to off drops
+ * the history as pt_temporal_reset does; new parameters while the setting stays on do not.  The setting survives pt_resize and is independent of
+ * pt_temporal_track_moments and pt_temporal_demodulate (with demodulation on both histories hold illumination).  PT_ERR_INVALID: maxFast not >= 1 or
+ * not finite, sigmaScale negative or not finite, radius outside 1 .. 3, a flag bit; the setting and the history stay as they were.
+ * (Not provided: a clamp of the moments, a guide-weighted window, begin / end and zoom forms, per-rank histories.) */
+int pt_temporal_fast(pt_context* ctx, const pt_FastParams* params /* NULL: off */);
+
+/* Copies the fast history out: colour (RGBA32F, row-major, width * height * 4 floats) and length (width * height floats); either pointer may be NULL.
+ * Synchronous.  PT_ERR_STATE: there is no history, or the history was made with pt_temporal_fast off. */
+int pt_read_temporal_fast(pt_context* ctx, float* rgba32f_out, float* length_out);
+
 /* Test access to the image the display pass samples: builds the offscreen image of a disp_width x disp_height viewport and its full mip chain exactly
  * as pt_tonemap_zoom does with auto-exposure on, and copies level `level` (RGBA32F, row-major) to rgba32f_out, its extent to *width / *height (each may
  * be NULL).  Returns the number of levels (>= 1), or a negative pt_Result. */

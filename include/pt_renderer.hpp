@@ -164,6 +164,12 @@ public:
   // tonemapSvgf, denoiseHistory and tonemapHistory multiply their final image by guide plane 0 again.  All of them need guide plane 0 then.  A change
   // drops the history.
   bool temporalDemodulate(bool on) { return check(pt_temporal_demodulate(m_ctx, on ? 1 : 0)); }
+  // responsive history (no reference counterpart): with temporalFast(&p) temporalAccumulate[Moving] keep a second, short history
+  // (p.maxFast in the place of maxHistory) beside the long one, clamp the long one to the short one's local mean +- p.sigmaScale standard deviations and
+  // cut the history length to maxFast where the clamp moved a channel, so that a change of lighting the guides cannot see shows within a few frames.
+  // nullptr: off.  Going from off to on or back drops the history; new parameters do not.
+  bool temporalFast(const pt_FastParams* p) { return check(pt_temporal_fast(m_ctx, p)); }
+  bool readTemporalFast(float* rgba32f, float* length) { return check(pt_read_temporal_fast(m_ctx, rgba32f, length)); }
   bool denoiseHistory(const pt_DenoiseParams& p, float* rgba32f) { return check(pt_denoise_history(m_ctx, &p, rgba32f)); }
   // dp == nullptr: no spatial filter
   bool tonemapHistory(const pt_DenoiseParams* dp, const pt_Tonemapper& tm, uint8_t* rgba8) { return check(pt_tonemap_history(m_ctx, dp, &tm, rgba8)); }

@@ -278,6 +278,15 @@ typedef struct pt_TemporalParams {
   uint32_t flags;           /* none defined: must be 0 */
 } pt_TemporalParams;
 
+/* pt_temporal_fast: the responsive history (no reference counterpart; defined in DESIGN.md section 5.7 and stated once in csrc/pt_fast.h).  A second,
+ * short history is kept beside the long one, and the long one is clamped to the short one's local mean +- sigmaScale standard deviations. */
+typedef struct pt_FastParams {
+  float    maxFast;    /* cap of the fast history's length, in the place of pt_TemporalParams::maxHistory; >= 1, finite (ReLAX: 4 .. 6) */
+  float    sigmaScale; /* half width of the clamp interval in standard deviations of the fast history over the window; >= 0, finite */
+  int32_t  radius;     /* the window is (2 radius + 1)^2 pixels; 1 .. 3 */
+  uint32_t flags;      /* none defined: must be 0 */
+} pt_FastParams;
+
 /* pt_svgf_variance / pt_svgf_history / pt_tonemap_svgf: the variance-guided filter of the history (no reference counterpart; defined in DESIGN.md
  * section 5.4 and stated once in csrc/pt_svgf.h).  The luminance edge stop is measured in standard deviations of the per-pixel variance estimate
  * that the moments in the history (pt_temporal_track_moments) give; guide terms are those of pt_DenoiseParams. */
@@ -355,6 +364,7 @@ static_assert(sizeof(pt_Ray) == 32 && sizeof(pt_RayHit) == 32, "Ray / RayHit");
 static_assert(sizeof(pt_DenoiseParams) == 24, "DenoiseParams");
 static_assert(sizeof(pt_TemporalParams) == 80, "TemporalParams");
 static_assert(sizeof(pt_SvgfParams) == 32, "SvgfParams");
+static_assert(sizeof(pt_FastParams) == 16, "FastParams");
 #endif
 
 #endif /* PT_TYPES_H */

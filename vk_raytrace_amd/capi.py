@@ -78,6 +78,8 @@ API = [
     ("pt_read_instance_plane", C.c_int, [_P, _P]),
     ("pt_temporal_accumulate_moving", C.c_int, [_P, C.POINTER(hd.TemporalParams), _P]),
     ("pt_temporal_demodulate", C.c_int, [_P, C.c_int]),
+    ("pt_temporal_fast", C.c_int, [_P, C.POINTER(hd.FastParams)]),
+    ("pt_read_temporal_fast", C.c_int, [_P, _P, _P]),
     ("pt_debug_display_level", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_local_shard", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pt_scatter_shards", C.c_int, [_P, _P, C.c_int]),
@@ -124,6 +126,7 @@ DEBUG_API = [
     ("pt_debug_temporal_time", C.c_int, [_P, C.POINTER(hd.TemporalParams), C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_temporal.hip: (ctx, params, reps, ms per run out): the temporal kernel alone, device events
     ("pt_debug_motion_time", C.c_int, [_P, C.POINTER(hd.TemporalParams), C.c_int, C.c_uint32, C.c_float, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_temporal.hip: (ctx, params, part (0 instance pass, 1 moving temporal kernel), guide planes, miss_depth, reps, ms per run out), device events
     ("pt_debug_albedo_time", C.c_int, [_P, C.POINTER(hd.TemporalParams), C.c_int, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_temporal.hip: (ctx, params, part (0 demodulating temporal kernel, 1 remodulation pass), reps, ms per run out), device events
+    ("pt_debug_fast_time", C.c_int, [_P, C.POINTER(hd.TemporalParams), C.c_int, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_temporal.hip: (ctx, params, part (0 fast temporal step, 1 clamp kernel), reps, ms per run out), device events
     ("pt_debug_svgf_lds", C.c_int, [_P, C.c_int]),  # csrc/pt_svgf.hip: (ctx, largest step staged in LDS; negative: the default) -> the value in force
     ("pt_debug_svgf_time", C.c_int, [_P, C.POINTER(hd.SvgfParams), C.c_int, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_svgf.hip: (ctx, params, part (-2 whole, -1 variance, i: iteration i), reps, ms per run out), device events
     ("pt_debug_bounce_counts", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[max_bounces][16], max_bounces) -> staged bounces of the newest finished launch sequence

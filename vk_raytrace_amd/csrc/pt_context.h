@@ -143,6 +143,11 @@ struct pt_context {
   // demodulated history (pt_albedo.hip): with demodulate the temporal step divides the pixel's own colour by guide plane 0;
   // histDemodulated: the history that is held was made that way, and its consumers multiply their final image by guide plane 0
   bool     demodulate = false, histDemodulated = false;
+  // responsive history (pt_fast.hip): with `fast` the step keeps a second, short history -- colour and length, each twice, swapped
+  // with histSet like the others; the guide image is shared -- and clamps the long one to it; histFast: the history that is held was made that way
+  DevBuf   dHistFast[2], dHistFastLength[2];
+  bool     fast = false, histFast = false;
+  pt_FastParams fastParams = {};
   bool     haveFull = false;
   // pipelined display (pt_tonemap_begin / pt_tonemap_end): a ring of pinned host images, each with the event that says its copy has landed
   // and the event after which the accumulation image may be written again (the untile pass has read it)
@@ -215,6 +220,9 @@ void       launch_temporal_d(hipStream_t stream, const TemporalMArgs& a, const T
                              uint32_t numInstances);
 void       launch_remodulate(hipStream_t stream, const float4* albedo, const float4* c, float4* out, size_t n);
 int        debug_remodulate_time(pt_context* c, int reps, float* ms_out);
+// pt_fast.hip: the clamp of the long history that was just written (hc, hn: in place, each lane its own pixel) to the fast one written beside it (hf, hnf)
+struct FastConst;
+void       launch_fast_clamp(hipStream_t stream, const float4* hf, const float* hnf, float4* hc, float* hn, int w, int h, const FastConst& k);
 void       refresh_scene_ptrs(pt_context* c);
 int        upload_instances(pt_context* c);
 std::vector<InstanceRec> effective_instances(const pt_context* c);  // the instance records as the kernels see them

@@ -74,9 +74,11 @@ static inline void stages_release(pt_context* c)
     dev_free(c->dHistGuide[s]);
     dev_free(c->dHistLength[s]);
     dev_free(c->dHistMoments[s]);
+    dev_free(c->dHistFast[s]);
+    dev_free(c->dHistFastLength[s]);
     dev_free(c->dSvgfVar[s]);
   }
-  c->haveHistory = c->histHasMoments = c->histDemodulated = false;
+  c->haveHistory = c->histHasMoments = c->histDemodulated = c->histFast = false;
 }
 
 // ---- handing results back -----------------------------------------------------------------------------------------------------------------------------------

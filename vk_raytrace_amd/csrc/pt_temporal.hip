@@ -4,6 +4,7 @@
 // planes 1 and 2 and the camera, and writes only the history.
 #include "pt_stage.h"
 #include "pt_motion.h"  // (pt_temporal.h) the motion table of pt_temporal_accumulate_moving; its kernels are pt_motion.hip's
+#include "pt_fast.h"    // the responsive history (section 5.7): its parameters and refusals; its kernel is pt_fast.hip's
 
 // One block covers a TP_TX x TP_TY tile of the image, one pixel per lane: a wave covers two rows of 32 pixels, so that adjacent lanes read and write
 // adjacent 16-byte pixels (512 contiguous bytes per row and plane) and the 4-byte length plane in 128-byte runs.  The gather is data dependent but
@@ -48,13 +49,14 @@ __global__ void __launch_bounds__(TP_BLOCK) k_temporal(TpArgs a)
 // with tracking on (pt_temporal_track_moments) the kernel of pt_svgf.hip runs instead: the same pixel function, and the moments image besides.
 // moving: the kernels of pt_motion.hip (section 5.5), over the instance plane and the table prepare_temporal uploaded (none without a history).
 // demodulating (pt_temporal_demodulate): the kernels of pt_albedo.hip (section 5.6), which read guide plane 0 besides -- prepare_temporal saw to it.
-static void launch_temporal(const pt_context* c, const TpArgs& a, bool moving = false)
+// moments: with the moments image (the long step of a context that tracks them; the fast step of section 5.7 never has one)
+static void launch_step(const pt_context* c, const TpArgs& a, bool moving, bool moments)
 {
-  if(c->trackMoments || moving || c->demodulate)
+  if(moments || moving || c->demodulate)
   {
     const int           r = c->histSet;
-    const TemporalMArgs m{a.c, a.g1, a.g2, a.hc, a.hg, a.hn, c->trackMoments ? (const float2*)c->dHistMoments[r].p : nullptr, a.hcOut, a.hgOut, a.hnOut,
-                          c->trackMoments ? (float2*)c->dHistMoments[r ^ 1].p : nullptr, a.w, a.h};
+    const TemporalMArgs m{a.c, a.g1, a.g2, a.hc, a.hg, a.hn, moments ? (const float2*)c->dHistMoments[r].p : nullptr, a.hcOut, a.hgOut, a.hnOut,
+                          moments ? (float2*)c->dHistMoments[r ^ 1].p : nullptr, a.w, a.h};
     if(c->demodulate)
       launch_temporal_d(c->stream, m, a.k, (const float4*)c->dGuide[0].p, moving, (const uint32_t*)c->dInstPlane.p, (const MotionRec*)c->dMotionTable.p,
                         moving && c->haveHistory ? uint32_t(c->hInstances.size()) : 0u);
@@ -65,6 +67,39 @@ static void launch_temporal(const pt_context* c, const TpArgs& a, bool moving = 
     return;
   }
   k_temporal<<<stage_grid(a.w, a.h, TP_TX, TP_TY), dim3(TP_TX, TP_TY), 0, c->stream>>>(a);
+}
+
+// The fast step's arguments (section 5.7): the long step's with the fast images in the place of Hc and Hn and maxFast in the place of maxHistory.  It
+// reads (Hf, Hg, Hnf) of the set that is read and writes (Hf', Hnf'); Hg' is written again with the bits the long step gave it.
+static TpArgs fast_step_args(const pt_context* c, const TpArgs& a, const FastConst& f)
+{
+  const int r = c->histSet, wr = r ^ 1;
+  TpArgs    b = a;
+  b.hc           = (const float4*)c->dHistFast[r].p;
+  b.hn           = (const float*)c->dHistFastLength[r].p;
+  b.hcOut        = (float4*)c->dHistFast[wr].p;
+  b.hnOut        = (float*)c->dHistFastLength[wr].p;
+  b.k.maxHistory = f.maxFast;
+  return b;
+}
+static void enqueue_clamp(const pt_context* c, const TpArgs& a, const TpArgs& b, const FastConst& f)
+{
+  launch_fast_clamp(c->stream, b.hcOut, b.hnOut, a.hcOut, a.hnOut, a.w, a.h, f);
+}
+
+// One call's kernels, enqueued on the context's stream: the long step; with pt_temporal_fast on, the fast step -- the same kernel over other pointers,
+// without moments -- and the clamp of what the long step wrote, in place, behind both.
+static void launch_temporal(const pt_context* c, const TpArgs& a, bool moving = false)
+{
+  launch_step(c, a, moving, c->trackMoments);
+  if(!c->fast)
+    return;
+  FastConst   f{};
+  const char* why = "";
+  (void)fast_constants(&c->fastParams, &f, &why);  // (pt_temporal_fast accepted them)
+  const TpArgs b = fast_step_args(c, a, f);
+  launch_step(c, b, moving, false);
+  enqueue_clamp(c, a, b, f);
 }
 
 // the objectToWorld and worldToObject words of the scene's instances as they stand (none without a scene): what a call leaves with its history
@@ -123,6 +158,12 @@ static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalPar
   if(c->trackMoments)
     for(int s = 0; s < 2; ++s)
       STAGE_TRY(dev_alloc(c, c->dHistMoments[s], sizeof(float2) * n));
+  if(c->fast)
+    for(int s = 0; s < 2; ++s)
+    {
+      STAGE_TRY(dev_alloc(c, c->dHistFast[s], sizeof(float4) * n));
+      STAGE_TRY(dev_alloc(c, c->dHistFastLength[s], sizeof(float) * n));
+    }
   STAGE_TRY(untile_to_rowmajor(c));
   const int r = c->histSet, wr = r ^ 1;
   a.c     = (const float4*)c->dRowMajor.p;
@@ -160,6 +201,7 @@ static int temporal_accumulate(pt_context* c, const char* who, const pt_Temporal
   c->haveHistory     = true;
   c->histHasMoments  = c->trackMoments;
   c->histDemodulated = c->demodulate;      // what rgba32f_out and the history hold is illumination then (section 5.6)
+  c->histFast        = c->fast;            // the fast images swapped with the others (section 5.7)
   c->histInst        = instance_words(c);  // ... and the current instance transforms (section 5.5)
   return check_traversal(c);
 }
@@ -181,7 +223,7 @@ int pt_temporal_accumulate_moving(pt_context* c, const pt_TemporalParams* p, flo
 int pt_temporal_reset(pt_context* c)
 {
   CTX_CHECK(c);
-  c->haveHistory = c->histHasMoments = c->histDemodulated = false;  // the buffers stay for the next call; pt_resize and pt_destroy free them
+  c->haveHistory = c->histHasMoments = c->histDemodulated = c->histFast = false;  // the buffers stay for the next call; pt_resize and pt_destroy free them
   return PT_OK;
 }
 
@@ -193,7 +235,7 @@ int pt_temporal_track_moments(pt_context* c, int on)
   if((on != 0) != c->trackMoments)
   {
     c->trackMoments = on != 0;
-    c->haveHistory = c->histHasMoments = c->histDemodulated = false;  // a history without moments cannot be continued with them, and the other way round
+    c->haveHistory = c->histHasMoments = c->histDemodulated = c->histFast = false;  // a history without moments cannot be continued with them, and the other way round
   }
   return PT_OK;
 }
@@ -207,9 +249,40 @@ int pt_temporal_demodulate(pt_context* c, int on)
   if((on != 0) != c->demodulate)
   {
     c->demodulate = on != 0;
-    c->haveHistory = c->histHasMoments = c->histDemodulated = false;  // a history of colour cannot be continued with illumination, and the other way round
+    c->haveHistory = c->histHasMoments = c->histDemodulated = c->histFast = false;  // a history of colour cannot be continued with illumination, and the other way round
   }
   return PT_OK;
+}
+
+int pt_temporal_fast(pt_context* c, const pt_FastParams* p)
+{
+  CTX_CHECK(c);
+  if(p)
+  {
+    const char* why = "";
+    const int   rc  = fast_constants(p, nullptr, &why);
+    if(rc != PT_OK)
+      return c->fail(rc, "pt_temporal_fast: %s", why);
+    c->fastParams = *p;  // new parameters while the setting stays on keep the history
+  }
+  if((p != nullptr) != c->fast)
+  {
+    c->fast = p != nullptr;
+    c->haveHistory = c->histHasMoments = c->histDemodulated = c->histFast = false;  // a history without the fast images cannot be continued with them, and the other way round
+  }
+  return PT_OK;
+}
+
+int pt_read_temporal_fast(pt_context* c, float* rgba32f_out, float* length_out)
+{
+  CTX_CHECK(c);
+  STAGE_TRY(stage_need_history(c, "pt_read_temporal_fast", false));
+  const char* why = "";
+  if(fast_need_history(c->histFast, &why) != PT_OK)
+    return c->fail(PT_ERR_STATE, "pt_read_temporal_fast: %s", why);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t n = stage_pixels(c);
+  return stage_read(c, {{rgba32f_out, c->dHistFast[c->histSet].p, sizeof(float4) * n}, {length_out, c->dHistFastLength[c->histSet].p, sizeof(float) * n}});
 }
 
 int pt_read_temporal_history(pt_context* c, float* rgba32f_out, float* length_out)
@@ -264,6 +337,27 @@ __attribute__((visibility("default"))) int pt_debug_albedo_time(pt_context* c, c
   TpArgs a;
   STAGE_TRY(prepare_temporal(c, "pt_debug_albedo_time", p, a));
   return stage_time(c, "pt_debug_albedo_time", reps, ms_out, [&] { launch_temporal(c, a); });
+}
+
+// Measurement access (not part of pt_api.h; tools/fast_rate.py), with pt_temporal_fast on and a history made that way.  what = 0: the fast step -- the
+// temporal kernel the other settings select, without moments, over the fast images; what = 1: k_fast_clamp with the setting's parameters.  Before the
+// timed runs the whole call's kernels run once, untimed, so that the clamp finds what a call gives it; every run writes the set that is not the history,
+// which stays as it was.  Synchronous.
+__attribute__((visibility("default"))) int pt_debug_fast_time(pt_context* c, const pt_TemporalParams* p, int what, int reps, float* ms_out)
+{
+  CTX_CHECK(c);
+  if(!ms_out || reps < 1 || (what != 0 && what != 1))
+    return c->fail(PT_ERR_INVALID, "pt_debug_fast_time: null, reps < 1 or no such part");
+  if(!c->fast)
+    return c->fail(PT_ERR_STATE, "pt_debug_fast_time: pt_temporal_fast is off");
+  STAGE_TRY(stage_need_history(c, "pt_debug_fast_time", false));
+  TpArgs a;
+  STAGE_TRY(prepare_temporal(c, "pt_debug_fast_time", p, a));
+  FastConst   f{};
+  const char* why = "";
+  (void)fast_constants(&c->fastParams, &f, &why);
+  const TpArgs b = fast_step_args(c, a, f);
+  return stage_time(c, "pt_debug_fast_time", reps, ms_out, [&] { what == 0 ? launch_step(c, b, false, false) : enqueue_clamp(c, a, b, f); }, [&] { launch_temporal(c, a); });
 }
 
 }  // extern "C"

@@ -370,6 +370,25 @@ class HipRenderer(Renderer):
         image by guide plane 0 again.  temporal_accumulate[_moving] and read_temporal_history return illumination then.  A change drops the history."""
         self._check(self._lib.pt_temporal_demodulate(self._ctx, int(on)))
 
+    # -- responsive history (no reference counterpart) --------------------------------------------------
+    @staticmethod
+    def fast_params(max_fast=4.0, sigma_scale=2.0, radius=2):
+        return hd.FastParams(maxFast=max_fast, sigmaScale=sigma_scale, radius=radius, flags=0)
+
+    def temporal_fast(self, params):
+        """pt_temporal_fast: with an hd.FastParams, temporal_accumulate[_moving] keep a second, short history (maxFast in the place of maxHistory) beside
+        the long one, clamp the long one to the short one's mean +- sigmaScale standard deviations over a (2 radius + 1)^2 window and cut the history
+        length to maxFast where the clamp moved a channel: lighting changes the guides cannot see show within a few frames.  None: off.  Going from
+        off to on or back drops the history; new parameters do not."""
+        self._check(self._lib.pt_temporal_fast(self._ctx, None if params is None else C.byref(params)))
+
+    def read_temporal_fast(self):
+        """pt_read_temporal_fast: the fast history, (colour (H, W, 4), length (H, W)) float32"""
+        w, h = self.size
+        colour, length = np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32)
+        self._check(self._lib.pt_read_temporal_fast(self._ctx, colour.ctypes.data, length.ctypes.data))
+        return colour, length
+
     # -- variance-guided filter of the history (no reference counterpart) ------------------------------
     @staticmethod
     def svgf_params(iterations=5, sigma_lum=4.0, lum_floor=1.0e-4, sigma_guide=(1.0, 0.3, 0.5), min_temporal=4.0):
