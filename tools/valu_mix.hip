@@ -11,6 +11,9 @@
 //   MIX 1  k_shade: per block 4 fma, 4 mul, 2 add, 1 min / max, 2 compares, 2 selects, 2 integer, 1 cvt, 1 move + the IEEE division's shape
 //          (v_div_scale x2, v_rcp, v_div_fmas, v_div_fixup around the fmas) = 28 VALU + 5 SALU (3 blocks per loop iteration = 84 + 15; the kernel: 78.8 + 19.0 per sample)
 //   MIX 2  independent v_fmac_f32 (the form bench.py calibrates with), as the cross-check against tools/valu_peak.hip
+//   MIX 3  packet kernel (k_closest_k, bounce 0) at its MEASURED ratio (profiles/r06_valu.json: 64.4 VALU, 48.7 SALU, 3.9 SMEM wave-instructions per
+//          sample -- 0.76 scalar per vector instruction where MIX 0 has 0.35): per block 16 VALU + 12 SALU + one s_load_dwordx4 the block waits for
+//          (4 blocks per loop iteration = 64 + 48 + 4; the loop's own add / compare / branch come on top) -> profiles/packet_order_mix.txt
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
@@ -31,8 +34,20 @@
   "v_mul_f32 %3, %1, %2\n v_fma_f32 %4, -%0, %3, %1\n v_div_fmas_f32 %4, %4, %2, %3\n v_div_fixup_f32 %9, %4, %8, %9\n"                       \
   "s_add_u32 %19, %19, 1\n s_cmp_lt_u32 %19, 77\n s_cselect_b32 %20, %19, 3\n s_and_b64 %18, %16, %17\n s_lshl_b32 %20, %20, 2\n"
 
+// MIX 3: 16 VALU (3 fma, 2 mul, 2 max, 2 min, 2 compares into SGPR pairs, 2 selects, 2 moves out of SGPRs, 1 v_readlane) + 12 SALU (mask and / compare /
+// select chains, first-set-bit, index arithmetic) + 1 scalar load of a quad whose offset the SALU chain computed, waited for before the block ends.
+#define PACKET_BLOCK_ASM                                                                                                                     \
+  "s_load_dwordx4 s[40:43], %24, %20\n"                                                                                                      \
+  "v_fma_f32 %0, %8, %21, %22\n v_fma_f32 %1, %9, %21, %22\n v_fma_f32 %2, %8, %23, %22\n v_max_f32 %3, %0, %1\n v_max_f32 %4, %2, %3\n"       \
+  "v_mul_f32 %5, %4, %23\n v_min_f32 %6, %0, %2\n v_min_f32 %7, %6, %1\n v_mul_f32 %7, %7, %21\n v_cmp_le_f32 %16, %5, %7\n"                 \
+  "v_cmp_lt_f32 %17, %2, %3\n s_and_b64 %16, %16, exec\n s_and_b64 %17, %17, %16\n s_cmp_lg_u64 %16, 0\n s_cselect_b32 %19, %19, 5\n"        \
+  "s_ff1_i32_b64 %20, %16\n s_and_b32 %20, %20, 63\n v_readlane_b32 %20, %10, %20\n s_cmp_eq_u32 %19, 77\n s_cselect_b32 %19, 3, %19\n"      \
+  "s_add_u32 %19, %19, 1\n s_and_b32 %20, %20, 0xfc\n v_cndmask_b32 %8, %6, %7, %16\n"                                                       \
+  "v_cndmask_b32 %9, %4, %5, %17\n v_mov_b32 %14, %19\n v_mov_b32 %15, %20\n s_waitcnt lgkmcnt(0)\n s_xor_b32 %19, %19, s40\n"               \
+  "s_and_b32 %19, %19, 63\n"
+
 template <int MIX, int WAVES>
-__global__ void __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) __launch_bounds__(256) k(float* out, int iters)
+__global__ void __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) __launch_bounds__(256) k(float* out, int iters, const unsigned* table = nullptr)
 {
   float a0 = threadIdx.x * 1e-3f, a1 = a0 + 1.f, a2 = a0 + 2.f, a3 = a0 + 3.f, a4 = a0 + 4.f, a5 = a0 + 5.f, a6 = a0 + 6.f, a7 = a0 + 7.f;
   float p0 = 0.5f + a0, p1 = 0.25f + a0;
@@ -55,6 +70,12 @@ __global__ void __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) __launch_boun
                      "+s"(s0), "+s"(s1), "+s"(s2), "+s"(u0), "+s"(u1)
                    : "v"(q), "v"(r), "v"(m)
                    : "vcc", "scc");
+    if(MIX == 3)
+      asm volatile(PACKET_BLOCK_ASM PACKET_BLOCK_ASM PACKET_BLOCK_ASM PACKET_BLOCK_ASM
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "+v"(p0), "+v"(p1), "+v"(i0), "+v"(i1), "+v"(i2), "+v"(i3), "+v"(t0), "+v"(t1),
+                     "+s"(s0), "+s"(s1), "+s"(s2), "+s"(u0), "+s"(u1)
+                   : "v"(q), "v"(r), "v"(m), "s"(table)
+                   : "vcc", "scc", "s40", "s41", "s42", "s43", "memory");
 #define FMAC8 "v_fmac_f32 %0, %8, %9\n v_fmac_f32 %1, %8, %9\n v_fmac_f32 %2, %8, %9\n v_fmac_f32 %3, %8, %9\n v_fmac_f32 %4, %8, %9\n v_fmac_f32 %5, %8, %9\n v_fmac_f32 %6, %8, %9\n v_fmac_f32 %7, %8, %9\n"
     if(MIX == 2)  // 64 per loop iteration (a loop of 8 pays a branch per 8 instructions: 620 G/s instead of the ceiling)
       asm volatile(FMAC8 FMAC8 FMAC8 FMAC8 FMAC8 FMAC8 FMAC8 FMAC8
@@ -71,14 +92,17 @@ void run(const char* name, int cus, int valuPerIter, int saluPerIter)
   const int ITERS = 2400000 / valuPerIter;  // ~2.4 M VALU per wave and launch: a launch lasts milliseconds, its start-up does not show
   float* out;
   (void)hipMalloc(&out, 64);
+  unsigned* table;  // MIX 3 reads quads out of it through the scalar cache (offsets 0 .. 252)
+  (void)hipMalloc(&table, 4096);
+  (void)hipMemset(table, 0, 4096);
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0);
   (void)hipEventCreate(&e1);
   const unsigned blocks = cus * WAVES;  // one 256-thread block = one wave per SIMD of a CU
-  k<MIX, WAVES><<<blocks, 256>>>(out, ITERS);
+  k<MIX, WAVES><<<blocks, 256>>>(out, ITERS, table);
   (void)hipEventRecord(e0);
   for(int rr = 0; rr < 5; ++rr)
-    k<MIX, WAVES><<<blocks, 256>>>(out, ITERS);
+    k<MIX, WAVES><<<blocks, 256>>>(out, ITERS, table);
   (void)hipEventRecord(e1);
   (void)hipEventSynchronize(e1);
   float ms;
@@ -89,6 +113,7 @@ void run(const char* name, int cus, int valuPerIter, int saluPerIter)
   printf("%-34s waves/SIMD %d: %7.1f G VALU wave-instr/s (+ %6.1f G SALU/s)   = one VALU per %.2f ns per SIMD\n", name, WAVES, valu / 1e9,
          double(blocks) * 4 * ITERS * saluPerIter / t / 1e9, 1e9 * simds / valu);
   (void)hipFree(out);
+  (void)hipFree(table);
 }
 int main()
 {
@@ -107,5 +132,8 @@ int main()
   run<1, 4>("k_shade mix (k_shade: 4)", cus, 84, 15);
   run<1, 2>("k_shade mix", cus, 84, 15);
   run<1, 1>("k_shade mix", cus, 84, 15);
+  run<3, 8>("packet mix (64 VALU + 48 SALU + 4 SMEM)", cus, 64, 48);
+  run<3, 4>("packet mix", cus, 64, 48);
+  run<3, 1>("packet mix", cus, 64, 48);
   return 0;
 }

@@ -25,6 +25,7 @@
 #include "pt_internal.h"
 #include "pt_sahdev.h"
 #include "pt_cnode.h"
+#include "pt_order.h"
 
 namespace {
 
@@ -1073,6 +1074,9 @@ __global__ void k_collapse(const BvhNode* __restrict__ b2, const CollapseItem* _
     }
     w.pad[q] = make_uint4(0, 0, 0, 0);
   }
+#if PT_BVH_WIDTH == 4
+  pt_order_write(w);  // the packet walk's child order per direction-sign octant (pt_order.h)
+#endif
   out[it.wide] = w;
 }
 

@@ -93,6 +93,8 @@ struct PtTuning {
   int regen                = 1;    // bounce 0: the packet kernel computes the camera rays itself (k_generate only builds the queue); 0: k_generate writes them
   int handover             = 1;    // packet stage: a ray that needs the count pass enters it on the trace machine with the packet's pass-A hit, and a ray known to need the exact
                                    // loop goes straight to it (pt_render.hip k_closest_k); 0: both are redone from the root per lane (the A/B runs and the invariance tests)
+  int packetOrder          = 1;    // packet stage, flat structure: the children of a node are visited in the order of the node's per-octant table (pt_order.h), no per-visit keys;
+                                   // 0: sorted by the entry distance of the first lane that hits each child (the A/B runs and the invariance tests; always so in the two-level walk)
   int texGroups            = 1;    // the textures a material samples with one (u, v) are also stored interleaved when they share size and sampler (pt_device.h TexRec::tiled)
   int texTile              = 1;    // RGBA8 images whose size allows it are stored block-linear (8 x 4-texel tiles = one 128-byte line; pt_device.h tex_index)
   int blasWorkers          = 8;    // two-level build: host threads (own stream + arena each) that build the BLASes concurrently

@@ -10,8 +10,15 @@
 // The fused slab test picks near / far planes by the sign of the ray direction; a packet shares that choice only if
 // all its lanes agree on the three signs.  The (rare) packets that do not -- the block containing the optical axis --
 // fall back to the per-lane traversal.
+//
+// Child order (ORDER, PT_TUNE packetOrder): the children a visit hits are entered in the order of the node's table for the packet's direction-sign
+// octant (pt_order.h, written when the node is built), no per-visit keys.  The books of such a visit are kept in lanes 0..3 of the vector unit --
+// lane i stands for the i-th nearest slot of the table -- because the kernel is bound by scalar issue, not vector issue: one masked LDS store pushes
+// the hit children but the nearest, one v_readlane enters that one.  ORDER = false is the visit sorted by the entry distance of the first lane that
+// hits each child; the two-level walk keeps it for every visit (with the table it lost 8 % on the C5 stand-in, profiles/packet_order_bench.txt).
 #pragma once
 #include "pt_trace.h"
+#include "pt_order.h"
 
 #define PACKET_STACK 128  // wave-level stack entries (4-wide nodes push at most 3 per visit; overflow is counted like the per-lane one)
 
@@ -31,11 +38,54 @@ PT_DEV uint4 sloadu4(const void* base, uint32_t byteOff)
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 
+typedef uint32_t pt_u8v __attribute__((ext_vector_type(8)));
+typedef const pt_u8v __attribute__((address_space(4)))* pt_cu8ptr;
+// child quad and pad of a node (+96 .. +127) in one scalar load
+PT_DEV void sload_children(const void* base, uint32_t at, uint32_t cc[4], uint32_t& t0, uint32_t& t1)
+{
+  const pt_u8v v = *((pt_cu8ptr)(unsigned long long)(reinterpret_cast<const char*>(base) + at + 96u));
+  cc[0] = v.s0; cc[1] = v.s1; cc[2] = v.s2; cc[3] = v.s3;
+  t0 = v.s4; t1 = v.s5;
+}
+// The table-ordered visit.  cc: the node's child references (BVH_NONE: empty slot), hm: the lanes that hit each child's box, t0 / t1: the node's order
+// table, octShift: 8 * octant.  Lane i < 4 looks up the i-th nearest slot and its child; the hit ones are ranked with mbcnt; the nearest is entered,
+// the others are stored furthest first, so that the nearest of them is popped first.  Returns false when no child was hit.  A full stack drops the
+// nearer children and counts them, like the sorted visit.
+PT_DEV bool packet_visit_table(const uint32_t cc[4], const unsigned long long hm[4], uint32_t t0, uint32_t t1, uint32_t octShift, uint32_t* wstack, int& sp, uint32_t& cur, Counters* counters)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t h0 = hm[0] ? cc[0] : BVH_NONE, h1 = hm[1] ? cc[1] : BVH_NONE, h2 = hm[2] ? cc[2] : BVH_NONE, h3 = hm[3] ? cc[3] : BVH_NONE;  // wave-uniform
+  const uint32_t ob = uint32_t(((((unsigned long long)t1) << 32) | t0) >> octShift) ^ PT_ORDER_SLOTS;                                       // the octant's byte (bits 0..7)
+  const uint32_t s  = (ob >> ((2u * lane) & 6u)) & 3u;
+  const uint32_t lo = (s & 1u) ? h1 : h0, hi = (s & 1u) ? h3 : h2;
+  const uint32_t c  = (s & 2u) ? hi : lo;
+  const bool     hit = c != BVH_NONE;
+  const unsigned long long hb = __builtin_amdgcn_ballot_w64(hit) & 0xfull;
+  if(hb == 0ull)
+    return false;
+  const int np   = __popcll(hb) - 1;  // children to push
+  const int room = PACKET_STACK - sp;
+  const int lim  = np < room ? np : room;
+  // stack level above sp of this lane's child; np: the nearest, entered.  Lanes 4 and up count all the hits below them: -1, no level
+  const int j    = np - int(__builtin_amdgcn_mbcnt_lo(uint32_t(hb), 0u));
+  cur            = __builtin_amdgcn_readlane(c, __ffsll((long long)hb) - 1);
+  if(hit && uint32_t(j) < uint32_t(lim))
+    wstack[sp + j] = c;
+  if(np > room)
+  {
+    asm volatile("");  // (keeps this a scalar branch of its own: merged with the lane test below it costs every visit two mask instructions)
+    if(lane == 0u)
+      atomicAdd(&counters->stackOverflow, uint32_t(np - room));
+  }
+  sp += lim;
+  return true;
+}
+
 // `valid`: the lane carries a ray.  wstack: PACKET_STACK dwords of LDS shared by the wave.  Returns false when the packet
 // is not sign-coherent (nothing was traversed; the caller runs the per-lane traversal instead).
 // SHADOW: any-hit semantics of traverse<TM_SHADOW> -- an opaque hit inside (0, tmax) ends the lane (`opaqueHit`), the bound stays
 // tmax because an opaque occluder may lie behind the nearest non-opaque candidate.
-template <bool SHADOW>
+template <bool SHADOW, bool ORDER>
 PT_DEV bool traverse_packet(const DeviceScene& S, bool valid, f3 o, f3 d, float tmax, uint32_t* wstack, RayHit& best, bool& opaqueHit, Counters* counters)
 {
   const RayBox rb = make_raybox(o, d);
@@ -50,6 +100,13 @@ PT_DEV bool traverse_packet(const DeviceScene& S, bool valid, f3 o, f3 d, float 
   if(S.numTris == 0 || vm == 0ull)
     return true;
   const uint32_t offX = sx ? 48u : 0u, offY = sy ? 48u : 0u, offZ = sz ? 48u : 0u;  // wave-uniform
+  const uint32_t octShift = (sx ? 8u : 0u) | (sy ? 16u : 0u) | (sz ? 32u : 0u);     // 8 * the packet's octant (pt_order.h)
+  unsigned long long vmask = vm;                                                     // the lanes still in the packet (SHADOW lanes leave it)
+  // (closest-hit packets with the table: a lane without a ray carries the bound -1, below every box's entry distance, instead of being masked out of
+  // every hit mask; its bound never changes, and the caller reads the hit of lanes with a ray only)
+  constexpr bool BOUND_MASKS = ORDER && !SHADOW;
+  if(BOUND_MASKS && !valid)
+    best.t = -1.0f;
 
   uint32_t cur = 0;
   int      sp  = 0;
@@ -67,11 +124,18 @@ PT_DEV bool traverse_packet(const DeviceScene& S, bool valid, f3 o, f3 d, float 
       const float4   px = sload4(S.wide, at + offX), qx = sload4(S.wide, at + 48u - offX);
       const float4   py = sload4(S.wide, at + 16u + offY), qy = sload4(S.wide, at + 64u - offY);
       const float4   pz = sload4(S.wide, at + 32u + offZ), qz = sload4(S.wide, at + 80u - offZ);
-      const uint4    ch = sloadu4(S.wide, at + 96u);
       const float    pxs[4] = {px.x, px.y, px.z, px.w}, qxs[4] = {qx.x, qx.y, qx.z, qx.w};
       const float    pys[4] = {py.x, py.y, py.z, py.w}, qys[4] = {qy.x, qy.y, qy.z, qy.w};
       const float    pzs[4] = {pz.x, pz.y, pz.z, pz.w}, qzs[4] = {qz.x, qz.y, qz.z, qz.w};
-      const uint32_t cc[4]  = {ch.x, ch.y, ch.z, ch.w};
+      uint32_t       cc[4], t0 = 0u, t1 = 0u;
+      if(ORDER)
+        sload_children(S.wide, at, cc, t0, t1);
+      else
+      {
+        const uint4 ch = sloadu4(S.wide, at + 96u);
+        cc[0] = ch.x; cc[1] = ch.y; cc[2] = ch.z; cc[3] = ch.w;
+      }
+      unsigned long long hms[4];
       float          key[4];   // wave-uniform ordering key: entry distance of the first lane that hits the child
       uint32_t       cid[4];
       int            nh = 0;
@@ -80,15 +144,22 @@ PT_DEV bool traverse_packet(const DeviceScene& S, bool valid, f3 o, f3 d, float 
       {
         const float nr = fmaxf(fmaxf(__builtin_fmaf(pxs[k], rb.idir.x, rb.nlo.x), __builtin_fmaf(pys[k], rb.idir.y, rb.nlo.y)), fmaxf(__builtin_fmaf(pzs[k], rb.idir.z, rb.nlo.z), 0.0f)) * 0.9999996f;
         const float fr = fminf(fminf(__builtin_fmaf(qxs[k], rb.idir.x, rb.nhi.x), __builtin_fmaf(qys[k], rb.idir.y, rb.nhi.y)), fminf(__builtin_fmaf(qzs[k], rb.idir.z, rb.nhi.z), SHADOW ? tmax : best.t)) * 1.0000004f;
-        const unsigned long long hm = (cc[k] != BVH_NONE) ? __ballot(valid && nr <= fr) : 0ull;
-        if(hm)
+        // (the table visit maps a hit mask to the child reference or BVH_NONE: an empty slot needs no test of its own there)
+        const unsigned long long hm = ORDER ? (BOUND_MASKS ? __builtin_amdgcn_ballot_w64(nr <= fr) : (__builtin_amdgcn_ballot_w64(nr <= fr) & vmask)) : (cc[k] != BVH_NONE) ? __ballot(valid && nr <= fr) : 0ull;
+        hms[k] = hm;
+        if(!ORDER && hm)
         {
           key[nh] = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(nr), __ffsll((long long)hm) - 1));
           cid[nh] = cc[k];
           ++nh;
         }
       }
-      if(nh)
+      if(ORDER)
+      {
+        if(packet_visit_table(cc, hms, t0, t1, octShift, wstack, sp, cur, counters))
+          continue;
+      }
+      else if(nh)
       {
         // scalar insertion sort, nearest first (nh <= 4, all operands wave-uniform)
 #pragma unroll
@@ -151,7 +222,9 @@ PT_DEV bool traverse_packet(const DeviceScene& S, bool valid, f3 o, f3 d, float 
         }
       }
     }
-    if(sp == 0 || (SHADOW && __ballot(valid) == 0ull))
+    if(SHADOW)
+      vmask = __ballot(valid);
+    if(sp == 0 || (SHADOW && vmask == 0ull))
       break;
     cur = __builtin_amdgcn_readfirstlane(wstack[--sp]);
   }
@@ -165,10 +238,11 @@ PT_DEV bool traverse_packet(const DeviceScene& S, bool valid, f3 o, f3 d, float 
   return true;
 }
 
+template <bool ORDER>
 PT_DEV bool traverse_packet_closest(const DeviceScene& S, bool valid, f3 o, f3 d, uint32_t* wstack, RayHit& best, Counters* counters)
 {
   bool dummy;
-  return traverse_packet<false>(S, valid, o, d, PT_INFINITY, wstack, best, dummy, counters);
+  return traverse_packet<false, ORDER>(S, valid, o, d, PT_INFINITY, wstack, best, dummy, counters);
 }
 
 #if PT_BVH_WIDTH != 2

@@ -269,7 +269,9 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_TRACE_WAVES_TWO : PT_TRA
 // fp.regen (bounce 0 only): the camera rays are computed HERE from (path slot -> pixel, frame) instead of being written by k_generate and read back --
 // 32 B per sample less written, 32 B less read; what later stages need is written from here: the direction and RNG state (k_shade), and the whole
 // ray of a path that goes on to the refilling trace machine (queueR).
-template <bool TWO>
+// ORDER (PT_TUNE packetOrder; flat structure only, the two-level walk is instantiated with false): the children of a node are entered in the order of the
+// node's table (pt_order.h) instead of sorted per visit.
+template <bool TWO, bool ORDER>
 __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_PACKET_WAVES_TWO : PT_PACKET_WAVES) k_closest_k(DeviceScene S, RenderBuffers rb, FrameParams fp, const uint32_t* __restrict__ queueIn, int bounce, int handover)
 {
   __shared__ uint32_t wstack[PACKET_STACK];
@@ -304,7 +306,7 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TWO ? PT_PACKET_WAVES_TWO : PT_PA
       }
     }
     RayHit     h;
-    const bool packet = TWO ? traverse_packet_two(S, valid, o, d, wstack, h, rb.counters) : traverse_packet_closest(S, valid, o, d, wstack, h, rb.counters);
+    const bool packet = TWO ? traverse_packet_two(S, valid, o, d, wstack, h, rb.counters) : traverse_packet_closest<ORDER>(S, valid, o, d, wstack, h, rb.counters);
     bool       redo   = valid && !packet;  // not settled here: the ray goes on with the untouched seed ...
     bool       handed = false, exact = false;  // ... of which: into pass B with this pass A's hit / straight to the exact loop (PT_TUNE handover)
     uint32_t   seedOut = seed;
@@ -1054,6 +1056,7 @@ static void plan_frame(std::vector<PtStep>& steps, hipStream_t stream, const PtT
   // from the stored state), a packet stage at bounce 0, no heat map (it keeps the path's cost in rayO.w), bounce 0 not already in k_tail
   const int  packetBounces = tune.packetClosestBounces;
   const int  handover      = tune.handover ? 1 : 0;
+  const bool packetOrder   = tune.packetOrder != 0;
   const bool packetStage = !TWO || tune.packetTwo;  // the two-level structure has a packet stage of its own since round 4 (pt_packet.h traverse_packet_two)
   fp.regen = (tune.regen && packetStage && !heat && fp.st.maxSamples == 1 && packetBounces >= 1 && tailFrom > 0 && fp.st.maxDepth > 0) ? 1 : 0;
   for(int s = 0; s < fp.st.maxSamples; ++s)
@@ -1090,7 +1093,10 @@ static void plan_frame(std::vector<PtStep>& steps, hipStream_t stream, const PtT
           {
             const uint32_t kwAll = PT_PACKET_WAVES_LAUNCH;
             const uint32_t kw    = TWO ? kwAll * PT_PACKET_WAVES_TWO / PT_PACKET_WAVES : kwAll;
-            k_closest_k<TWO><<<wavesAll < kw ? wavesAll : kw, TRACE_BLOCK, 0, stream>>>(scene, rb, fp, qIn, depth, handover);
+            if(packetOrder && !TWO)
+              k_closest_k<false, true><<<wavesAll < kw ? wavesAll : kw, TRACE_BLOCK, 0, stream>>>(scene, rb, fp, qIn, depth, handover);
+            else
+              k_closest_k<TWO, false><<<wavesAll < kw ? wavesAll : kw, TRACE_BLOCK, 0, stream>>>(scene, rb, fp, qIn, depth, handover);
             if(handover)
               k_closest_r<TWO><<<gridTrace, TRACE_BLOCK, 0, stream>>>(scene, rb, depth, PT_REFILL_BELOW_DEFAULT, PT_SUPPLY_CHUNK);
             else

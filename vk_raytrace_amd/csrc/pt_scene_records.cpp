@@ -403,7 +403,7 @@ void pt_parse_tuning(const char* tune, PtTuning& t, std::string& unknown)
                              {"cnodes", &PtTuning::cnodes}, {"shadeTris", &PtTuning::shadeTris}, {"tail", &PtTuning::tailBelow}, {"warm", &PtTuning::warm}, {"texTile", &PtTuning::texTile},
                              {"texGroups", &PtTuning::texGroups}, {"regen", &PtTuning::regen}, {"packetTwo", &PtTuning::packetTwo}, {"blasWorkers", &PtTuning::blasWorkers},
                              {"batch", &PtTuning::batch}, {"inflight", &PtTuning::framesInFlight}, {"displaySlots", &PtTuning::displaySlots}, {"bands", &PtTuning::bands},
-                             {"bandTiles", &PtTuning::bandTiles}, {"fuse", &PtTuning::fuse}, {"arena", &PtTuning::arena}, {"handover", &PtTuning::handover}};
+                             {"bandTiles", &PtTuning::bandTiles}, {"fuse", &PtTuning::fuse}, {"arena", &PtTuning::arena}, {"handover", &PtTuning::handover}, {"packetOrder", &PtTuning::packetOrder}};
   const std::string all(tune);
   size_t            at = 0;
   while(at <= all.size())
