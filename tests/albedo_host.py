@@ -5,44 +5,28 @@ import ctypes as C
 
 import numpy as np
 
-from tests import host_harness as hh, motion_host as mh, svgf_host as sh, temporal_host as th
-from vk_raytrace_amd import host_device as hd
+from tests import history_host as hs, host_harness as hh, svgf_host as sh
 
 CSRC, COMPILE = hh.CSRC, hh.COMPILE
 _P = C.c_void_p
 SIGNATURES = [
-    ("ah_temporal", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(hd.TemporalParams), _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    ("ah_temporal", C.c_int, hs.STEP),
     ("ah_remodulate", None, [_P, _P, C.c_size_t, _P]),
     ("ah_refusal", C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_int]),
+    hs.LAYOUT,
 ]
 SETTING, STEP_NEEDS_PLANE, NEED_PLANE, DENOISE_FLAGS = 0, 1, 2, 3   # ah_refusal's `what`
 _host = hh.StageLibrary("libalbedohost", "albedo_host.cpp", SIGNATURES)
 build, compile_to, bind, lib = _host.build, _host.compile_to, _host.bind, _host.lib
-History = mh.History     # colour, guide, length, world_to_clip, eye and .moments (None: not tracked)
+History = hs.History     # colour, guide, length, world_to_clip, eye and .moments (None: not tracked)
 
 
 def temporal(colour, albedo, normal, depth, view_inverse, proj_inverse, p, hist=None, moments=False, ids=None, tab=None, want_outcome=False, L=None):
     """ah_temporal: one call of the demodulating step.  ids None: the static form; else (H, W) uint32 with tab what motion_host.table returns.
     moments: the history (if any) has .moments and the new one gets them.  Returns (status, History or None[, outcome (H, W) int32])"""
-    w, h, keep, head, tail = th._inputs(colour, normal, depth, view_inverse, proj_inverse, hist)
-    g0 = np.ascontiguousarray(albedo, np.float32)
-    assert g0.shape == (h, w, 4)
-    ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
-    if ids is not None:
-        ids = np.ascontiguousarray(ids, np.uint32)
-        assert ids.shape == (h, w)
-    tab = None if tab is None else np.ascontiguousarray(tab, np.float32)
-    hm = None
-    if moments:
-        hm = np.zeros((h, w, 2), np.float32) if hist is None else np.ascontiguousarray(hist.moments, np.float32)   # (never read without a history)
-        assert hm.shape == (h, w, 2)
-    oc, og, on = np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32)
-    om = np.empty((h, w, 2), np.float32) if moments else None
-    oo = np.empty((h, w), np.int32) if want_outcome else None
-    rc = (L or lib()).ah_temporal(head[0], g0.ctypes.data, *head[1:], C.byref(p), *tail, ptr(ids), ptr(tab), 0 if tab is None else len(tab), ptr(hm),
-                                  oc.ctypes.data, og.ctypes.data, on.ctypes.data, ptr(om), ptr(oo))
-    new = None if rc != 0 else History(oc, og, on, np.array(p.worldToClip, np.float32), keep[3][12:15], om)
-    return (rc, new, oo) if want_outcome else (rc, new)
+    rc, new, pr = hs.run((L or lib()).ah_temporal, colour, normal, depth, view_inverse, proj_inverse, p, hist, albedo=albedo, ids=ids, tab=tab, moments=moments,
+                         probes=("outcome",) if want_outcome else ())
+    return (rc, new, pr["outcome"]) if want_outcome else (rc, new)
 
 
 def remodulate(x, albedo, L=None):

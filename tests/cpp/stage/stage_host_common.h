@@ -1,4 +1,5 @@
-// What the host builds of the stage headers (denoise_host.cpp, temporal_host.cpp, svgf_host.cpp) share besides those headers.
+// What the host builds of the stage headers (denoise_host.cpp, temporal_host.cpp, svgf_host.cpp, motion_host.cpp, albedo_host.cpp, fast_host.cpp) share
+// besides those headers.  The one call of the history stage they share is stage/history_step.h.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -13,7 +14,15 @@ static inline uint32_t planes_of(const float* const g[PT_DENOISE_GUIDES])
   return m;
 }
 
-// the static reason of a *_constants call in why_out (why_len bytes, may be NULL)
+// the moments image of the history that is read, row-major, as svgf_moments reads it (M: SvM of pt_svgf.h)
+template <class M>
+struct RowMajorMoments {
+  const M* hm;
+  int      w;
+  M        histMoments(int x, int y) const { return hm[size_t(y) * size_t(w) + size_t(x)]; }
+};
+
+// the static reason of a *_constants call or a refusal in why_out (why_len bytes, may be NULL)
 static inline void copy_why(const char* why, char* why_out, int why_len)
 {
   if(why_out && why_len > 0)

@@ -1,9 +1,6 @@
 // The host build of the variance-guided filter: vk_raytrace_amd/csrc/pt_svgf.h compiled by g++, whole calls over row-major images in ordinary memory.
 // tests/svgf_host.py compiles and binds it; tests/test_svgf_model.py holds it to a float64 model, tests/test_svgf_gpu.py holds the device to it.
-#include <cstring>
-#include <vector>
-#include "pt_svgf.h"
-#include "stage/stage_host_common.h"
+#include "stage/history_step.h"
 
 namespace {
 SvRowMajor source(const float* colour, const float* const g[PT_DENOISE_GUIDES], const float* variance, const float* length, const float* moments, int w)
@@ -22,38 +19,9 @@ SvRowMajor source(const float* colour, const float* const g[PT_DENOISE_GUIDES], 
 
 extern "C" {
 
-// pt_temporal_accumulate with tracking on, on the host: the arguments of th_temporal (tests/cpp/temporal_host.cpp) and the moments image of the history
-// that is read (w * h * 2 floats; not read for a first call), the four new history images out.
-int sh_temporal_m(const float* colour, const float* normal, const float* depth, int w, int h, const float* view_inverse, const float* proj_inverse,
-                  const pt_TemporalParams* params, const float* hist_colour, const float* hist_guide, const float* hist_length, const float* hist_moments,
-                  const float* world_to_clip_h, const float* eye_h, float* out_colour, float* out_guide, float* out_length, float* out_moments)
-{
-  const char* why = "";
-  const int   rc  = temporal_constants(params, &why);
-  if(rc != PT_OK)
-    return rc;
-  if(!colour || !normal || !depth || !view_inverse || !proj_inverse || !out_colour || !out_guide || !out_length || !out_moments || w <= 0 || h <= 0
-     || (hist_colour && (!hist_guide || !hist_length || !hist_moments || !world_to_clip_h || !eye_h)))
-    return PT_ERR_INVALID;
-  const TemporalConst k = temporal_const(view_inverse, proj_inverse, hist_colour ? world_to_clip_h : nullptr, hist_colour ? eye_h : nullptr, params);
-  const TpRowMajor src{(const DnPx*)colour, (const DnPx*)normal, (const DnPx*)depth, (const DnPx*)hist_colour, (const DnPx*)hist_guide, hist_length, w};
-  const SvRowMajor msrc = source(nullptr, nullptr, nullptr, nullptr, hist_moments, w);
-#pragma omp parallel for schedule(static)
-  for(int y = 0; y < h; ++y)
-    for(int x = 0; x < w; ++x)
-    {
-      TemporalProbe     pr;
-      const TemporalOut o  = temporal_pixel(src, k, x, y, w, h, &pr);
-      const SvM         m  = svgf_moments(msrc, pr, o, src.colour(x, y));
-      const size_t      at = size_t(y) * size_t(w) + size_t(x);
-      std::memcpy(out_colour + 4 * at, &o.colour, sizeof(DnPx));
-      std::memcpy(out_guide + 4 * at, &o.guide, sizeof(DnPx));
-      out_length[at]          = o.length;
-      out_moments[2 * at]     = m.x;
-      out_moments[2 * at + 1] = m.y;
-    }
-  return PT_OK;
-}
+// pt_temporal_accumulate with tracking on, on the host: th_temporal's call (tests/cpp/temporal_host.cpp) with the moments image of the history that is
+// read (w * h * 2 floats; not read for a first call) and the new one, which this form requires.
+int sh_temporal_m(const HistoryCall* q) { return q ? history_step(*q, q->out_moments != nullptr) : PT_ERR_INVALID; }
 
 // pt_svgf_variance on the host: V0 from the history's colour, length and moments and the guide planes (guides[j] NULL: plane j not installed)
 int sh_variance(const float* hist_colour, const float* hist_length, const float* hist_moments, const float* const guides[PT_DENOISE_GUIDES], int w, int h,

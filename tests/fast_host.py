@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from tests import host_harness as hh, motion_host as mh, temporal_host as th
+from tests import history_host as hs, host_harness as hh
 from vk_raytrace_amd import host_device as hd
 
 CSRC, COMPILE = hh.CSRC, hh.COMPILE
@@ -15,7 +15,8 @@ SIGNATURES = [
     ("fh_constants", C.c_int, [_FP, C.c_char_p, C.c_int]),
     ("fh_need_history", C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     ("fh_clamp", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _FP] + [_P] * 8),
-    ("fh_step", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(hd.TemporalParams), _FP, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P] + [_P] * 7),
+    ("fh_step", C.c_int, hs.STEP),
+    hs.LAYOUT,
 ]
 _host = hh.StageLibrary("libfasthost", "fast_host.cpp", SIGNATURES)
 build, compile_to, bind, lib = _host.build, _host.compile_to, _host.bind, _host.lib
@@ -25,11 +26,7 @@ def params(max_fast=4.0, sigma_scale=2.0, radius=2, flags=0):
     return hd.FastParams(maxFast=max_fast, sigmaScale=sigma_scale, radius=radius, flags=flags)
 
 
-class History(mh.History):
-    """motion_host.History with the fast images (fast, fast_length) and, for the tests, the long step's result before the clamp (raw, raw_length)"""
-    def __init__(self, colour, guide, length, world_to_clip, eye, moments, fast, fast_length, raw=None, raw_length=None):
-        super().__init__(colour, guide, length, world_to_clip, eye, moments)
-        self.fast, self.fast_length, self.raw, self.raw_length = fast, fast_length, raw, raw_length
+History = hs.History     # ... with the fast images (fast, fast_length) and, for the tests, the long step's result before the clamp (raw, raw_length)
 
 
 def constants(p, L=None):
@@ -64,27 +61,4 @@ def clamp(hf, hnf, hc, hn, fp, want_probe=False, L=None):
 def step(colour, albedo, normal, depth, view_inverse, proj_inverse, p, fp, hist=None, moments=False, ids=None, tab=None, L=None):
     """fh_step: one call with the setting on.  albedo None: pt_temporal_demodulate off.  ids None: the static form; else (H, W) uint32 with tab what
     motion_host.table returns.  hist: a History of this module (or None).  Returns (status, History or None)"""
-    w, h, keep, head, tail = th._inputs(colour, normal, depth, view_inverse, proj_inverse, hist)
-    ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
-    g0 = None if albedo is None else np.ascontiguousarray(albedo, np.float32)
-    assert g0 is None or g0.shape == (h, w, 4)
-    if ids is not None:
-        ids = np.ascontiguousarray(ids, np.uint32)
-        assert ids.shape == (h, w)
-    tab = None if tab is None else np.ascontiguousarray(tab, np.float32)
-    hm = None
-    if moments:
-        hm = np.zeros((h, w, 2), np.float32) if hist is None else np.ascontiguousarray(hist.moments, np.float32)   # (never read without a history)
-    hf = hnf = None
-    if hist is not None:
-        hf, hnf = np.ascontiguousarray(hist.fast, np.float32), np.ascontiguousarray(hist.fast_length, np.float32)
-        assert hf.shape == (h, w, 4) and hnf.shape == (h, w)
-    oc, og, on = np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32)
-    of, onf = np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32)
-    om = np.empty((h, w, 2), np.float32) if moments else None
-    raw = np.empty(h * w * 5, np.float32)
-    rc = (L or lib()).fh_step(head[0], ptr(g0), *head[1:], C.byref(p), C.byref(fp), tail[0], tail[1], tail[2], ptr(hf), ptr(hnf), tail[3], tail[4], ptr(ids), ptr(tab),
-                              0 if tab is None else len(tab), ptr(hm), oc.ctypes.data, og.ctypes.data, on.ctypes.data, of.ctypes.data, onf.ctypes.data, ptr(om), raw.ctypes.data)
-    if rc != 0:
-        return rc, None
-    return rc, History(oc, og, on, np.array(p.worldToClip, np.float32), keep[3][12:15], om, of, onf, raw[:h * w * 4].reshape(h, w, 4).copy(), raw[h * w * 4:].reshape(h, w).copy())
+    return hs.run((L or lib()).fh_step, colour, normal, depth, view_inverse, proj_inverse, p, hist, albedo=albedo, ids=ids, tab=tab, fp=fp, moments=moments)[:2]

@@ -84,7 +84,11 @@ def build_library(name, units, flags=(), needs_libptmi=False):
 
 
 def compile_to(out, unit, header_dir):
-    """The one-unit library `out` with `header_dir` searched before csrc/ (a scratch copy of a header with a planted break); no cache, no record"""
+    """The one-unit library `out` with `header_dir` searched before csrc/ (a scratch copy of a header with a planted break); no cache, no record.
+    csrc/'s other headers are copied next to it first: one that includes the broken header finds it in its own directory, which must be the scratch one"""
+    for name in os.listdir(CSRC):
+        if name.endswith(".h") and not os.path.exists(os.path.join(header_dir, name)):
+            shutil.copy(os.path.join(CSRC, name), header_dir)
     _gxx(["-I" + header_dir] + COMPILE + ["-shared", "-o", out, os.path.join(CPP, unit)])
     return out
 

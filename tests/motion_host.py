@@ -6,15 +6,15 @@ import ctypes as C
 
 import numpy as np
 
-from tests import host_harness as hh, temporal_host as th
-from vk_raytrace_amd import host_device as hd
+from tests import history_host as hs, host_harness as hh
 
 CSRC, COMPILE = hh.CSRC, hh.COMPILE
 _P = C.c_void_p
 SIGNATURES = [
     ("mh_table", None, [_P, _P, C.c_uint32, _P]),
-    ("mh_temporal_moving", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(hd.TemporalParams), _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P] + [_P] * 10),
+    ("mh_temporal_moving", C.c_int, hs.STEP),
     ("mh_instances", C.c_uint32, [_P, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_float, _P, _P, _P, _P]),
+    hs.LAYOUT,
 ]
 INSTANCE_WORDS = 24     # PT_MOTION_INSTANCE_WORDS: objectToWorld rows (12), worldToObject rows (12)
 RECORD_WORDS = 28       # MotionRec: toPrev rows (12), normalToPrev rows (12), moved, padding (3)
@@ -51,37 +51,14 @@ def moved_bits(tab):
     return np.ascontiguousarray(tab[:, 24]).view(np.uint32)
 
 
-class History(th.History):
-    """th.History, with the moments image where tracking is on (None otherwise)"""
-    def __init__(self, colour, guide, length, world_to_clip, eye, moments=None):
-        super().__init__(colour, guide, length, world_to_clip, eye)
-        self.moments = moments
+History = hs.History     # colour, guide, length, world_to_clip, eye and .moments (None: not tracked)
 
 
 def temporal_moving(colour, normal, depth, view_inverse, proj_inverse, p, ids, tab, hist=None, moments=False, want_probe=False, L=None):
     """mh_temporal_moving: one call.  ids: (H, W) uint32; tab: what table() returns (None: no instances).  Returns (status, History or None[, probe dict
     as temporal_host.probe returns it, its point being (P'.xyz, t_exp)])"""
-    w, h, keep, head, tail = th._inputs(colour, normal, depth, view_inverse, proj_inverse, hist)
-    ids = np.ascontiguousarray(ids, np.uint32)
-    assert ids.shape == (h, w)
-    tab = None if tab is None else np.ascontiguousarray(tab, np.float32)
-    n = 0 if tab is None else len(tab)
-    hm = None
-    if moments and hist is not None:
-        hm = np.ascontiguousarray(hist.moments, np.float32)
-        assert hm.shape == (h, w, 2)
-    oc, og, on = np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32)
-    om = np.empty((h, w, 2), np.float32) if moments else None
-    if moments and hist is None:
-        hm = np.zeros((h, w, 2), np.float32)    # never read: no tap is counted without a history
-    pr = None
-    if want_probe:
-        pr = {"fxfy": np.empty((h, w, 2), np.float32), "taps": np.empty((h, w, 4, 2), np.int32), "verdicts": np.empty((h, w, 4), np.int32),
-              "sw": np.empty((h, w), np.float32), "outcome": np.empty((h, w), np.int32), "point": np.empty((h, w, 4), np.float32)}
-    ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
-    probe_args = [ptr(None)] * 6 if pr is None else [pr[k].ctypes.data for k in ("fxfy", "taps", "verdicts", "sw", "outcome", "point")]
-    rc = (L or lib()).mh_temporal_moving(*head, C.byref(p), *tail, ids.ctypes.data, ptr(tab), n, ptr(hm), oc.ctypes.data, og.ctypes.data, on.ctypes.data, ptr(om), *probe_args)
-    new = None if rc != 0 else History(oc, og, on, np.array(p.worldToClip, np.float32), keep[3][12:15], om)
+    rc, new, pr = hs.run((L or lib()).mh_temporal_moving, colour, normal, depth, view_inverse, proj_inverse, p, hist, ids=ids, tab=tab, moments=moments,
+                         probes=hs.PROBES if want_probe else ())
     return (rc, new, pr) if want_probe else (rc, new)
 
 

@@ -4,14 +4,15 @@ import ctypes as C
 
 import numpy as np
 
-from tests import host_harness as hh, temporal_host as th
+from tests import history_host as hs, host_harness as hh
 from vk_raytrace_amd import host_device as hd
 
 CSRC = hh.CSRC
 _P = C.c_void_p
 _G = C.POINTER(_P)
 SIGNATURES = [
-    ("sh_temporal_m", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(hd.TemporalParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("sh_temporal_m", C.c_int, hs.STEP),
+    hs.LAYOUT,
     ("sh_variance", C.c_int, [_P, _P, _P, _G, C.c_int, C.c_int, C.POINTER(hd.SvgfParams), _P]),
     ("sh_iteration", C.c_int, [_P, _P, _G, C.c_int, C.c_int, C.POINTER(hd.SvgfParams), C.c_int, _P, _P]),
     ("sh_constants", C.c_int, [C.POINTER(hd.SvgfParams), C.c_uint, C.c_char_p, C.c_int]),
@@ -27,28 +28,14 @@ def params(iterations, sigma_lum=4.0, lum_floor=1e-4, sigma_guide=(1.0, 1.0, 1.0
     return p
 
 
-class History(th.History):
-    """temporal_host.History and the moments image"""
-    def __init__(self, colour, guide, length, moments, world_to_clip, eye):
-        super().__init__(colour, guide, length, world_to_clip, eye)
-        self.moments = moments
+def History(colour, guide, length, moments, world_to_clip, eye):
+    """history_host.History with the moments image, in this module's argument order"""
+    return hs.History(colour, guide, length, world_to_clip, eye, moments)
 
 
 def temporal_m(colour, normal, depth, view_inverse, proj_inverse, p, hist=None, L=None):
     """sh_temporal_m: one call with tracking on.  Returns (status, History or None)"""
-    w, h, keep, head, tail = th._inputs(colour, normal, depth, view_inverse, proj_inverse, hist)
-    if hist is None:
-        tail = [None] * 6
-    else:
-        hm = np.ascontiguousarray(hist.moments, np.float32)
-        assert hm.shape == (h, w, 2)
-        keep.append(hm)
-        tail = tail[:3] + [hm.ctypes.data] + tail[3:]
-    oc, og, on, om = np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32), np.empty((h, w, 2), np.float32)
-    rc = (L or lib()).sh_temporal_m(*head, C.byref(p), *tail, oc.ctypes.data, og.ctypes.data, on.ctypes.data, om.ctypes.data)
-    if rc != 0:
-        return rc, None
-    return rc, History(oc, og, on, om, np.array(p.worldToClip, np.float32), keep[3][12:15])
+    return hs.run((L or lib()).sh_temporal_m, colour, normal, depth, view_inverse, proj_inverse, p, hist, moments=True)[:2]
 
 
 def variance(hist_colour, hist_length, hist_moments, guides, p, L=None):

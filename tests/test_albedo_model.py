@@ -395,9 +395,9 @@ def test_the_binding_names_the_setting():
 
 
 # ---- planted breaks ----------------------------------------------------------------------------------------------------------------------------------------------
-ALBEDO, UNIT = "pt_albedo.h", "albedo_host.cpp"
+ALBEDO, UNIT, STEP, COMMON = "pt_albedo.h", "albedo_host.cpp", "stage/history_step.h", "stage/stage_host_common.h"
 BREAKS = {
-    "moments_from_the_raw_colour": ([(UNIT, "svgf_moments(msrc, pr, o, src.colour(x, y));", "svgf_moments(msrc, pr, o, mem.colour(x, y));")],
+    "moments_from_the_raw_colour": ([(STEP, "svgf_moments(msrc, pr, o, src.colour(x, y));", "svgf_moments(msrc, pr, o, ((const DnPx*)q.colour)[at]);")],
                                     lambda L: check_composition_static((45, 37), "none", True, L)),
     "remodulation_at_the_history_position": ([(UNIT, "std::memcpy(&g, albedo + 4 * i, sizeof(DnPx));", "std::memcpy(&g, albedo + 4 * (i + 1 < n ? i + 1 : i), sizeof(DnPx));")],
                                              lambda L: check_checkerboard(300, L)),
@@ -415,7 +415,8 @@ BREAKS = {
 def test_a_planted_break_fails_its_test(name):
     edits, check = BREAKS[name]
     with tempfile.TemporaryDirectory() as tmp:
-        for fname, src_dir in ((ALBEDO, ah.CSRC), (UNIT, os.path.join(ROOT, "tests", "cpp"))):
+        os.mkdir(os.path.join(tmp, "stage"))       # the unit's own headers go next to its copy
+        for fname, src_dir in ((ALBEDO, ah.CSRC), (UNIT, os.path.join(ROOT, "tests", "cpp")), (STEP, os.path.join(ROOT, "tests", "cpp")), (COMMON, os.path.join(ROOT, "tests", "cpp"))):
             text = open(os.path.join(src_dir, fname)).read()
             for _, old, new in [e for e in edits if e[0] == fname]:
                 assert text.count(old) == 1, (name, old)

@@ -592,18 +592,20 @@ def test_hostile_planes_sanitized():
 
 
 # ---- planted breaks ----------------------------------------------------------------------------------------------------------------------------------------------
-FAST_H, UNIT = "pt_fast.h", "fast_host.cpp"
+FAST_H, UNIT, STEP, COMMON = "pt_fast.h", "fast_host.cpp", "stage/history_step.h", "stage/stage_host_common.h"
 BREAKS = {
-    "clamp_reads_the_read_set": ([(UNIT, "const FcRowMajor src{(const DnPx*)out_fast, out_fast_length, w};",
-                                   "const FcRowMajor src{(const DnPx*)(hist_fast ? hist_fast : out_fast), hist_fast ? hist_fast_length : out_fast_length, w};")],
+    "clamp_reads_the_read_set": ([(STEP, "clamp_image(q.out_fast, q.out_fast_length, q.out_colour, q.out_length, q.w, q.h, fk, q.out_colour, q.out_length);",
+                                   "clamp_image(q.hist_fast ? q.hist_fast : q.out_fast, q.hist_fast ? q.hist_fast_length : q.out_fast_length, q.out_colour, q.out_length, q.w, q.h, fk, "
+                                   "q.out_colour, q.out_length);")],
                                  lambda L: check_step_is_two_steps_then_the_clamp(L)),
     "sigma_without_the_max": ([(FAST_H, "sqrtf(v < 0.0f ? 0.0f : v)", "sqrtf(v)")], lambda L: check_negative_variance_counts_as_zero(L)),
     "length_not_cut": ([(FAST_H, "o.length = k.maxFast < n ? k.maxFast : n;", "o.length = n;")], lambda L: check_length_is_cut_where_a_channel_moved(L)),
     "length_cut_everywhere": ([(FAST_H, "if(o.colour.x != c.x || o.colour.y != c.y || o.colour.z != c.z)", "if(true)")], lambda L: check_length_is_cut_where_a_channel_moved(L)),
-    "fast_step_with_max_history": ([(UNIT, "kf.maxHistory          = fk.maxFast;", "")], lambda L: check_composition_static((45, 37), "none", False, False, L)),
+    "fast_step_with_max_history": ([(STEP, "kf.maxHistory         = fk.maxFast;", "")], lambda L: check_composition_static((45, 37), "none", False, False, L)),
     "skipped_tap_counted": ([(FAST_H, "      if(!(f.w > 0.0f))\n        continue;  // a tap that does not count is left out of n as well\n      cnt = cnt + 1.0f;",
                               "      cnt = cnt + 1.0f;\n      if(!(f.w > 0.0f))\n        continue;")], lambda L: check_hostile_planes(L)),
-    "fast_step_reads_the_raw_colour": ([(UNIT, "    if(albedo)\n    {", "    if(albedo && !isFast)\n    {")], lambda L: check_composition_static((45, 37), "none", False, True, L)),
+    "fast_step_reads_the_raw_colour": ([(STEP, "  step_form(q, kf, q.hist_fast,", "  HistoryCall raw = q;\n  raw.albedo      = nullptr;\n  step_form(raw, kf, q.hist_fast,")],
+                                       lambda L: check_composition_static((45, 37), "none", False, True, L)),
 }
 
 
@@ -611,7 +613,8 @@ BREAKS = {
 def test_a_planted_break_fails_its_test(name):
     edits, check = BREAKS[name]
     with tempfile.TemporaryDirectory() as tmp:
-        for fname, src_dir in ((FAST_H, fh.CSRC), (UNIT, os.path.join(ROOT, "tests", "cpp"))):
+        os.mkdir(os.path.join(tmp, "stage"))       # the unit's own headers go next to its copy
+        for fname, src_dir in ((FAST_H, fh.CSRC), (UNIT, os.path.join(ROOT, "tests", "cpp")), (STEP, os.path.join(ROOT, "tests", "cpp")), (COMMON, os.path.join(ROOT, "tests", "cpp"))):
             text = open(os.path.join(src_dir, fname)).read()
             for _, old, new in [e for e in edits if e[0] == fname]:
                 assert text.count(old) == 1, (name, old)

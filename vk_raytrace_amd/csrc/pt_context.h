@@ -16,6 +16,7 @@ int  dev_alloc(pt_context* c, DevBuf& b, size_t bytes);
 bool dev_alloc_quiet(DevBuf& b, size_t bytes);  // like dev_alloc, but a failed allocation is an answer (false), not an error
 void dev_free(DevBuf& b);
 int  upload(pt_context* c, DevBuf& b, const void* src, size_t bytes);
+#include "pt_history.h"  // History, HistorySettings: members of the context
 
 struct pt_context {
   PtTuning    tune;  // launch-policy knobs of THIS context (PT_TUNE at pt_create)
@@ -124,30 +125,13 @@ struct pt_context {
   // denoiser (pt_denoise.hip): the two ping-pong images, allocated on first use, and the caller's guide planes; pt_resize and pt_destroy free them
   DevBuf   dDenoise[2], dGuide[PT_DENOISE_GUIDES];
   int      denoiseLdsMaxStep = -1;  // largest step whose iteration stages its tile in LDS (-1: the measured default; pt_debug_denoise_lds)
-  // temporal stage (pt_temporal.hip): the history -- colour, packed guide (encoded normal, depth) and length, each twice (one set is read while the other
-  // is written) -- allocated on first use, and the camera it was made with; pt_resize and pt_destroy free it, pt_temporal_reset drops it
-  DevBuf   dHistColour[2], dHistGuide[2], dHistLength[2];
-  int      histSet     = 0;      // the set that holds the history (the next call reads it and writes the other)
-  bool     haveHistory = false;
-  float    histWorldToClip[16] = {0}, histEye[3] = {0, 0, 0};
-  // motion of moving instances (pt_motion.hip): the instance plane (one word per pixel; pt_resize and pt_destroy free it), the
-  // objectToWorld and worldToObject words of every instance as they were when the history was made (24 per instance, stored by every accumulate call) and
-  // the motion table of the call in flight
+  History         hist;          // the history of the display path (pt_history.h; pt_temporal.hip writes it) ...
+  HistorySettings histSettings;  // ... and the settings the next temporal call runs under
+  // motion of moving instances (pt_motion.hip): the instance plane (one word per pixel) and the motion table of the call in flight
   DevBuf   dInstPlane, dMotionTable;
-  std::vector<float> histInst;
-  // variance-guided filter (pt_svgf.hip): with trackMoments the history has a fourth image, the luminance moments (float2, twice like the others);
-  // histHasMoments: the history that is held was made while tracking was on.  dSvgfVar: the filter's two variance planes, allocated on first use.
-  DevBuf   dHistMoments[2], dSvgfVar[2];
-  bool     trackMoments = false, histHasMoments = false;
+  // variance-guided filter (pt_svgf.hip): the filter's two variance planes, allocated on first use
+  DevBuf   dSvgfVar[2];
   int      svgfLdsMaxStep = -1;  // largest step whose iteration stages its tile in LDS (-1: the measured default; pt_debug_svgf_lds)
-  // demodulated history (pt_albedo.hip): with demodulate the temporal step divides the pixel's own colour by guide plane 0;
-  // histDemodulated: the history that is held was made that way, and its consumers multiply their final image by guide plane 0
-  bool     demodulate = false, histDemodulated = false;
-  // responsive history (pt_fast.hip): with `fast` the step keeps a second, short history -- colour and length, each twice, swapped
-  // with histSet like the others; the guide image is shared -- and clamps the long one to it; histFast: the history that is held was made that way
-  DevBuf   dHistFast[2], dHistFastLength[2];
-  bool     fast = false, histFast = false;
-  pt_FastParams fastParams = {};
   bool     haveFull = false;
   // pipelined display (pt_tonemap_begin / pt_tonemap_end): a ring of pinned host images, each with the event that says its copy has landed
   // and the event after which the accumulation image may be written again (the untile pass has read it)
@@ -199,30 +183,6 @@ int        untile_to_rowmajor(pt_context* c);  // the row-major accumulation ima
 int        display_chain(pt_context* c, int dispW, int dispH, bool chain, hipEvent_t readDone, MipView& mv);  // the display pass's offscreen image and its mip chain, enqueued
 int        display_levels(pt_context* c, const float4* image, int dispW, int dispH, bool chain, MipView& mv);  // ... the part after level 0 (`image`, accumulation size) is chosen
 int        display_finish(pt_context* c, const pt_Tonemapper* tm, MipView& mv, int dispW, int dispH, uint8_t* out);  // ... the tonemap kernel and the copy to `out` (host), enqueued
-struct TemporalConst;
-struct TemporalMArgs {  // pt_svgf.hip: k_temporal_m, the temporal kernel that also writes the moments -- the arguments of k_temporal and the fourth image
-  const float4 *c, *g1, *g2, *hc, *hg;
-  const float*  hn;
-  const float2* hm;
-  float4 *      hcOut, *hgOut;
-  float*        hnOut;
-  float2*       hmOut;
-  int           w, h;
-};
-void       launch_temporal_m(hipStream_t stream, const TemporalMArgs& a, const TemporalConst& k);
-struct MotionRec;
-// pt_motion.hip: the temporal kernels of pt_temporal_accumulate_moving (a.hm == NULL: the one without the moments image) and the timing of its instance pass
-void       launch_temporal_moving(hipStream_t stream, const TemporalMArgs& a, const TemporalConst& k, const uint32_t* ids, const MotionRec* table, uint32_t numInstances);
-int        debug_instances_time(pt_context* c, uint32_t planes, float missDepth, int reps, float* ms_out);
-// pt_albedo.hip: the temporal kernels of a context with pt_temporal_demodulate on (a.hm == NULL: without the moments image; ids / table / numInstances
-// are read by the moving form only), the remodulation of n pixels (out may be c) and the timing of that pass
-void       launch_temporal_d(hipStream_t stream, const TemporalMArgs& a, const TemporalConst& k, const float4* albedo, bool moving, const uint32_t* ids, const MotionRec* table,
-                             uint32_t numInstances);
-void       launch_remodulate(hipStream_t stream, const float4* albedo, const float4* c, float4* out, size_t n);
-int        debug_remodulate_time(pt_context* c, int reps, float* ms_out);
-// pt_fast.hip: the clamp of the long history that was just written (hc, hn: in place, each lane its own pixel) to the fast one written beside it (hf, hnf)
-struct FastConst;
-void       launch_fast_clamp(hipStream_t stream, const float4* hf, const float* hnf, float4* hc, float* hn, int w, int h, const FastConst& k);
 void       refresh_scene_ptrs(pt_context* c);
 int        upload_instances(pt_context* c);
 std::vector<InstanceRec> effective_instances(const pt_context* c);  // the instance records as the kernels see them

@@ -159,10 +159,10 @@ static int enqueue_denoise_history(pt_context* c, const char* who, const pt_Deno
 {
   STAGE_TRY(stage_need_image(c, who));
   STAGE_TRY(stage_need_history(c, who, false));
-  const float4* hist = (const float4*)c->dHistColour[c->histSet].p;
+  const float4* hist = (const float4*)c->hist.colour[c->hist.rd()].p;
   // a demodulated history: the final image is multiplied by guide plane 0 -- the filtered one in place (it is one of the
   // denoiser's two: iterations >= 1), the history itself into the denoiser's first image
-  const bool    remod  = c->histDemodulated;
+  const bool    remod  = c->hist.demodulated;
   const float4* albedo = (const float4*)c->dGuide[0].p;
   STAGE_TRY(stage_need_albedo(c, who));
   const char* why = "";

@@ -28,9 +28,9 @@ static inline int stage_need_full_image(pt_context* c, const char* who)
 }
 static inline int stage_need_history(pt_context* c, const char* who, bool moments)
 {
-  if(!c->haveHistory)
+  if(!c->hist.have)
     return c->fail(PT_ERR_STATE, "%s: there is no history (no pt_temporal_accumulate since pt_resize / pt_temporal_reset)", who);
-  if(moments && !c->histHasMoments)
+  if(moments && !c->hist.hasMoments)
     return c->fail(PT_ERR_STATE, "%s: the history was made without moments (pt_temporal_track_moments)", who);
   return PT_OK;
 }
@@ -40,7 +40,7 @@ static inline uint32_t guide_planes_set(const pt_context* c);  // (under "small 
 static inline int stage_need_albedo(pt_context* c, const char* who)
 {
   const char* why = "";
-  const int   rc  = albedo_need_plane(c->histDemodulated, guide_planes_set(c), &why);
+  const int   rc  = albedo_need_plane(c->hist.demodulated, guide_planes_set(c), &why);
   return rc != PT_OK ? c->fail(rc, "%s: %s", who, why) : PT_OK;
 }
 
@@ -68,17 +68,9 @@ static inline void stages_release(pt_context* c)
     dev_free(b);
   dev_free(c->dInstPlane);
   dev_free(c->dMotionTable);
-  for(int s = 0; s < 2; ++s)
-  {
-    dev_free(c->dHistColour[s]);
-    dev_free(c->dHistGuide[s]);
-    dev_free(c->dHistLength[s]);
-    dev_free(c->dHistMoments[s]);
-    dev_free(c->dHistFast[s]);
-    dev_free(c->dHistFastLength[s]);
-    dev_free(c->dSvgfVar[s]);
-  }
-  c->haveHistory = c->histHasMoments = c->histDemodulated = c->histFast = false;
+  for(DevBuf& b : c->dSvgfVar)
+    dev_free(b);
+  c->hist.release();
 }
 
 // ---- handing results back -----------------------------------------------------------------------------------------------------------------------------------

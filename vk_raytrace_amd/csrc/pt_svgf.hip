@@ -235,9 +235,9 @@ static int prepare_svgf(pt_context* c, const char* who, const pt_SvgfParams* p, 
   }
   for(int j = 0; j < PT_DENOISE_GUIDES; ++j)
     a.g[j] = (const float4*)c->dGuide[j].p;
-  a.c         = (const float4*)c->dHistColour[c->histSet].p;
-  a.hn        = (const float*)c->dHistLength[c->histSet].p;
-  a.hm        = (const float2*)c->dHistMoments[c->histSet].p;
+  a.c         = (const float4*)c->hist.colour[c->hist.rd()].p;
+  a.hn        = (const float*)c->hist.length[c->hist.rd()].p;
+  a.hm        = (const float2*)c->hist.moments[c->hist.rd()].p;
   a.v         = nullptr;
   a.out       = nullptr;
   a.vOut      = nullptr;
@@ -283,7 +283,7 @@ static int enqueue_svgf(pt_context* c, const char* who, const pt_SvgfParams* p, 
   STAGE_TRY(prepare_svgf(c, who, p, a));
   enqueue_variance(c, a);
   enqueue_iterations(c, a, p->iterations, colour, variance);
-  if(c->histDemodulated)
+  if(c->hist.demodulated)
     launch_remodulate(c->stream, a.g[0], colour, const_cast<float4*>(colour), stage_pixels(c));
   HIP_TRY(c, hipGetLastError());
   return PT_OK;
@@ -298,7 +298,7 @@ int pt_read_temporal_moments(pt_context* c, float* m_out)
     return c->fail(PT_ERR_INVALID, "pt_read_temporal_moments: null");
   STAGE_TRY(stage_need_history(c, "pt_read_temporal_moments", true));
   HIP_TRY(c, hipSetDevice(c->device));
-  return stage_read(c, {{m_out, c->dHistMoments[c->histSet].p, sizeof(float2) * stage_pixels(c)}});
+  return stage_read(c, {{m_out, c->hist.moments[c->hist.rd()].p, sizeof(float2) * stage_pixels(c)}});
 }
 
 int pt_svgf_variance(pt_context* c, const pt_SvgfParams* p, float* variance_out)

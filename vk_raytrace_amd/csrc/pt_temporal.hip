@@ -46,59 +46,63 @@ __global__ void __launch_bounds__(TP_BLOCK) k_temporal(TpArgs a)
   a.hnOut[at]          = o.length;
 }
 
-// with tracking on (pt_temporal_track_moments) the kernel of pt_svgf.hip runs instead: the same pixel function, and the moments image besides.
+// The host-side record of one step: its images and its constants.  TpArgs above is k_temporal's kernel argument and is filled at that kernel's launch line only.
+struct StepArgs {
+  TemporalMArgs m;
+  TemporalConst k;
+};
+
+// with the moments image (pt_temporal_track_moments) the kernel of pt_svgf.hip runs instead: the same pixel function, and the moments image besides.
 // moving: the kernels of pt_motion.hip (section 5.5), over the instance plane and the table prepare_temporal uploaded (none without a history).
 // demodulating (pt_temporal_demodulate): the kernels of pt_albedo.hip (section 5.6), which read guide plane 0 besides -- prepare_temporal saw to it.
-// moments: with the moments image (the long step of a context that tracks them; the fast step of section 5.7 never has one)
-static void launch_step(const pt_context* c, const TpArgs& a, bool moving, bool moments)
+static void launch_step(const pt_context* c, const StepArgs& s, bool moving)
 {
-  if(moments || moving || c->demodulate)
-  {
-    const int           r = c->histSet;
-    const TemporalMArgs m{a.c, a.g1, a.g2, a.hc, a.hg, a.hn, moments ? (const float2*)c->dHistMoments[r].p : nullptr, a.hcOut, a.hgOut, a.hnOut,
-                          moments ? (float2*)c->dHistMoments[r ^ 1].p : nullptr, a.w, a.h};
-    if(c->demodulate)
-      launch_temporal_d(c->stream, m, a.k, (const float4*)c->dGuide[0].p, moving, (const uint32_t*)c->dInstPlane.p, (const MotionRec*)c->dMotionTable.p,
-                        moving && c->haveHistory ? uint32_t(c->hInstances.size()) : 0u);
-    else if(moving)
-      launch_temporal_moving(c->stream, m, a.k, (const uint32_t*)c->dInstPlane.p, (const MotionRec*)c->dMotionTable.p, c->haveHistory ? uint32_t(c->hInstances.size()) : 0u);
-    else
-      launch_temporal_m(c->stream, m, a.k);
-    return;
-  }
-  k_temporal<<<stage_grid(a.w, a.h, TP_TX, TP_TY), dim3(TP_TX, TP_TY), 0, c->stream>>>(a);
+  const TemporalMArgs& m     = s.m;
+  const uint32_t*      ids   = (const uint32_t*)c->dInstPlane.p;
+  const MotionRec*     table = (const MotionRec*)c->dMotionTable.p;
+  const uint32_t       n     = moving && c->hist.have ? uint32_t(c->hInstances.size()) : 0u;  // (without a history there is no table)
+  if(c->histSettings.demodulate)
+    launch_temporal_d(c->stream, m, s.k, (const float4*)c->dGuide[0].p, moving, ids, table, n);
+  else if(moving)
+    launch_temporal_moving(c->stream, m, s.k, ids, table, n);
+  else if(m.hmOut)
+    launch_temporal_m(c->stream, m, s.k);
+  else
+    k_temporal<<<stage_grid(m.w, m.h, TP_TX, TP_TY), dim3(TP_TX, TP_TY), 0, c->stream>>>(TpArgs{m.c, m.g1, m.g2, m.hc, m.hg, m.hn, m.hcOut, m.hgOut, m.hnOut, m.w, m.h, s.k});
 }
 
-// The fast step's arguments (section 5.7): the long step's with the fast images in the place of Hc and Hn and maxFast in the place of maxHistory.  It
-// reads (Hf, Hg, Hnf) of the set that is read and writes (Hf', Hnf'); Hg' is written again with the bits the long step gave it.
-static TpArgs fast_step_args(const pt_context* c, const TpArgs& a, const FastConst& f)
+// The fast step's arguments (section 5.7), and the setting's constants in f: the long step's with the fast images in the place of Hc and Hn, maxFast in the place of
+// maxHistory and no moments.  It reads (Hf, Hg, Hnf) of the set that is read and writes (Hf', Hnf'); Hg' is written again with the bits the long step gave it.
+static StepArgs fast_step_args(const pt_context* c, const StepArgs& a, FastConst& f)
 {
-  const int r = c->histSet, wr = r ^ 1;
-  TpArgs    b = a;
-  b.hc           = (const float4*)c->dHistFast[r].p;
-  b.hn           = (const float*)c->dHistFastLength[r].p;
-  b.hcOut        = (float4*)c->dHistFast[wr].p;
-  b.hnOut        = (float*)c->dHistFastLength[wr].p;
-  b.k.maxHistory = f.maxFast;
+  const char* why = "";
+  (void)fast_constants(&c->histSettings.fastParams, &f, &why);  // (pt_temporal_fast accepted them)
+  const History& H = c->hist;
+  StepArgs       b = a;
+  b.m.hc           = (const float4*)H.fast[H.rd()].p;
+  b.m.hn           = (const float*)H.fastLength[H.rd()].p;
+  b.m.hm           = nullptr;
+  b.m.hcOut        = (float4*)H.fast[H.wr()].p;
+  b.m.hnOut        = (float*)H.fastLength[H.wr()].p;
+  b.m.hmOut        = nullptr;
+  b.k.maxHistory   = f.maxFast;
   return b;
 }
-static void enqueue_clamp(const pt_context* c, const TpArgs& a, const TpArgs& b, const FastConst& f)
+static void enqueue_clamp(const pt_context* c, const StepArgs& a, const StepArgs& b, const FastConst& f)
 {
-  launch_fast_clamp(c->stream, b.hcOut, b.hnOut, a.hcOut, a.hnOut, a.w, a.h, f);
+  launch_fast_clamp(c->stream, b.m.hcOut, b.m.hnOut, a.m.hcOut, a.m.hnOut, a.m.w, a.m.h, f);
 }
 
 // One call's kernels, enqueued on the context's stream: the long step; with pt_temporal_fast on, the fast step -- the same kernel over other pointers,
 // without moments -- and the clamp of what the long step wrote, in place, behind both.
-static void launch_temporal(const pt_context* c, const TpArgs& a, bool moving = false)
+static void launch_temporal(const pt_context* c, const StepArgs& a, bool moving = false)
 {
-  launch_step(c, a, moving, c->trackMoments);
-  if(!c->fast)
+  launch_step(c, a, moving);
+  if(!c->histSettings.fast)
     return;
-  FastConst   f{};
-  const char* why = "";
-  (void)fast_constants(&c->fastParams, &f, &why);  // (pt_temporal_fast accepted them)
-  const TpArgs b = fast_step_args(c, a, f);
-  launch_step(c, b, moving, false);
+  FastConst      f{};
+  const StepArgs b = fast_step_args(c, a, f);
+  launch_step(c, b, moving);
   enqueue_clamp(c, a, b, f);
 }
 
@@ -115,15 +119,16 @@ static std::vector<float> instance_words(const pt_context* c)
 // Everything pt_temporal_accumulate checks, then both history sets allocated and the row-major accumulation image enqueued on the context's stream
 // behind the frames rendered so far; the kernel's arguments in `a`.  Nothing of the history changes here.  moving: what the moving form needs besides,
 // and its motion table made from the transforms kept with the history and the scene's current ones, on the device.
-static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalParams* p, TpArgs& a, bool moving = false)
+static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalParams* p, StepArgs& a, bool moving = false)
 {
+  History& H = c->hist;
   STAGE_TRY(stage_need_image(c, who));
   if(!c->haveCamera)
     return c->fail(PT_ERR_STATE, "%s before pt_set_camera", who);
   if(!c->dGuide[1].p || !c->dGuide[2].p)
     return c->fail(PT_ERR_STATE, "%s: guide planes 1 (normal) and 2 (depth) must be installed (pt_render_guides or pt_set_denoise_guides)", who);
   const char* needs = "";
-  if(albedo_step_needs_plane(c->demodulate, guide_planes_set(c), &needs) != PT_OK)
+  if(albedo_step_needs_plane(c->histSettings.demodulate, guide_planes_set(c), &needs) != PT_OK)
     return c->fail(PT_ERR_STATE, "%s: %s", who, needs);
   STAGE_TRY(stage_need_full_image(c, who));
   const char* why = "";
@@ -136,73 +141,40 @@ static int prepare_temporal(pt_context* c, const char* who, const pt_TemporalPar
       return c->fail(PT_ERR_STATE, "%s: no instance plane is installed (pt_render_instance_plane or pt_set_instance_plane)", who);
     if(!c->haveScene)
       return c->fail(PT_ERR_STATE, "%s before pt_set_scene", who);
-    if(c->haveHistory && c->histInst.size() != c->hInstances.size() * PT_MOTION_INSTANCE_WORDS)
-      return c->fail(PT_ERR_STATE, "%s: the history was made with %zu instances, the scene has %zu (pt_temporal_reset)", who, c->histInst.size() / PT_MOTION_INSTANCE_WORDS,
+    if(H.have && H.inst.size() != c->hInstances.size() * PT_MOTION_INSTANCE_WORDS)
+      return c->fail(PT_ERR_STATE, "%s: the history was made with %zu instances, the scene has %zu (pt_temporal_reset)", who, H.inst.size() / PT_MOTION_INSTANCE_WORDS,
                      c->hInstances.size());
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  if(moving && c->haveHistory)
+  if(moving && H.have)
   {
     const std::vector<float> cur = instance_words(c);
     std::vector<MotionRec>   table(c->hInstances.size());
-    motion_table(c->histInst.data(), cur.data(), uint32_t(table.size()), table.data());
+    motion_table(H.inst.data(), cur.data(), uint32_t(table.size()), table.data());
     STAGE_TRY(upload(c, c->dMotionTable, table.data(), sizeof(MotionRec) * table.size()));
   }
-  const size_t n = stage_pixels(c);
-  for(int s = 0; s < 2; ++s)
-  {
-    STAGE_TRY(dev_alloc(c, c->dHistColour[s], sizeof(float4) * n));
-    STAGE_TRY(dev_alloc(c, c->dHistGuide[s], sizeof(float4) * n));
-    STAGE_TRY(dev_alloc(c, c->dHistLength[s], sizeof(float) * n));
-  }
-  if(c->trackMoments)
-    for(int s = 0; s < 2; ++s)
-      STAGE_TRY(dev_alloc(c, c->dHistMoments[s], sizeof(float2) * n));
-  if(c->fast)
-    for(int s = 0; s < 2; ++s)
-    {
-      STAGE_TRY(dev_alloc(c, c->dHistFast[s], sizeof(float4) * n));
-      STAGE_TRY(dev_alloc(c, c->dHistFastLength[s], sizeof(float) * n));
-    }
+  STAGE_TRY(H.alloc(c, c->histSettings, stage_pixels(c)));
   STAGE_TRY(untile_to_rowmajor(c));
-  const int r = c->histSet, wr = r ^ 1;
-  a.c     = (const float4*)c->dRowMajor.p;
-  a.g1    = (const float4*)c->dGuide[1].p;
-  a.g2    = (const float4*)c->dGuide[2].p;
-  a.hc    = (const float4*)c->dHistColour[r].p;
-  a.hg    = (const float4*)c->dHistGuide[r].p;
-  a.hn    = (const float*)c->dHistLength[r].p;
-  a.hcOut = (float4*)c->dHistColour[wr].p;
-  a.hgOut = (float4*)c->dHistGuide[wr].p;
-  a.hnOut = (float*)c->dHistLength[wr].p;
-  a.w     = c->width;
-  a.h     = c->height;
-  a.k     = temporal_const(c->scene.camera.viewInverse, c->scene.camera.projInverse, c->haveHistory ? c->histWorldToClip : nullptr,
-                           c->haveHistory ? c->histEye : nullptr, p);
+  const int  r = H.rd(), wr = H.wr();
+  const bool mom = c->histSettings.trackMoments;
+  a.m = TemporalMArgs{(const float4*)c->dRowMajor.p, (const float4*)c->dGuide[1].p, (const float4*)c->dGuide[2].p, (const float4*)H.colour[r].p, (const float4*)H.guide[r].p,
+                      (const float*)H.length[r].p, mom ? (const float2*)H.moments[r].p : nullptr, (float4*)H.colour[wr].p, (float4*)H.guide[wr].p,
+                      (float*)H.length[wr].p, mom ? (float2*)H.moments[wr].p : nullptr, c->width, c->height};
+  a.k = temporal_const(c->scene.camera.viewInverse, c->scene.camera.projInverse, H.have ? H.worldToClip : nullptr, H.have ? H.eye : nullptr, p);
   return PT_OK;
 }
 
 // one call of either form
 static int temporal_accumulate(pt_context* c, const char* who, const pt_TemporalParams* p, float* out, bool moving)
 {
-  TpArgs a;
+  StepArgs a;
   STAGE_TRY(prepare_temporal(c, who, p, a, moving));
   launch_temporal(c, a, moving);
   HIP_TRY(c, hipGetLastError());
   if(out)
-    HIP_TRY(c, hipMemcpyAsync(out, a.hcOut, sizeof(float4) * stage_pixels(c), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, a.m.hcOut, sizeof(float4) * stage_pixels(c), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, sync_all(c));
-  // the set just written is the history now, made with the current camera
-  for(int i = 0; i < 16; ++i)
-    c->histWorldToClip[i] = p->worldToClip[i];
-  for(int i = 0; i < 3; ++i)
-    c->histEye[i] = c->scene.camera.viewInverse[12 + i];
-  c->histSet ^= 1;
-  c->haveHistory     = true;
-  c->histHasMoments  = c->trackMoments;
-  c->histDemodulated = c->demodulate;      // what rgba32f_out and the history hold is illumination then (section 5.6)
-  c->histFast        = c->fast;            // the fast images swapped with the others (section 5.7)
-  c->histInst        = instance_words(c);  // ... and the current instance transforms (section 5.5)
+  c->hist.commit(c->histSettings, p->worldToClip, &c->scene.camera.viewInverse[12], instance_words(c));
   return check_traversal(c);
 }
 
@@ -223,7 +195,7 @@ int pt_temporal_accumulate_moving(pt_context* c, const pt_TemporalParams* p, flo
 int pt_temporal_reset(pt_context* c)
 {
   CTX_CHECK(c);
-  c->haveHistory = c->histHasMoments = c->histDemodulated = c->histFast = false;  // the buffers stay for the next call; pt_resize and pt_destroy free them
+  c->hist.drop();  // the buffers stay for the next call; pt_resize and pt_destroy free them
   return PT_OK;
 }
 
@@ -232,11 +204,7 @@ int pt_temporal_track_moments(pt_context* c, int on)
   CTX_CHECK(c);
   if(on != 0 && on != 1)
     return c->fail(PT_ERR_INVALID, "pt_temporal_track_moments: on must be 0 or 1");
-  if((on != 0) != c->trackMoments)
-  {
-    c->trackMoments = on != 0;
-    c->haveHistory = c->histHasMoments = c->histDemodulated = c->histFast = false;  // a history without moments cannot be continued with them, and the other way round
-  }
+  c->hist.set_to(c->histSettings.trackMoments, on != 0);  // a history without moments cannot be continued with them, and the other way round
   return PT_OK;
 }
 
@@ -246,11 +214,7 @@ int pt_temporal_demodulate(pt_context* c, int on)
   const char* why = "";
   if(albedo_setting(on, &why) != PT_OK)
     return c->fail(PT_ERR_INVALID, "pt_temporal_demodulate: %s", why);
-  if((on != 0) != c->demodulate)
-  {
-    c->demodulate = on != 0;
-    c->haveHistory = c->histHasMoments = c->histDemodulated = c->histFast = false;  // a history of colour cannot be continued with illumination, and the other way round
-  }
+  c->hist.set_to(c->histSettings.demodulate, on != 0);  // a history of colour cannot be continued with illumination, and the other way round
   return PT_OK;
 }
 
@@ -263,13 +227,9 @@ int pt_temporal_fast(pt_context* c, const pt_FastParams* p)
     const int   rc  = fast_constants(p, nullptr, &why);
     if(rc != PT_OK)
       return c->fail(rc, "pt_temporal_fast: %s", why);
-    c->fastParams = *p;  // new parameters while the setting stays on keep the history
+    c->histSettings.fastParams = *p;  // new parameters while the setting stays on keep the history
   }
-  if((p != nullptr) != c->fast)
-  {
-    c->fast = p != nullptr;
-    c->haveHistory = c->histHasMoments = c->histDemodulated = c->histFast = false;  // a history without the fast images cannot be continued with them, and the other way round
-  }
+  c->hist.set_to(c->histSettings.fast, p != nullptr);  // a history without the fast images cannot be continued with them, and the other way round
   return PT_OK;
 }
 
@@ -278,11 +238,11 @@ int pt_read_temporal_fast(pt_context* c, float* rgba32f_out, float* length_out)
   CTX_CHECK(c);
   STAGE_TRY(stage_need_history(c, "pt_read_temporal_fast", false));
   const char* why = "";
-  if(fast_need_history(c->histFast, &why) != PT_OK)
+  if(fast_need_history(c->hist.isFast, &why) != PT_OK)
     return c->fail(PT_ERR_STATE, "pt_read_temporal_fast: %s", why);
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t n = stage_pixels(c);
-  return stage_read(c, {{rgba32f_out, c->dHistFast[c->histSet].p, sizeof(float4) * n}, {length_out, c->dHistFastLength[c->histSet].p, sizeof(float) * n}});
+  return stage_read(c, {{rgba32f_out, c->hist.fast[c->hist.rd()].p, sizeof(float4) * n}, {length_out, c->hist.fastLength[c->hist.rd()].p, sizeof(float) * n}});
 }
 
 int pt_read_temporal_history(pt_context* c, float* rgba32f_out, float* length_out)
@@ -291,7 +251,7 @@ int pt_read_temporal_history(pt_context* c, float* rgba32f_out, float* length_ou
   STAGE_TRY(stage_need_history(c, "pt_read_temporal_history", false));
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t n = stage_pixels(c);
-  return stage_read(c, {{rgba32f_out, c->dHistColour[c->histSet].p, sizeof(float4) * n}, {length_out, c->dHistLength[c->histSet].p, sizeof(float) * n}});
+  return stage_read(c, {{rgba32f_out, c->hist.colour[c->hist.rd()].p, sizeof(float4) * n}, {length_out, c->hist.length[c->hist.rd()].p, sizeof(float) * n}});
 }
 
 // Measurement access (not part of pt_api.h; tools/temporal_rate.py): the kernel of pt_temporal_accumulate enqueued `reps` times between two events on
@@ -302,7 +262,7 @@ __attribute__((visibility("default"))) int pt_debug_temporal_time(pt_context* c,
   CTX_CHECK(c);
   if(!ms_out || reps < 1)
     return c->fail(PT_ERR_INVALID, "pt_debug_temporal_time: null or reps < 1");
-  TpArgs a;
+  StepArgs a;
   STAGE_TRY(prepare_temporal(c, "pt_debug_temporal_time", p, a));
   return stage_time(c, "pt_debug_temporal_time", reps, ms_out, [&] { launch_temporal(c, a); });  // (the kernel the setting of pt_temporal_track_moments selects)
 }
@@ -317,7 +277,7 @@ __attribute__((visibility("default"))) int pt_debug_motion_time(pt_context* c, c
     return c->fail(PT_ERR_INVALID, "pt_debug_motion_time: null, reps < 1 or no such part");
   if(what == 0)
     return debug_instances_time(c, planes, miss_depth, reps, ms_out);
-  TpArgs a;
+  StepArgs a;
   STAGE_TRY(prepare_temporal(c, "pt_debug_motion_time", p, a, true));
   return stage_time(c, "pt_debug_motion_time", reps, ms_out, [&] { launch_temporal(c, a, true); });
 }
@@ -332,9 +292,9 @@ __attribute__((visibility("default"))) int pt_debug_albedo_time(pt_context* c, c
     return c->fail(PT_ERR_INVALID, "pt_debug_albedo_time: null, reps < 1 or no such part");
   if(what == 1)
     return debug_remodulate_time(c, reps, ms_out);
-  if(!c->demodulate)
+  if(!c->histSettings.demodulate)
     return c->fail(PT_ERR_STATE, "pt_debug_albedo_time: pt_temporal_demodulate is off");
-  TpArgs a;
+  StepArgs a;
   STAGE_TRY(prepare_temporal(c, "pt_debug_albedo_time", p, a));
   return stage_time(c, "pt_debug_albedo_time", reps, ms_out, [&] { launch_temporal(c, a); });
 }
@@ -348,16 +308,14 @@ __attribute__((visibility("default"))) int pt_debug_fast_time(pt_context* c, con
   CTX_CHECK(c);
   if(!ms_out || reps < 1 || (what != 0 && what != 1))
     return c->fail(PT_ERR_INVALID, "pt_debug_fast_time: null, reps < 1 or no such part");
-  if(!c->fast)
+  if(!c->histSettings.fast)
     return c->fail(PT_ERR_STATE, "pt_debug_fast_time: pt_temporal_fast is off");
   STAGE_TRY(stage_need_history(c, "pt_debug_fast_time", false));
-  TpArgs a;
+  StepArgs a;
   STAGE_TRY(prepare_temporal(c, "pt_debug_fast_time", p, a));
-  FastConst   f{};
-  const char* why = "";
-  (void)fast_constants(&c->fastParams, &f, &why);
-  const TpArgs b = fast_step_args(c, a, f);
-  return stage_time(c, "pt_debug_fast_time", reps, ms_out, [&] { what == 0 ? launch_step(c, b, false, false) : enqueue_clamp(c, a, b, f); }, [&] { launch_temporal(c, a); });
+  FastConst      f{};
+  const StepArgs b = fast_step_args(c, a, f);
+  return stage_time(c, "pt_debug_fast_time", reps, ms_out, [&] { what == 0 ? launch_step(c, b, false) : enqueue_clamp(c, a, b, f); }, [&] { launch_temporal(c, a); });
 }
 
 }  // extern "C"
