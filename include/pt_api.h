@@ -500,6 +500,25 @@ int pt_pick(pt_context* ctx, float pick_x, float pick_y, const float view_invers
  * launched.  A query touches neither the accumulation image, the path state, the frame slots nor any pt_Stats field. */
 int pt_trace_rays(pt_context* ctx, int kind, uint32_t flags, uint64_t n, const pt_Ray* rays, pt_RayHit* hits, uint32_t hits_per_ray);
 
+/* Path queries: the radiance along a caller's own rays (stands in for PathTrace of shaders/pathtrace.glsl, called from the sample loop of
+ * shaders/pathtrace.comp:97-105, without that shader's pinhole camera and image: light-map and irradiance-probe baking, panoramas, fisheye,
+ * orthographic and stereo views, re-sampling chosen pixels, the radiance along one ray from a surface point).  Defined in DESIGN.md section 3.2.
+ * Per ray: seed = ray.seed; for each of state->maxSamples samples a path starts on the SAME ray (origin, direction; tmax is ignored, the first ray is
+ * unbounded like PT_RAYS_CLOSEST) and runs the frames' path loop to state->maxDepth -- emission, direct light with MIS, both BSDFs, Russian
+ * roulette -- on the stream that continues from the previous sample; its radiance is clamped as the frames clamp it (fireflyClampThreshold) and
+ * summed in sample order; radiance = sum / maxSamples.  (A frame draws a new camera ray per sample; a caller who wants that changes the ray between
+ * one-sample calls.)  One sample on the camera ray of a pixel of frame 0 with that pixel's seed is that pixel of frame 0, bit for bit.
+ * state: maxDepth (0 .. PT_MAX_DEPTH), maxSamples (1 .. PT_PATHS_MAX_SAMPLES), fireflyClampThreshold, hdrMultiplier, pbrMode (0 / 1) and
+ * debugging_mode (every mode but PT_DEBUG_HEATMAP, which needs a frame's clocks) are read; frame, size and the heat-map bounds are ignored.
+ * Invalid rays (pt_trace_rays' rule without tmax): radiance 0, firstT 0, seed unchanged, closestRays 0, status PT_RAY_INVALID; not walked.
+ * flags: PT_RAYS_DEVICE as for pt_trace_rays (16-byte aligned device arrays, in place); host arrays are staged through the same two buffers.
+ * Needs what pt_render_frame needs of the scene side -- pt_set_scene, pt_build_accel, an environment or sun & sky, pt_set_camera (only its nbLights
+ * is read) -- else PT_ERR_STATE; no pt_resize.  Synchronous like pt_trace_rays: waits for the frames in flight, runs on the context's stream,
+ * reports a traversal-stack overflow with PT_ERR_STATE.  n == 0: PT_OK.  Null pointers with n > 0, an unknown flag bit, a misaligned device
+ * pointer or a state outside the ranges above: PT_ERR_INVALID, nothing is launched.  A path query touches neither the accumulation image, the
+ * path state, the frame slots nor any pt_Stats field: frames before and after it come out as if it had not happened. */
+int pt_trace_paths(pt_context* ctx, const pt_RtxState* state, uint32_t flags, uint64_t n, const pt_Ray* rays, pt_PathResult* results);
+
 /* Measures, on this device, the two ceilings the measurement contract prices kernels against (no reference counterpart): VALU issue
  * (independent wave64 v_fma_f32 at 8 waves per SIMD on every CU, wave-instructions per second) and HBM streaming (float4 copy and
  * read-only over 1 GiB buffers, bytes per second).  Synchronous, a few tens of milliseconds. */

@@ -106,6 +106,10 @@ public:
   bool traceRays(int kind, uint64_t n, const pt_Ray* rays, pt_RayHit* hits, uint32_t hitsPerRay = 1) { return check(pt_trace_rays(m_ctx, kind, 0u, n, rays, hits, hitsPerRay)); }
   // ... and on 16-byte aligned device memory of the context's GPU, in place
   bool traceRaysDevice(int kind, uint64_t n, const pt_Ray* dRays, pt_RayHit* dHits, uint32_t hitsPerRay = 1) { return check(pt_trace_rays(m_ctx, kind, PT_RAYS_DEVICE, n, dRays, dHits, hitsPerRay)); }
+  // the radiance along a caller's own rays (PathTrace of shaders/pathtrace.glsl under the sample loop of pathtrace.comp, without its camera and
+  // image): pt_trace_paths on host arrays, and on 16-byte aligned device memory of the context's GPU
+  bool tracePaths(const pt_RtxState& state, uint64_t n, const pt_Ray* rays, pt_PathResult* results) { return check(pt_trace_paths(m_ctx, &state, 0u, n, rays, results)); }
+  bool tracePathsDevice(const pt_RtxState& state, uint64_t n, const pt_Ray* dRays, pt_PathResult* dResults) { return check(pt_trace_paths(m_ctx, &state, PT_RAYS_DEVICE, n, dRays, dResults)); }
   void readAccum(float* rgba32f) { check(pt_read_accum(m_ctx, rgba32f)); }
   void writeAccum(const float* rgba32f) { check(pt_write_accum(m_ctx, rgba32f)); }  // checkpoint restore
   void useAnyHit(bool enable) { check(pt_use_any_hit(m_ctx, enable ? 1 : 0)); }  // RtxPipeline::useAnyHit

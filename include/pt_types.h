@@ -255,6 +255,18 @@ enum { PT_RAYS_CLOSEST = 0, PT_RAYS_OCCLUDED = 1, PT_RAYS_NEAREST = 2, PT_RAYS_C
 #define PT_RAYS_MAX_HITS 16u   /* largest hits_per_ray of PT_RAYS_CANDIDATES */
 #define PT_QUERY_CHUNK (1u << 20) /* host arrays are staged through two device buffers of this many records (32 MB each) */
 
+/* pt_trace_paths: one pt_Ray in, one record out (32 bytes, like pt_RayHit).  Stands in for what PathTrace of shaders/pathtrace.glsl returns along the
+ * ray, averaged over the sample loop of shaders/pathtrace.comp; defined in DESIGN.md section 3.2 ("Path queries") and stated at pt_trace_paths. */
+typedef struct pt_PathResult {
+  float    radiance[3]; /* mean over the samples of the firefly-clamped path radiance */
+  float    firstT;      /* t of the first sample's first closest hit; 0 on a miss */
+  uint32_t seed;        /* RNG state after the last sample */
+  uint32_t status;      /* PT_RAY_HIT: the first sample's first ray hit something; PT_RAY_INVALID: the ray was not walked */
+  uint32_t closestRays; /* closest-hit rays traced over all samples */
+  uint32_t _pad;        /* 0 */
+} pt_PathResult;
+#define PT_PATHS_MAX_SAMPLES 65536 /* largest RtxState.maxSamples of pt_trace_paths */
+
 /* pt_denoise / pt_tonemap_denoised: the edge-avoiding a-trous filter between the accumulation image and the display pass (no reference counterpart;
  * defined in DESIGN.md "Denoiser" and stated once in csrc/pt_denoise.h).  Guide planes are row-major RGBA32F images of the accumulation size whose
  * .xyz steer the weights; by convention plane 0 is the albedo (the only one PT_DENOISE_DEMODULATE reads), 1 the normal, 2 the depth in .x. */
@@ -361,6 +373,7 @@ static_assert(sizeof(pt_SunAndSky) == 96, "SunAndSky");
 static_assert(sizeof(pt_PrimMesh) == 20, "PrimMesh");
 static_assert(sizeof(pt_Node) == 68, "Node");
 static_assert(sizeof(pt_Ray) == 32 && sizeof(pt_RayHit) == 32, "Ray / RayHit");
+static_assert(sizeof(pt_PathResult) == sizeof(pt_RayHit), "PathResult: staged through the buffers of pt_trace_rays");
 static_assert(sizeof(pt_DenoiseParams) == 24, "DenoiseParams");
 static_assert(sizeof(pt_TemporalParams) == 80, "TemporalParams");
 static_assert(sizeof(pt_SvgfParams) == 32, "SvgfParams");

@@ -121,6 +121,8 @@ struct pt_context {
   DevBuf   dFrame, dSlotTile, dCounters;
   DevBuf   dPick;
   DevBuf   dQueryRays, dQueryHits;  // pt_trace_rays with host arrays: staging buffers of PT_QUERY_CHUNK records each, allocated on first use
+  DevBuf   dPathsChunk;             // pt_trace_paths (pt_paths.hip): the word its wavefronts reserve rays from, cleared on the stream before each launch
+  int      pathsWaves = 0;          // wavefronts of its launches (0: the default; pt_debug_paths_waves)
   DevBuf   dRowMajor, dRgba8, dMean, dMips, dGather, dFullTiles, dFullSlotTile, dTileLocalIndex;
   // denoiser (pt_denoise.hip): the two ping-pong images, allocated on first use, and the caller's guide planes; pt_resize and pt_destroy free them
   DevBuf   dDenoise[2], dGuide[PT_DENOISE_GUIDES];

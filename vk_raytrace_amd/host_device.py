@@ -115,6 +115,12 @@ class RayHit(C.Structure):
                 ("seed", C.c_uint32), ("status", C.c_uint32)]
 
 
+class PathResult(C.Structure):
+    """pt_PathResult (pt_trace_paths): the mean clamped radiance along the ray, the first sample's first hit distance (0: miss), the RNG state after
+    the last sample, PT_RAY_HIT / PT_RAY_INVALID, the closest-hit rays traced over all samples"""
+    _fields_ = [("radiance", C.c_float * 3), ("firstT", C.c_float), ("seed", C.c_uint32), ("status", C.c_uint32), ("closestRays", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class DenoiseParams(C.Structure):
     """pt_DenoiseParams (pt_denoise, pt_tonemap_denoised): sigmaColor 0 switches the colour term off; sigmaGuide[j] is read for installed planes only"""
     _fields_ = [("iterations", C.c_int32), ("sigmaColor", C.c_float), ("sigmaGuide", C.c_float * 3), ("flags", C.c_uint32)]
@@ -164,11 +170,12 @@ assert C.sizeof(RtxState) == 48 and C.sizeof(SceneCamera) == 140 and C.sizeof(Ve
 assert C.sizeof(GltfShadeMaterial) == 216 and C.sizeof(Light) == 64 and C.sizeof(EnvAccel) == 16
 assert C.sizeof(Tonemapper) == 48 and C.sizeof(SunAndSky) == 96 and C.sizeof(PrimMesh) == 20 and C.sizeof(Node) == 68
 assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32 and C.sizeof(DenoiseParams) == 24 and C.sizeof(TemporalParams) == 80
-assert C.sizeof(SvgfParams) == 32 and C.sizeof(FastParams) == 16
+assert C.sizeof(SvgfParams) == 32 and C.sizeof(FastParams) == 16 and C.sizeof(PathResult) == 32
 
 vertex_dtype = np.dtype(VertexAttributes)
 ray_dtype = np.dtype(Ray)
 rayhit_dtype = np.dtype(RayHit)
+pathresult_dtype = np.dtype(PathResult)
 material_dtype = np.dtype(GltfShadeMaterial)
 light_dtype = np.dtype(Light)
 primmesh_dtype = np.dtype(PrimMesh)

@@ -210,6 +210,33 @@ class HipRenderer(Renderer):
         the results are in place when the call returns."""
         self._check(self._lib.pt_trace_rays(self._ctx, int(kind), capi.PT_RAYS_DEVICE, int(n), C.c_void_p(int(rays_ptr)), C.c_void_p(int(hits_ptr)), int(hits_per_ray)))
 
+    def trace_paths(self, state: hd.RtxState, origins, directions, seeds=None):
+        """pt_trace_paths on host arrays: the radiance along each ray (origins, directions: (n, 3); seeds (n,) uint32, default 0: the RNG state each
+        ray's paths start from) under `state` -- maxDepth, maxSamples, fireflyClampThreshold, hdrMultiplier, pbrMode and debugging_mode are read.
+        Returns a structured array (hd.pathresult_dtype) of shape (n,)."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("trace_paths: origins and directions differ in length")
+        rays = np.zeros(len(o), hd.ray_dtype)
+        rays["origin"], rays["direction"] = o, d
+        rays["tmax"] = np.inf  # (ignored: the first ray of a path is unbounded)
+        rays["seed"] = 0 if seeds is None else np.asarray(seeds, np.uint32)
+        return self.trace_path_records(state, rays)
+
+    def trace_path_records(self, state: hd.RtxState, rays):
+        """pt_trace_paths on an array of hd.ray_dtype records (what trace_paths assembles)"""
+        rays = np.ascontiguousarray(rays, hd.ray_dtype)
+        out = np.zeros(len(rays), hd.pathresult_dtype)
+        self._check(self._lib.pt_trace_paths(self._ctx, C.byref(state), 0, len(rays), rays.ctypes.data, out.ctypes.data))
+        return out
+
+    def trace_paths_device(self, state: hd.RtxState, rays_ptr, results_ptr, n):
+        """pt_trace_paths with PT_RAYS_DEVICE: rays_ptr / results_ptr are plain integers, the addresses of n pt_Ray and n pt_PathResult records in the
+        memory of the context's GPU (16-byte aligned), e.g. a torch tensor's data_ptr().  The caller owns the memory and keeps it alive; the results
+        are in place when the call returns."""
+        self._check(self._lib.pt_trace_paths(self._ctx, C.byref(state), capi.PT_RAYS_DEVICE, int(n), C.c_void_p(int(rays_ptr)), C.c_void_p(int(results_ptr))))
+
     def tonemap(self, tm: hd.Tonemapper, display_size=None):
         """RenderOutput::genMipmap + run.  display_size (W, H): the viewport while de-scaling (Tonemapper.zoom = 1 / level)."""
         w, h = display_size or self.size
