@@ -335,6 +335,22 @@ int pt_set_instance_plane(pt_context* ctx, const uint32_t* ids);
  * there.  Synchronous like pt_read_denoise_guides.  PT_ERR_STATE: before pt_resize; no plane is installed.  ids_out == NULL: PT_ERR_INVALID. */
 int pt_read_instance_plane(pt_context* ctx, uint32_t* ids_out);
 
+/* No reference counterpart.  The chained guide pass (csrc/pt_chain.h): pt_render_guides, but the pixel's camera ray is
+ * followed through mirrors and clear glass (pt_GuideChain, pt_types.h) and the selected planes are written for the first surface that is neither:
+ * plane 0 the product of the base colours along the chain times the end surface's, plane 1 the end surface's normal, plane 2 the summed length of the
+ * chain (the virtual depth, which pt_temporal_accumulate reprojects correctly for a planar mirror).  A chain that leaves the scene after at least one
+ * link gives (tint, 1), (0, 0, 0, 1) and (length so far + miss_depth, 0, 0, 0).  With maxLinks == 0, or where nothing is followable, the planes are
+ * bit for bit pt_render_guides'.  A kernel of its own; besides the guide planes it writes the context's link plane, one word per pixel:
+ * links | end << 8, end = 0 a surface that is not followed, 1 a miss, 2 the link limit, 3 a direction that cannot be followed.  Asynchronous, side
+ * effects and errors as pt_render_guides; PT_ERR_INVALID besides, with nothing launched: chain == NULL, maxLinks > PT_GUIDE_CHAIN_MAX_LINKS, a
+ * threshold that is negative or not finite, any flag bit. */
+int pt_render_guides_chain(pt_context* ctx, const pt_GuideChain* chain, uint32_t planes, float miss_depth);
+
+/* No reference counterpart.  Copies the link plane of the latest pt_render_guides_chain (width * height words, row-major) out.  Synchronous like
+ * pt_read_denoise_guides.  PT_ERR_STATE: before pt_resize; no chained pass ran at the current size (a pt_resize to another size drops the plane).
+ * links_out == NULL: PT_ERR_INVALID. */
+int pt_read_guide_chain(pt_context* ctx, uint32_t* links_out /* W*H, row-major */);
+
 /* No reference counterpart.  pt_temporal_accumulate for a scene whose nodes moved since the history was made (pt_update_instances): a pixel whose
  * instance plane entry names a node whose world matrix changed takes its point and its normal through that node's motion (history transform o inverse
  * of the current one; the inverse transpose for the normal) before the reprojection and the tap tests; every other pixel, and everything that is

@@ -145,6 +145,13 @@ public:
   bool temporalAccumulate(const pt_TemporalParams& p, float* rgba32f = nullptr) { return check(pt_temporal_accumulate(m_ctx, &p, rgba32f)); }
   bool temporalReset() { return check(pt_temporal_reset(m_ctx)); }
   bool readTemporalHistory(float* rgba32f, float* length) { return check(pt_read_temporal_history(m_ctx, rgba32f, length)); }
+  // ... or for the first surface behind mirrors and clear glass (no reference counterpart): the same planes, and the link plane
+  // (width * height words: links | end << 8) read back
+  bool renderGuidesChain(const pt_GuideChain& chain, uint32_t planes = PT_GUIDES_BASECOLOR | PT_GUIDES_NORMAL | PT_GUIDES_DEPTH, float missDepth = 1.0e30f)
+  {
+    return check(pt_render_guides_chain(m_ctx, &chain, planes, missDepth));
+  }
+  bool readGuideChain(uint32_t* links) { return check(pt_read_guide_chain(m_ctx, links)); }
   // motion of moving instances (no reference counterpart): after updateInstances, renderInstancePlane in place of renderGuides
   // (the same pass; guidePlanes may be 0) and temporalAccumulateMoving in place of temporalAccumulate -- pixels of a node that moved take their point and
   // normal through its motion before they are reprojected.  The plane holds node indices (width * height words; PT_INSTANCE_NONE: nothing hit).

@@ -299,6 +299,19 @@ typedef struct pt_FastParams {
   uint32_t flags;      /* none defined: must be 0 */
 } pt_FastParams;
 
+/* pt_render_guides_chain: the guide pass that follows mirrors and clear glass to the first rough surface (no reference counterpart; defined in
+ * DESIGN.md section 5.8 and stated once in csrc/pt_chain.h).  A surface is followed when its resolved roughness is at most maxRoughness and it is a
+ * mirror (metallic >= minMetallic) or glass ((1 - metallic) * transmission >= minTransmission); a threshold above 1 turns that class off.  The
+ * resolved roughness of a material is never below 0.001. */
+#define PT_GUIDE_CHAIN_MAX_LINKS 8
+typedef struct pt_GuideChain {
+  uint32_t maxLinks;        /* 0 .. PT_GUIDE_CHAIN_MAX_LINKS: segments followed beyond the camera ray */
+  float    maxRoughness;    /* a surface is followed only when its resolved roughness <= this; >= 0, finite */
+  float    minMetallic;     /* mirror class:  metallic >= this; >= 0, finite */
+  float    minTransmission; /* glass class:   (1 - metallic) * transmission >= this; >= 0, finite */
+  uint32_t flags;           /* none defined; any bit is PT_ERR_INVALID */
+} pt_GuideChain;
+
 /* pt_svgf_variance / pt_svgf_history / pt_tonemap_svgf: the variance-guided filter of the history (no reference counterpart; defined in DESIGN.md
  * section 5.4 and stated once in csrc/pt_svgf.h).  The luminance edge stop is measured in standard deviations of the per-pixel variance estimate
  * that the moments in the history (pt_temporal_track_moments) give; guide terms are those of pt_DenoiseParams. */
@@ -378,6 +391,7 @@ static_assert(sizeof(pt_DenoiseParams) == 24, "DenoiseParams");
 static_assert(sizeof(pt_TemporalParams) == 80, "TemporalParams");
 static_assert(sizeof(pt_SvgfParams) == 32, "SvgfParams");
 static_assert(sizeof(pt_FastParams) == 16, "FastParams");
+static_assert(sizeof(pt_GuideChain) == 20, "GuideChain");
 #endif
 
 #endif /* PT_TYPES_H */

@@ -22,6 +22,7 @@ PT_PATHS_MAX_SAMPLES = 65536  # largest RtxState.maxSamples of pt_trace_paths
 PT_DENOISE_GUIDES = 3  # guide planes of the denoiser (include/pt_types.h)
 PT_DENOISE_DEMODULATE = 1  # pt_DenoiseParams.flags
 PT_GUIDES_BASECOLOR, PT_GUIDES_NORMAL, PT_GUIDES_DEPTH = 1, 2, 4  # pt_render_guides plane mask (include/pt_api.h): planes 0, 1, 2
+PT_GUIDE_CHAIN_MAX_LINKS = 8  # pt_GuideChain::maxLinks (include/pt_types.h)
 PT_INSTANCE_NONE = 0xFFFFFFFF  # instance plane (pt_render_instance_plane): the pixel's first camera ray hits nothing
 PT_DISPLAY_RING = 8  # images pt_tonemap_begin may have pending (include/pt_api.h)
 PT_FN = {"sin": 0, "cos": 1, "tan": 2, "asin": 3, "acos": 4, "atan2": 5, "exp": 6, "log": 7, "pow": 8}
@@ -74,6 +75,8 @@ API = [
     ("pt_svgf_variance", C.c_int, [_P, C.POINTER(hd.SvgfParams), _P]),
     ("pt_svgf_history", C.c_int, [_P, C.POINTER(hd.SvgfParams), _P, _P]),
     ("pt_tonemap_svgf", C.c_int, [_P, C.POINTER(hd.SvgfParams), C.POINTER(hd.Tonemapper), _P]),
+    ("pt_render_guides_chain", C.c_int, [_P, C.POINTER(hd.GuideChain), C.c_uint32, C.c_float]),
+    ("pt_read_guide_chain", C.c_int, [_P, _P]),
     ("pt_render_instance_plane", C.c_int, [_P, C.c_uint32, C.c_float]),
     ("pt_set_instance_plane", C.c_int, [_P, _P]),
     ("pt_read_instance_plane", C.c_int, [_P, _P]),
@@ -124,6 +127,7 @@ DEBUG_API = [
     ("pt_debug_trace_probe", C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_int, _P, C.c_int]),  # csrc/pt_probe.h trace_probe, every load inside the row: (ctx, kind, n, in, in_stride, out, out_stride)
     ("pt_debug_denoise_lds", C.c_int, [_P, C.c_int]),  # csrc/pt_denoise.hip: (ctx, largest step staged in LDS; negative: the default) -> the value in force
     ("pt_debug_denoise_time", C.c_int, [_P, C.POINTER(hd.DenoiseParams), C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_denoise.hip: (ctx, params, reps, ms per run out): the filter alone, device events
+    ("pt_debug_guides_chain_time", C.c_int, [_P, C.POINTER(hd.GuideChain), C.c_uint32, C.c_float, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_chain.hip: (ctx, chain, planes, miss_depth, reps, ms per run out): the chained guide pass alone, device events
     ("pt_debug_guides_time", C.c_int, [_P, C.c_uint32, C.c_float, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_guides.hip: (ctx, planes, miss_depth, reps, ms per run out): the guide pass alone, device events
     ("pt_debug_temporal_time", C.c_int, [_P, C.POINTER(hd.TemporalParams), C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_temporal.hip: (ctx, params, reps, ms per run out): the temporal kernel alone, device events
     ("pt_debug_motion_time", C.c_int, [_P, C.POINTER(hd.TemporalParams), C.c_int, C.c_uint32, C.c_float, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_temporal.hip: (ctx, params, part (0 instance pass, 1 moving temporal kernel), guide planes, miss_depth, reps, ms per run out), device events

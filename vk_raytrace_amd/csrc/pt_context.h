@@ -131,6 +131,7 @@ struct pt_context {
   HistorySettings histSettings;  // ... and the settings the next temporal call runs under
   // motion of moving instances (pt_motion.hip): the instance plane (one word per pixel) and the motion table of the call in flight
   DevBuf   dInstPlane, dMotionTable;
+  DevBuf   dChainPlane;  // the link plane of the chained guide pass (pt_chain.hip): one word per pixel
   // variance-guided filter (pt_svgf.hip): the filter's two variance planes, allocated on first use
   DevBuf   dSvgfVar[2];
   int      svgfLdsMaxStep = -1;  // largest step whose iteration stages its tile in LDS (-1: the measured default; pt_debug_svgf_lds)

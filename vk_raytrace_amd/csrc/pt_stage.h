@@ -68,6 +68,7 @@ static inline void stages_release(pt_context* c)
     dev_free(b);
   dev_free(c->dInstPlane);
   dev_free(c->dMotionTable);
+  dev_free(c->dChainPlane);
   for(DevBuf& b : c->dSvgfVar)
     dev_free(b);
   c->hist.release();

@@ -136,6 +136,11 @@ class FastParams(C.Structure):
     _fields_ = [("maxFast", C.c_float), ("sigmaScale", C.c_float), ("radius", C.c_int32), ("flags", C.c_uint32)]
 
 
+class GuideChain(C.Structure):
+    """pt_GuideChain (pt_render_guides_chain): how many segments are followed beyond the camera ray, and what counts as a mirror or as clear glass"""
+    _fields_ = [("maxLinks", C.c_uint32), ("maxRoughness", C.c_float), ("minMetallic", C.c_float), ("minTransmission", C.c_float), ("flags", C.c_uint32)]
+
+
 class SvgfParams(C.Structure):
     """pt_SvgfParams (pt_svgf_variance, pt_svgf_history, pt_tonemap_svgf): the luminance stop is sigmaLum standard deviations of the estimated variance plus
     lumFloor; sigmaGuide[j] is read for installed planes only; a history shorter than minTemporal estimates its variance spatially"""
@@ -170,7 +175,7 @@ assert C.sizeof(RtxState) == 48 and C.sizeof(SceneCamera) == 140 and C.sizeof(Ve
 assert C.sizeof(GltfShadeMaterial) == 216 and C.sizeof(Light) == 64 and C.sizeof(EnvAccel) == 16
 assert C.sizeof(Tonemapper) == 48 and C.sizeof(SunAndSky) == 96 and C.sizeof(PrimMesh) == 20 and C.sizeof(Node) == 68
 assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32 and C.sizeof(DenoiseParams) == 24 and C.sizeof(TemporalParams) == 80
-assert C.sizeof(SvgfParams) == 32 and C.sizeof(FastParams) == 16 and C.sizeof(PathResult) == 32
+assert C.sizeof(SvgfParams) == 32 and C.sizeof(FastParams) == 16 and C.sizeof(PathResult) == 32 and C.sizeof(GuideChain) == 20
 
 vertex_dtype = np.dtype(VertexAttributes)
 ray_dtype = np.dtype(Ray)

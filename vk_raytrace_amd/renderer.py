@@ -302,6 +302,26 @@ class HipRenderer(Renderer):
         stays as it is.  The depth plane holds `miss_depth` where nothing is hit."""
         self._check(self._lib.pt_render_guides(self._ctx, int(planes), float(miss_depth)))
 
+    @staticmethod
+    def guide_chain(max_links=4, max_roughness=0.05, min_metallic=0.9, min_transmission=0.9):
+        """an hd.GuideChain: follow at most max_links segments through surfaces of resolved roughness <= max_roughness that are mirrors (metallic >=
+        min_metallic) or clear glass ((1 - metallic) * transmission >= min_transmission); a threshold above 1 turns that class off"""
+        return hd.GuideChain(maxLinks=max_links, maxRoughness=max_roughness, minMetallic=min_metallic, minTransmission=min_transmission, flags=0)
+
+    def capture_guides_chain(self, chain, planes=7, miss_depth=1.0e30):
+        """pt_render_guides_chain: capture_guides for the first surface behind mirrors and clear glass: plane 0 the product of
+        the base colours along the chain, plane 1 the end surface's normal, plane 2 the summed length.  Asynchronous; read_guides returns the planes,
+        read_guide_chain the link plane."""
+        self._check(self._lib.pt_render_guides_chain(self._ctx, C.byref(chain), int(planes), float(miss_depth)))
+
+    def read_guide_chain(self):
+        """pt_read_guide_chain: the link plane of the latest capture_guides_chain, (H, W) uint32: links | end << 8 (end: 0 a surface that is not
+        followed, 1 a miss, 2 the link limit, 3 a direction that cannot be followed)"""
+        w, h = self.size
+        out = np.empty((h, w), np.uint32)
+        self._check(self._lib.pt_read_guide_chain(self._ctx, out.ctypes.data))
+        return out
+
     def read_guides(self, planes=None):
         """pt_read_denoise_guides: the installed guide planes as a tuple of three (H, W, 4) float32 images.  planes: mask of the planes to read
         (None: all three); a plane outside it comes back as None, one inside it that is not installed is an error (PT_ERR_STATE)."""
