@@ -535,6 +535,22 @@ int pt_trace_rays(pt_context* ctx, int kind, uint32_t flags, uint64_t n, const p
  * path state, the frame slots nor any pt_Stats field: frames before and after it come out as if it had not happened. */
 int pt_trace_paths(pt_context* ctx, const pt_RtxState* state, uint32_t flags, uint64_t n, const pt_Ray* rays, pt_PathResult* results);
 
+/* Gather queries: the light that arrives at a caller's points (light-map texels, irradiance probes).  The reference has no baker; every sample is
+ * PathTrace of shaders/pathtrace.glsl along a direction drawn AT the point -- for PT_GATHER_HEMISPHERE by the BSDF's own cosine sampler
+ * (CosineSampleHemisphere of shaders/pbr_disney.glsl in the frame of shaders/common.glsl:80-92 about the point's normal, from the origin
+ * OffsetRay gives), for PT_GATHER_SPHERE uniformly over the sphere from the position itself.  Defined in DESIGN.md section 3.3.
+ * Per point: seed = point.seed; each of state->maxSamples samples draws two numbers for its direction, then runs pt_trace_paths' path on that ray
+ * with the stream that continues from the draws; the radiance is clamped per sample and reduced in sample order:
+ *   PT_GATHER_HEMISPHERE  results is pt_GatherResult[n]: irradiance = pi * sum / maxSamples (the pdf is cos / pi, so the cosine cancels)
+ *   PT_GATHER_SPHERE      results is pt_ProbeResult[n]:  sh[k] = 4 pi * sum(radiance * Y_k(direction)) / maxSamples, nine real basis functions
+ * hitFraction: the samples whose first ray hit geometry / maxSamples.  An invalid point (a non-finite position component; HEMISPHERE also a
+ * non-finite or zero normal, or one whose unit vector is not finite and non-zero in fp32: a squared length that under- or overflows) is not walked: numerics 0, seed unchanged, status PT_RAY_INVALID.
+ * state, flags (PT_RAYS_DEVICE: 16-byte aligned device arrays, in place; else host arrays staged through the query buffers: PT_QUERY_CHUNK points a
+ * piece for HEMISPHERE, PT_QUERY_CHUNK / 4 for SPHERE), what the call needs, its refusals and its synchronisation are pt_trace_paths'.  A kind
+ * other than the two: PT_ERR_INVALID.  n == 0: PT_OK.  A gather touches neither the accumulation image, the path state, the frame slots nor any
+ * pt_Stats field. */
+int pt_gather(pt_context* ctx, const pt_RtxState* state, uint32_t kind, uint32_t flags, uint64_t n, const pt_GatherPoint* points, void* results);
+
 /* Measures, on this device, the two ceilings the measurement contract prices kernels against (no reference counterpart): VALU issue
  * (independent wave64 v_fma_f32 at 8 waves per SIMD on every CU, wave-instructions per second) and HBM streaming (float4 copy and
  * read-only over 1 GiB buffers, bytes per second).  Synchronous, a few tens of milliseconds. */

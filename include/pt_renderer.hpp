@@ -110,6 +110,11 @@ public:
   // image): pt_trace_paths on host arrays, and on 16-byte aligned device memory of the context's GPU
   bool tracePaths(const pt_RtxState& state, uint64_t n, const pt_Ray* rays, pt_PathResult* results) { return check(pt_trace_paths(m_ctx, &state, 0u, n, rays, results)); }
   bool tracePathsDevice(const pt_RtxState& state, uint64_t n, const pt_Ray* dRays, pt_PathResult* dResults) { return check(pt_trace_paths(m_ctx, &state, PT_RAYS_DEVICE, n, dRays, dResults)); }
+  // the light arriving at the caller's points (no counterpart in the reference, which has no baker): pt_gather -- irradiance from cosine-distributed
+  // paths about each point's normal, spherical-harmonic probes from uniformly distributed ones -- on host arrays, and on 16-byte aligned device memory
+  bool gatherIrradiance(const pt_RtxState& state, uint64_t n, const pt_GatherPoint* points, pt_GatherResult* results) { return check(pt_gather(m_ctx, &state, PT_GATHER_HEMISPHERE, 0u, n, points, results)); }
+  bool gatherProbes(const pt_RtxState& state, uint64_t n, const pt_GatherPoint* points, pt_ProbeResult* results) { return check(pt_gather(m_ctx, &state, PT_GATHER_SPHERE, 0u, n, points, results)); }
+  bool gatherDevice(const pt_RtxState& state, uint32_t kind, uint64_t n, const pt_GatherPoint* dPoints, void* dResults) { return check(pt_gather(m_ctx, &state, kind, PT_RAYS_DEVICE, n, dPoints, dResults)); }
   void readAccum(float* rgba32f) { check(pt_read_accum(m_ctx, rgba32f)); }
   void writeAccum(const float* rgba32f) { check(pt_write_accum(m_ctx, rgba32f)); }  // checkpoint restore
   void useAnyHit(bool enable) { check(pt_use_any_hit(m_ctx, enable ? 1 : 0)); }  // RtxPipeline::useAnyHit

@@ -267,6 +267,32 @@ typedef struct pt_PathResult {
 } pt_PathResult;
 #define PT_PATHS_MAX_SAMPLES 65536 /* largest RtxState.maxSamples of pt_trace_paths */
 
+/* pt_gather: one point in, one record out -- the integral of the path loop's radiance over the directions that leave the point.  No reference
+ * counterpart (the reference has no baker); each sample is PathTrace of shaders/pathtrace.glsl along a direction drawn at the point.  Defined in
+ * DESIGN.md section 3.3 ("Gather queries") and stated at pt_gather. */
+typedef struct pt_GatherPoint {
+  float    position[3];
+  uint32_t seed;      /* RNG state the point's samples start from */
+  float    normal[3]; /* PT_GATHER_HEMISPHERE: any finite non-zero length fp32 can normalise (about 1e-19 .. 1.8e19: the squared length must neither
+                       * underflow nor overflow); PT_GATHER_SPHERE: ignored, not even read for validity */
+  uint32_t _pad;      /* ignored */
+} pt_GatherPoint;
+typedef struct pt_GatherResult { /* PT_GATHER_HEMISPHERE */
+  float    irradiance[3]; /* pi x the mean over the cosine-distributed samples of the firefly-clamped path radiance */
+  float    hitFraction;   /* samples whose first ray hit geometry / maxSamples */
+  uint32_t seed;          /* RNG state after the last sample */
+  uint32_t status;        /* 0 or PT_RAY_INVALID: the point was not walked */
+  uint32_t closestRays;   /* closest-hit rays traced over all samples */
+  uint32_t _pad;          /* 0 */
+} pt_GatherResult;
+typedef struct pt_ProbeResult { /* PT_GATHER_SPHERE */
+  float    sh[9][3]; /* real spherical harmonics, bands 0 .. 2 in the order of DESIGN.md section 3.3, RGB per coefficient */
+  float    hitFraction;
+  uint32_t seed, status, closestRays, _pad; /* as in pt_GatherResult */
+} pt_ProbeResult;
+#define PT_GATHER_HEMISPHERE 0u /* pt_gather kind: cosine-distributed directions about the normal -> pt_GatherResult */
+#define PT_GATHER_SPHERE 1u     /* uniform directions -> pt_ProbeResult */
+
 /* pt_denoise / pt_tonemap_denoised: the edge-avoiding a-trous filter between the accumulation image and the display pass (no reference counterpart;
  * defined in DESIGN.md "Denoiser" and stated once in csrc/pt_denoise.h).  Guide planes are row-major RGBA32F images of the accumulation size whose
  * .xyz steer the weights; by convention plane 0 is the albedo (the only one PT_DENOISE_DEMODULATE reads), 1 the normal, 2 the depth in .x. */
@@ -387,6 +413,8 @@ static_assert(sizeof(pt_PrimMesh) == 20, "PrimMesh");
 static_assert(sizeof(pt_Node) == 68, "Node");
 static_assert(sizeof(pt_Ray) == 32 && sizeof(pt_RayHit) == 32, "Ray / RayHit");
 static_assert(sizeof(pt_PathResult) == sizeof(pt_RayHit), "PathResult: staged through the buffers of pt_trace_rays");
+static_assert(sizeof(pt_GatherPoint) == sizeof(pt_Ray) && sizeof(pt_GatherResult) == sizeof(pt_RayHit) && sizeof(pt_ProbeResult) == 4 * sizeof(pt_RayHit),
+              "GatherPoint / GatherResult / ProbeResult: staged through the buffers of pt_trace_rays");
 static_assert(sizeof(pt_DenoiseParams) == 24, "DenoiseParams");
 static_assert(sizeof(pt_TemporalParams) == 80, "TemporalParams");
 static_assert(sizeof(pt_SvgfParams) == 32, "SvgfParams");

@@ -19,6 +19,7 @@ PT_RAYS_DEVICE = 1  # pt_trace_rays flag: rays / hits are device pointers
 PT_RAYS_MAX_HITS = 16
 PT_QUERY_CHUNK = 1 << 20  # records per staging buffer of the host-pointer path
 PT_PATHS_MAX_SAMPLES = 65536  # largest RtxState.maxSamples of pt_trace_paths
+PT_GATHER_HEMISPHERE, PT_GATHER_SPHERE = 0, 1  # pt_gather kind
 PT_DENOISE_GUIDES = 3  # guide planes of the denoiser (include/pt_types.h)
 PT_DENOISE_DEMODULATE = 1  # pt_DenoiseParams.flags
 PT_GUIDES_BASECOLOR, PT_GUIDES_NORMAL, PT_GUIDES_DEPTH = 1, 2, 4  # pt_render_guides plane mask (include/pt_api.h): planes 0, 1, 2
@@ -101,6 +102,7 @@ API = [
     ("pt_pick", C.c_int, [_P, C.c_float, C.c_float, _P, _P, C.POINTER(hd.PickResult)]),
     ("pt_trace_rays", C.c_int, [_P, C.c_int, C.c_uint32, C.c_uint64, _P, _P, C.c_uint32]),
     ("pt_trace_paths", C.c_int, [_P, C.POINTER(hd.RtxState), C.c_uint32, C.c_uint64, _P, _P]),
+    ("pt_gather", C.c_int, [_P, C.POINTER(hd.RtxState), C.c_uint32, C.c_uint32, C.c_uint64, _P, _P]),
     ("pt_fpmath_eval", C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P]),
     ("pt_measure_peaks", C.c_int, [_P, C.POINTER(hd.Peaks)]),
     ("pt_set_profiling", C.c_int, [_P, C.c_int]),
@@ -137,6 +139,8 @@ DEBUG_API = [
     ("pt_debug_svgf_time", C.c_int, [_P, C.POINTER(hd.SvgfParams), C.c_int, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_svgf.hip: (ctx, params, part (-2 whole, -1 variance, i: iteration i), reps, ms per run out), device events
     ("pt_debug_paths_waves", C.c_int, [_P, C.c_int]),  # csrc/pt_paths.hip: (ctx, wavefronts of pt_trace_paths' launches; 0 or negative: the default)
     ("pt_debug_paths_time", C.c_int, [_P, C.POINTER(hd.RtxState), C.c_uint64, _P, _P, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_paths.hip: (ctx, state, n, device rays, device results, reps, ms per run out): the launch alone, device events
+    ("pt_debug_gather_waves", C.c_int, [_P, C.c_int]),  # csrc/pt_gather.hip: (ctx, wavefronts of pt_gather's launches; 0 or negative: the default)
+    ("pt_debug_gather_time", C.c_int, [_P, C.POINTER(hd.RtxState), C.c_uint32, C.c_uint64, _P, _P, C.c_int, C.POINTER(C.c_float)]),  # csrc/pt_gather.hip: (ctx, state, kind, n, device points, device results, reps, ms per run out): the launch alone, device events
     ("pt_debug_bounce_counts", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[max_bounces][16], max_bounces) -> staged bounces of the newest finished launch sequence
     ("pt_debug_accel_info", C.c_int, [_P, _P, C.c_int]),  # csrc/pt_debug.hip: (ctx, out[words], words) -> words of the info record (csrc/pt_accel_dump.h)
     ("pt_debug_accel_read", C.c_longlong, [_P, C.c_int, _P, C.c_size_t]),  # csrc/pt_debug.hip: (ctx, array id, dst, bytes) -> bytes the array holds; 0: no such array

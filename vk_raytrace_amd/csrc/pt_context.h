@@ -123,6 +123,8 @@ struct pt_context {
   DevBuf   dQueryRays, dQueryHits;  // pt_trace_rays with host arrays: staging buffers of PT_QUERY_CHUNK records each, allocated on first use
   DevBuf   dPathsChunk;             // pt_trace_paths (pt_paths.hip): the word its wavefronts reserve rays from, cleared on the stream before each launch
   int      pathsWaves = 0;          // wavefronts of its launches (0: the default; pt_debug_paths_waves)
+  DevBuf   dPointsChunk;            // pt_gather (pt_gather.hip): the word its wavefronts reserve points from, cleared on the stream before each launch
+  int      pointsWaves = 0;         // wavefronts of its launches (0: the default; pt_debug_gather_waves)
   DevBuf   dRowMajor, dRgba8, dMean, dMips, dGather, dFullTiles, dFullSlotTile, dTileLocalIndex;
   // denoiser (pt_denoise.hip): the two ping-pong images, allocated on first use, and the caller's guide planes; pt_resize and pt_destroy free them
   DevBuf   dDenoise[2], dGuide[PT_DENOISE_GUIDES];
@@ -186,6 +188,9 @@ int        untile_to_rowmajor(pt_context* c);  // the row-major accumulation ima
 int        display_chain(pt_context* c, int dispW, int dispH, bool chain, hipEvent_t readDone, MipView& mv);  // the display pass's offscreen image and its mip chain, enqueued
 int        display_levels(pt_context* c, const float4* image, int dispW, int dispH, bool chain, MipView& mv);  // ... the part after level 0 (`image`, accumulation size) is chosen
 int        display_finish(pt_context* c, const pt_Tonemapper* tm, MipView& mv, int dispW, int dispH, uint8_t* out);  // ... the tonemap kernel and the copy to `out` (host), enqueued
+// everything a query through the path loop checks before it launches (pt_paths.hip; pt_trace_paths and pt_gather, DESIGN.md sections 3.2 / 3.3),
+// each refusal with its own text under the caller's name `who`; then the kernel's parameters filled.  Nothing is allocated or launched.
+int        path_query_checks(pt_context* c, const char* who, const pt_RtxState* st, uint32_t flags, uint64_t n, const void* in, const void* results, FrameParams& fp);
 void       refresh_scene_ptrs(pt_context* c);
 int        upload_instances(pt_context* c);
 std::vector<InstanceRec> effective_instances(const pt_context* c);  // the instance records as the kernels see them

@@ -76,8 +76,9 @@ static hipError_t launch_paths(pt_context* c, const FrameParams& fp, uint32_t n,
   return hipGetLastError();
 }
 
-// Everything pt_trace_paths checks, each refusal with its own text; then the chunk counter allocated and the kernel's parameters filled.  Nothing is launched.
-static int prepare_paths(pt_context* c, const char* who, const pt_RtxState* st, uint32_t flags, uint64_t n, const void* rays, const void* results, FrameParams& fp)
+// Everything a query through the path loop checks (pt_context.h: pt_gather calls this too), each refusal with its own text; then the kernel's
+// parameters filled.  Nothing is allocated or launched.
+int path_query_checks(pt_context* c, const char* who, const pt_RtxState* st, uint32_t flags, uint64_t n, const void* rays, const void* results, FrameParams& fp)
 {
   if(!st)
     return c->fail(PT_ERR_INVALID, "%s: null state", who);
@@ -109,6 +110,13 @@ static int prepare_paths(pt_context* c, const char* who, const pt_RtxState* st, 
   fp.st      = *st;
   fp.batch   = 1;
   fp.variant = c->variant;
+  return PT_OK;
+}
+
+// path_query_checks, then the chunk counter allocated.  Nothing is launched.
+static int prepare_paths(pt_context* c, const char* who, const pt_RtxState* st, uint32_t flags, uint64_t n, const void* rays, const void* results, FrameParams& fp)
+{
+  STAGE_TRY(path_query_checks(c, who, st, flags, n, rays, results, fp));
   if(n == 0)
     return PT_OK;
   HIP_TRY(c, hipSetDevice(c->device));

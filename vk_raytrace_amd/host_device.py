@@ -121,6 +121,22 @@ class PathResult(C.Structure):
     _fields_ = [("radiance", C.c_float * 3), ("firstT", C.c_float), ("seed", C.c_uint32), ("status", C.c_uint32), ("closestRays", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class GatherPoint(C.Structure):
+    """pt_GatherPoint (pt_gather): where the samples leave from, the RNG state they start from and, for PT_GATHER_HEMISPHERE, the normal they leave about"""
+    _fields_ = [("position", C.c_float * 3), ("seed", C.c_uint32), ("normal", C.c_float * 3), ("_pad", C.c_uint32)]
+
+
+class GatherResult(C.Structure):
+    """pt_GatherResult (pt_gather, PT_GATHER_HEMISPHERE): irradiance, the fraction of samples whose first ray hit geometry, the RNG state after the
+    last sample, 0 / PT_RAY_INVALID, the closest-hit rays traced over all samples"""
+    _fields_ = [("irradiance", C.c_float * 3), ("hitFraction", C.c_float), ("seed", C.c_uint32), ("status", C.c_uint32), ("closestRays", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class ProbeResult(C.Structure):
+    """pt_ProbeResult (pt_gather, PT_GATHER_SPHERE): nine real spherical-harmonic coefficients (bands 0 .. 2) of the radiance, RGB each; then as GatherResult"""
+    _fields_ = [("sh", (C.c_float * 3) * 9), ("hitFraction", C.c_float), ("seed", C.c_uint32), ("status", C.c_uint32), ("closestRays", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class DenoiseParams(C.Structure):
     """pt_DenoiseParams (pt_denoise, pt_tonemap_denoised): sigmaColor 0 switches the colour term off; sigmaGuide[j] is read for installed planes only"""
     _fields_ = [("iterations", C.c_int32), ("sigmaColor", C.c_float), ("sigmaGuide", C.c_float * 3), ("flags", C.c_uint32)]
@@ -177,10 +193,15 @@ assert C.sizeof(Tonemapper) == 48 and C.sizeof(SunAndSky) == 96 and C.sizeof(Pri
 assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32 and C.sizeof(DenoiseParams) == 24 and C.sizeof(TemporalParams) == 80
 assert C.sizeof(SvgfParams) == 32 and C.sizeof(FastParams) == 16 and C.sizeof(PathResult) == 32 and C.sizeof(GuideChain) == 20
 
+assert C.sizeof(GatherPoint) == 32 and C.sizeof(GatherResult) == 32 and C.sizeof(ProbeResult) == 128
+
 vertex_dtype = np.dtype(VertexAttributes)
 ray_dtype = np.dtype(Ray)
 rayhit_dtype = np.dtype(RayHit)
 pathresult_dtype = np.dtype(PathResult)
+gatherpoint_dtype = np.dtype(GatherPoint)
+gatherresult_dtype = np.dtype(GatherResult)
+proberesult_dtype = np.dtype(ProbeResult)
 material_dtype = np.dtype(GltfShadeMaterial)
 light_dtype = np.dtype(Light)
 primmesh_dtype = np.dtype(PrimMesh)

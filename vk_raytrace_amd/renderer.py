@@ -237,6 +237,44 @@ class HipRenderer(Renderer):
         are in place when the call returns."""
         self._check(self._lib.pt_trace_paths(self._ctx, C.byref(state), capi.PT_RAYS_DEVICE, int(n), C.c_void_p(int(rays_ptr)), C.c_void_p(int(results_ptr))))
 
+    def gather_irradiance(self, state: hd.RtxState, positions, normals, seeds=None):
+        """pt_gather, PT_GATHER_HEMISPHERE, on host arrays: the irradiance at each point (positions, normals: (n, 3), normals of any non-zero length;
+        seeds (n,) uint32, default 0: the RNG state each point's samples start from) from state.maxSamples cosine-distributed paths under `state`
+        (the fields pt_trace_paths reads).  Returns a structured array (hd.gatherresult_dtype) of shape (n,)."""
+        return self.gather_records(state, capi.PT_GATHER_HEMISPHERE, self._gather_points("gather_irradiance", positions, normals, seeds))
+
+    def gather_probes(self, state: hd.RtxState, positions, seeds=None):
+        """pt_gather, PT_GATHER_SPHERE, on host arrays: nine spherical-harmonic coefficients (bands 0 .. 2, RGB) of the radiance arriving at each
+        position from state.maxSamples uniformly distributed paths.  Returns a structured array (hd.proberesult_dtype) of shape (n,)."""
+        return self.gather_records(state, capi.PT_GATHER_SPHERE, self._gather_points("gather_probes", positions, None, seeds))
+
+    @staticmethod
+    def _gather_points(who, positions, normals, seeds):
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        pts = np.zeros(len(p), hd.gatherpoint_dtype)
+        pts["position"] = p
+        if normals is not None:
+            nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+            if len(nrm) != len(p):
+                raise ValueError(f"{who}: positions and normals differ in length")
+            pts["normal"] = nrm
+        pts["seed"] = 0 if seeds is None else np.asarray(seeds, np.uint32)
+        return pts
+
+    def gather_records(self, state: hd.RtxState, kind, points):
+        """pt_gather on an array of hd.gatherpoint_dtype records (what gather_irradiance / gather_probes assemble): hd.gatherresult_dtype records for
+        capi.PT_GATHER_HEMISPHERE, hd.proberesult_dtype records for capi.PT_GATHER_SPHERE"""
+        points = np.ascontiguousarray(points, hd.gatherpoint_dtype)
+        out = np.zeros(len(points), hd.proberesult_dtype if int(kind) == capi.PT_GATHER_SPHERE else hd.gatherresult_dtype)
+        self._check(self._lib.pt_gather(self._ctx, C.byref(state), int(kind), 0, len(points), points.ctypes.data, out.ctypes.data))
+        return out
+
+    def gather_device(self, state: hd.RtxState, kind, points_ptr, results_ptr, n):
+        """pt_gather with PT_RAYS_DEVICE: points_ptr / results_ptr are plain integers, the addresses of n pt_GatherPoint records and n records of the
+        kind's result type in the memory of the context's GPU (16-byte aligned), e.g. a torch tensor's data_ptr().  The caller owns the memory and
+        keeps it alive; the results are in place when the call returns."""
+        self._check(self._lib.pt_gather(self._ctx, C.byref(state), int(kind), capi.PT_RAYS_DEVICE, int(n), C.c_void_p(int(points_ptr)), C.c_void_p(int(results_ptr))))
+
     def tonemap(self, tm: hd.Tonemapper, display_size=None):
         """RenderOutput::genMipmap + run.  display_size (W, H): the viewport while de-scaling (Tonemapper.zoom = 1 / level)."""
         w, h = display_size or self.size
