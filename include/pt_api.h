@@ -86,6 +86,32 @@ int pt_set_accel_mode(pt_context* ctx, int mode);
  * PT_ACCEL_FLAT rebuilds the whole structure.  Frames already handed to pt_render_frame keep the old transforms. */
 int pt_update_instances(pt_context* ctx, const pt_Node* nodes, uint32_t num_nodes);
 
+/* ---- deforming meshes (no reference counterpart: the reference builds its acceleration structures once, on load) --------------------------------
+ * pt_update_vertices replaces vertices[first_vertex .. first_vertex + num_vertices) of the scene's vertex buffer -- the whole record: position,
+ * packed normal and tangent, texcoords, colour -- for skinned characters, cloth, morph targets, an edit, a simulation mesh.  The data is copied before
+ * the call returns.  It waits for the frames in flight first: frames already handed to pt_render_frame keep the old geometry.  Indices, prim-mesh
+ * ranges, nodes and materials stay as they are; the call may be repeated before a refit.  Like pt_set_scene it refuses nothing of a vertex itself:
+ * non-finite positions are accepted (and, as there, left out of the per-mesh coordinate bound).
+ * Errors: PT_ERR_STATE before pt_set_scene; PT_ERR_INVALID, with nothing changed, for a null pointer with num_vertices > 0 and for a range that
+ * leaves the vertex buffer; num_vertices == 0 is PT_OK.
+ * With a structure built the call marks it STALE: until pt_refit_accel or pt_build_accel every call that walks the structure (pt_render_frame,
+ * pt_trace_rays, pt_trace_paths, pt_gather, pt_pick, pt_render_guides*, pt_render_instance_plane) returns PT_ERR_STATE with a message that names
+ * the pending refit.  pt_use_any_hit, pt_set_accel_mode and pt_update_instances treat a stale structure as built and rebuild it in full, which
+ * clears the mark.  Without a structure the call only updates the buffer and pt_build_accel builds from the new vertices.
+ *
+ * pt_refit_accel brings the structure up to date WITHOUT changing its topology: every child reference of every node, every leaf slot's (instance,
+ * primitive), every node count and range -- and so the traversal-stack depth -- stay; the leaf records, any-hit texcoords, leaf boxes, inner boxes,
+ * child-order tables, compact nodes and shading lines are made again from the vertices, in two-level mode also the per-mesh coordinate bounds, the
+ * merged structure's box and the instance hierarchy (as after pt_update_instances).  Rendered values equal those of a structure built from the same
+ * vertices bit for bit (trace contract: results do not depend on the topology); what degrades with the deformation is the speed, see pt_RefitInfo.
+ * Synchronous like pt_build_accel; afterwards the context is in the state pt_build_accel leaves.  A structure that is not stale is refitted as
+ * well and comes out bit-identical.  PT_ERR_STATE when there is no structure to refit.  out_info may be NULL.
+ * After a vertex update the history of the temporal stage belongs to other surfaces: drop it (pt_temporal_reset).
+ * (Not provided: topology changes, index or vertex-count changes, an automatic rebuild when the cost ratio grows, motion vectors for deformed
+ * surfaces, the refit path for pt_update_instances in flat mode, which keeps rebuilding.) */
+int pt_update_vertices(pt_context* ctx, uint32_t first_vertex, uint32_t num_vertices, const pt_VertexAttributes* vertices);
+int pt_refit_accel(pt_context* ctx, pt_RefitInfo* out_info);
+
 /* replaces Scene::updateCamera's UBO upload [src/scene.cpp:629-668] */
 int pt_set_camera(pt_context* ctx, const pt_SceneCamera* cam);
 
@@ -359,7 +385,8 @@ int pt_read_guide_chain(pt_context* ctx, uint32_t* links_out /* W*H, row-major *
  * pt_temporal_accumulate refuses, and PT_ERR_STATE without an instance plane, without a scene, and when the history was made with another number of
  * instances than the scene has (the scene was replaced: pt_temporal_reset).  On every refusal nothing is launched and the history is untouched.
  * pt_temporal_demodulate applies as it does to pt_temporal_accumulate.
- * (Not provided: deforming meshes, moving lights or materials, motion seen through reflection or refraction.) */
+ * (Not provided: motion of deforming meshes -- after pt_update_vertices the history should be dropped with pt_temporal_reset --, moving lights or
+ * materials, motion seen through reflection or refraction.) */
 int pt_temporal_accumulate_moving(pt_context* ctx, const pt_TemporalParams* params, float* rgba32f_out);
 
 /* ---- demodulated history (no reference counterpart) ------------------------------------------------------------------------------------------------

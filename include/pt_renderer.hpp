@@ -120,6 +120,15 @@ public:
   void useAnyHit(bool enable) { check(pt_use_any_hit(m_ctx, enable ? 1 : 0)); }  // RtxPipeline::useAnyHit
   void setAccelMode(int mode) { check(pt_set_accel_mode(m_ctx, mode)); }  // PT_ACCEL_TWO_LEVEL: AccelStructure's BLAS per prim-mesh + TLAS (src/accelstruct.cpp:110-162)
   void updateInstances(const pt_Node* nodes, uint32_t n) { check(pt_update_instances(m_ctx, nodes, n)); }  // new node.worldMatrix values: TLAS refit
+  // deforming meshes (no reference counterpart): new vertex records for a range of the vertex buffer, then a refit of the built
+  // hierarchies that keeps their topology (costAfter / costBefore of the info says when buildAccel is due); nothing walks the structure in between
+  void updateVertices(uint32_t first, uint32_t n, const pt_VertexAttributes* vertices) { check(pt_update_vertices(m_ctx, first, n, vertices)); }
+  pt_RefitInfo refitAccel()
+  {
+    pt_RefitInfo info{};
+    check(pt_refit_accel(m_ctx, &info));
+    return info;
+  }
   void tonemap(const pt_Tonemapper& tm, uint8_t* rgba8) { check(pt_tonemap(m_ctx, &tm, rgba8)); }
   // while SampleExample de-scales (m_descaling, src/sample_example.cpp:410-413): viewport of dispW x dispH from the reduced-size render
   void tonemapZoom(const pt_Tonemapper& tm, int dispW, int dispH, uint8_t* rgba8) { check(pt_tonemap_zoom(m_ctx, &tm, dispW, dispH, rgba8)); }

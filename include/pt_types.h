@@ -390,6 +390,19 @@ typedef struct pt_Stats {
   uint64_t launchesTraceFused;
 } pt_Stats;
 
+/* pt_refit_accel: what one refit did (no reference counterpart).  The tree cost is the sum over the used child boxes of every kept hierarchy -- the
+ * flat one, or the merged world-space one and every BLAS -- of dx dy + dy dz + dz dx, taken in double from the fp32 planes.  costBefore belongs to
+ * the structure as pt_build_accel left it (measured by the first refit after a build, before it changes a box, and kept); costAfter to the
+ * structure this refit leaves.  costAfter / costBefore is what tells a caller when a rebuild is due.  (Two-level mode: when pt_update_instances moved a
+ * once-instantiated node, the merged structure alone was built again; costBefore then holds its cost as just built plus the BLASes' as pt_build_accel left them.) */
+typedef struct pt_RefitInfo {
+  double   ms;           /* the call, by the host clock */
+  double   costBefore;
+  double   costAfter;
+  uint32_t nodesWritten; /* 4-wide nodes whose boxes were made again */
+  uint32_t slotsWritten; /* leaf slots whose records were made again */
+} pt_RefitInfo;
+
 /* pt_measure_peaks: ceilings measured on the device */
 typedef struct pt_Peaks {
   double  valuWaveInstrPerSec; /* wave64 VALU instructions issued per second, whole chip */
@@ -410,6 +423,7 @@ static_assert(sizeof(pt_EnvAccel) == 16, "EnvAccel");
 static_assert(sizeof(pt_Tonemapper) == 48, "Tonemapper");
 static_assert(sizeof(pt_SunAndSky) == 96, "SunAndSky");
 static_assert(sizeof(pt_PrimMesh) == 20, "PrimMesh");
+static_assert(sizeof(pt_RefitInfo) == 32, "RefitInfo");
 static_assert(sizeof(pt_Node) == 68, "Node");
 static_assert(sizeof(pt_Ray) == 32 && sizeof(pt_RayHit) == 32, "Ray / RayHit");
 static_assert(sizeof(pt_PathResult) == sizeof(pt_RayHit), "PathResult: staged through the buffers of pt_trace_rays");

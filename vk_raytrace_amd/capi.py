@@ -43,6 +43,8 @@ API = [
     ("pt_build_accel", C.c_int, [_P]),
     ("pt_set_accel_mode", C.c_int, [_P, C.c_int]),
     ("pt_update_instances", C.c_int, [_P, _P, C.c_uint32]),
+    ("pt_update_vertices", C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    ("pt_refit_accel", C.c_int, [_P, C.POINTER(hd.RefitInfo)]),
     ("pt_set_camera", C.c_int, [_P, C.POINTER(hd.SceneCamera)]),
     ("pt_set_env", C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("pt_hdr_load", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),

@@ -329,7 +329,7 @@ int pt_destroy(pt_context* c)
   CTX_CHECK(c);
   (void)hipSetDevice(c->device);
   (void)sync_all(c);
-  DevBuf* all[] = {&c->dMatLines, &c->dVertices, &c->dIndices, &c->dInstances, &c->dMaterials, &c->dLights, &c->dTexRecs, &c->dTexels, &c->dBvh, &c->dWide, &c->dTris, &c->dAlphaRecs, &c->dCNodes, &c->dCTlas, &c->dInstBlock, &c->dShadeTris, &c->dAlphaMats, &c->dAlphaMaps, &c->dPick, &c->dQueryRays, &c->dQueryHits, &c->dPathsChunk, &c->dPointsChunk, &c->dEnv,
+  DevBuf* all[] = {&c->dMatLines, &c->dVertices, &c->dIndices, &c->dInstances, &c->dMaterials, &c->dLights, &c->dTexRecs, &c->dTexels, &c->dBvh, &c->dWide, &c->dTris, &c->dAlphaRecs, &c->dCNodes, &c->dRefit, &c->dCTlas, &c->dInstBlock, &c->dShadeTris, &c->dAlphaMats, &c->dAlphaMaps, &c->dPick, &c->dQueryRays, &c->dQueryHits, &c->dPathsChunk, &c->dPointsChunk, &c->dEnv,
                    &c->dTlas, &c->dTlasLeaves, &c->dInstTriBase, &c->dActive, &c->dInstNodeBase, &c->dInstPad, &c->dEnvAccel, &c->dFrame, &c->dSlotTile, &c->dCounters, &c->dRowMajor, &c->dRgba8,
                    &c->dMean, &c->dMips, &c->dGather, &c->dFullTiles, &c->dFullSlotTile, &c->dTileLocalIndex};
   for(DevBuf* b : all)
@@ -446,6 +446,21 @@ int pt_set_scene(pt_context* c, const pt_SceneDesc* d)
   c->numInstances = d->numNodes;
   c->numTris      = uint32_t(R.triTotal);
   c->qRatioDepths = 0;  // queue-size feedback of the previous scene
+  // what pt_update_vertices needs -- the vertex count, every prim-mesh's vertex range, the positions -- replaced only now that the uploads succeeded: it
+  // range-checks a device write against them
+  c->numVertices = d->numVertices;
+  c->hPrimMeshVerts.resize(2 * size_t(d->numPrimMeshes));
+  for(uint32_t p = 0; p < d->numPrimMeshes; ++p)
+  {
+    c->hPrimMeshVerts[2 * p]     = d->primMeshes[p].vertexOffset;
+    c->hPrimMeshVerts[2 * p + 1] = d->primMeshes[p].vertexCount;
+  }
+  c->hPositions.resize(3 * size_t(d->numVertices));
+  for(uint32_t v = 0; v < d->numVertices; ++v)
+    std::memcpy(&c->hPositions[3 * size_t(v)], d->vertices[v].position, 12);
+  c->primTouched.assign(d->numPrimMeshes, 0);
+  c->accelStale     = false;
+  c->haveRefitTable = false;
   c->haveScene    = true;
   c->haveAccel    = false;
   refresh_scene_ptrs(c);
@@ -751,7 +766,7 @@ int pt_render_frame(pt_context* c, const pt_RtxState* st)
   if(!st)
     return c->fail(PT_ERR_INVALID, "pt_render_frame: null state");
   if(!c->haveScene || !c->haveAccel)
-    return c->fail(PT_ERR_STATE, "pt_render_frame before pt_set_scene / pt_build_accel");
+    return c->fail(PT_ERR_STATE, "pt_render_frame %s", c->no_accel());
   if(!c->haveEnv && c->scene.sunsky.in_use != 1)
     return c->fail(PT_ERR_STATE, "pt_render_frame without an environment (pt_set_env) or sun & sky");
   if(c->width == 0)
@@ -999,7 +1014,7 @@ int pt_pick(pt_context* c, float pick_x, float pick_y, const float* view_inverse
   if(!view_inverse || !proj_inverse || !out)
     return c->fail(PT_ERR_INVALID, "pt_pick: null");
   if(!c->haveScene || !c->haveAccel)
-    return c->fail(PT_ERR_STATE, "pt_pick before pt_set_scene / pt_build_accel");
+    return c->fail(PT_ERR_STATE, "pt_pick %s", c->no_accel());
   HIP_TRY(c, hipSetDevice(c->device));
   int rc;
   if((rc = dev_alloc(c, c->dPick, sizeof(pt_PickResult))) != PT_OK)

@@ -1,6 +1,6 @@
 // The acceleration-structure side of the C ABI: pt_build_accel (flat structure, or BLAS per prim-mesh + merged world-space structure + TLAS),
-// the refit of pt_update_instances and the two calls that force a rebuild (pt_use_any_hit, pt_set_accel_mode).  Host sequencing only: the
-// builders themselves are pt_accel.hip / pt_sah.hip.  Mirrors AccelStructure (src/accelstruct.cpp) of the reference.
+// the refit of pt_update_instances, the two calls that force a rebuild (pt_use_any_hit, pt_set_accel_mode) and the deforming meshes
+// (pt_update_vertices, pt_refit_accel; kernels: pt_refit.hip).  Host sequencing only: the builders themselves are pt_accel.hip / pt_sah.hip.  Mirrors AccelStructure (src/accelstruct.cpp) of the reference.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -20,6 +20,32 @@ void bounds_from_root(pt_context* c, const BvhNode& root, bool two)
     const float mn = two ? std::min(lmin[k], rmin[k]) : lmin[k], mx = two ? std::max(lmax[k], rmax[k]) : lmax[k];
     c->scene.boundsMin[k]    = std::isfinite(mn) ? mn : 0.f;
     c->scene.boundsInvExt[k] = (std::isfinite(mx - mn) && mx > mn) ? 1.0f / (mx - mn) : 0.f;
+  }
+}
+
+// a structure that is rebuilt or whose topology changes takes the parent table of the refit with it.  keepBlasCost: only the merged structure is built
+// again -- the cost of the BLASes as built, if it was measured, still belongs to them
+void drop_refit_table(pt_context* c, bool keepBlasCost = false)
+{
+  c->haveRefitTable = false;
+  c->haveCostBlas   = c->haveCostBlas && keepBlasCost;
+  dev_free(c->dRefit);
+}
+
+// hPrimBound of the prim-meshes pt_update_vertices touched, by build_scene_records' rule: the maximum |coordinate| over the mesh's finite coordinates
+void refresh_prim_bounds(pt_context* c)
+{
+  for(size_t p = 0; p < c->primTouched.size(); ++p)
+  {
+    if(!c->primTouched[p])
+      continue;
+    c->primTouched[p] = 0;
+    float        b = 0.f;
+    const float* q = c->hPositions.data() + 3 * size_t(c->hPrimMeshVerts[2 * p]);
+    for(size_t k = 0; k < 3 * size_t(c->hPrimMeshVerts[2 * p + 1]); ++k)
+      if(std::isfinite(q[k]))
+        b = std::max(b, std::fabs(q[k]));
+    c->hPrimBound[p] = b;
   }
 }
 
@@ -156,6 +182,7 @@ int build_merged(pt_context* c)
     ~KeepStat() { c->numWideNodes = c->numWideNodes - std::min(c->numWideNodes, before) + c->mergedWide; }
   } keep{c, before};
   c->mergedWide = 0;
+  drop_refit_table(c, true);  // the merged structure gets a new topology
   if(c->hMerged.empty())
     return PT_OK;
   const std::vector<InstanceRec> inst = effective_instances(c);
@@ -240,6 +267,7 @@ int build_two_level(pt_context* c)
     return c->fail(PT_ERR_HIP, "pt_build_accel (two-level): %s", msg);
   if((rc = build_merged(c)) != PT_OK)
     return rc;
+  c->hBlas = blas;
   c->hBlasRanges.clear();
   for(const PtBlasDesc& d : blas)
   {
@@ -272,7 +300,10 @@ int pt_build_accel(pt_context* c)
     return c->fail(PT_ERR_STATE, "pt_build_accel before pt_set_scene");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_all(c));
-  c->haveAccel = false;
+  c->haveAccel  = false;
+  c->accelStale = false;
+  drop_refit_table(c);
+  refresh_prim_bounds(c);  // (pt_update_vertices without a structure, or with one that is rebuilt instead of refitted)
   // overflows of the previous structure say nothing about the new one (check_traversal)
   HIP_TRY(c, hipMemset((char*)c->dCounters.p + offsetof(Counters, stackOverflow), 0, sizeof(unsigned int)));
   clear_overflow(c);
@@ -284,6 +315,7 @@ int pt_build_accel(pt_context* c)
   c->mergedTris = c->mergedWide = 0;
   c->mergedOnly = false;
   c->hBlasRanges.clear();
+  c->hBlas.clear();
   c->nodeCapacity = 0;
   dev_free(c->dCTlas);
   c->numBvhNodes = c->numTris > 1 ? c->numTris - 1 : 1;
@@ -339,7 +371,7 @@ int pt_use_any_hit(pt_context* c, int enable)
   if(rc != PT_OK)
     return rc;
   refresh_scene_ptrs(c);
-  if(c->haveAccel)
+  if(c->haveAccel || c->accelStale)
   {  // the opaque / non-opaque classification is baked into the triangle records: rebuild, like useAnyHit re-creates the pipeline
     c->haveAccel = false;
     return pt_build_accel(c);
@@ -358,7 +390,7 @@ int pt_set_accel_mode(pt_context* c, int mode)
   if(mode == c->accelMode)
     return PT_OK;
   c->accelMode = mode;
-  if(c->haveAccel)
+  if(c->haveAccel || c->accelStale)
   {
     c->haveAccel = false;
     return pt_build_accel(c);
@@ -390,6 +422,8 @@ int pt_update_instances(pt_context* c, const pt_Node* nodes, uint32_t numNodes)
   if(rc != PT_OK)
     return rc;
   refresh_scene_ptrs(c);
+  if(c->accelStale)  // pt_update_vertices since the build: the bottom-level structures are stale too
+    return pt_build_accel(c);
   if(!c->haveAccel)
     return PT_OK;
   if(c->accelMode == PT_ACCEL_TWO_LEVEL)
@@ -415,6 +449,150 @@ int pt_update_instances(pt_context* c, const pt_Node* nodes, uint32_t numNodes)
   }
   c->haveAccel = false;  // flat structure: the world-space triangles are baked in
   return pt_build_accel(c);
+}
+
+int pt_update_vertices(pt_context* c, uint32_t first, uint32_t num, const pt_VertexAttributes* vertices)
+{
+  CTX_CHECK(c);
+  if(!c->haveScene)
+    return c->fail(PT_ERR_STATE, "pt_update_vertices before pt_set_scene");
+  if(num == 0)
+    return PT_OK;
+  if(!vertices)
+    return c->fail(PT_ERR_INVALID, "pt_update_vertices: null vertices");
+  if(first > c->numVertices || num > c->numVertices - first || sizeof(pt_VertexAttributes) * (size_t(first) + num) > c->dVertices.bytes)  // (the buffer's own size too)
+    return c->fail(PT_ERR_INVALID, "pt_update_vertices: vertices %u .. %llu, the scene has %u", first, (unsigned long long)first + num, c->numVertices);
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_all(c));  // frames already handed over keep the geometry they were given
+  HIP_TRY(c, hipMemcpy((char*)c->dVertices.p + sizeof(pt_VertexAttributes) * size_t(first), vertices, sizeof(pt_VertexAttributes) * size_t(num), hipMemcpyHostToDevice));
+  for(uint32_t v = 0; v < num; ++v)
+    std::memcpy(&c->hPositions[3 * (size_t(first) + v)], vertices[v].position, 12);
+  for(size_t p = 0; p < c->primTouched.size(); ++p)
+  {
+    const uint64_t lo = c->hPrimMeshVerts[2 * p], hi = lo + c->hPrimMeshVerts[2 * p + 1];
+    if(lo < uint64_t(first) + num && hi > first)
+      c->primTouched[p] = 1;
+  }
+  if(c->haveAccel)
+  {  // the structure no longer describes the vertices: nothing walks it until pt_refit_accel or pt_build_accel
+    c->haveAccel  = false;
+    c->accelStale = true;
+  }
+  return PT_OK;
+}
+
+int pt_refit_accel(pt_context* c, pt_RefitInfo* out)
+{
+  CTX_CHECK(c);
+  if(out)
+    *out = pt_RefitInfo{};
+  if(!c->haveScene || !(c->haveAccel || c->accelStale))
+    return c->fail(PT_ERR_STATE, "pt_refit_accel: no structure to refit (pt_build_accel first)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_all(c));
+  const auto t0 = std::chrono::steady_clock::now();
+  pt_RefitInfo info{};
+#if PT_BVH_WIDTH != 4
+  {  // the refit works on the 4-wide nodes: other widths rebuild
+    const int rc = pt_build_accel(c);
+    info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if(out)
+      *out = info;
+    return rc;
+  }
+#else
+  const bool two = c->accelMode == PT_ACCEL_TWO_LEVEL;
+  // the hierarchies that are kept: their node ranges and where their leaf slots' triangles come from
+  std::vector<uint32_t> ranges;
+  std::vector<RfSlots>  slots;
+  uint32_t              numNodes = c->numWideNodes, numSlots = c->numTris;
+  if(!two)
+  {
+    if(c->numTris)
+    {
+      ranges = {0u, c->numWideNodes};
+      slots.push_back(RfSlots{0u, c->numTris, RF_WORLD, 0u, 0u});
+    }
+  }
+  else
+  {
+    numNodes = c->nodeCapacity;
+    numSlots = c->mergedTris;
+    if(c->mergedTris)
+    {
+      ranges = {0u, c->mergedWide};
+      slots.push_back(RfSlots{0u, c->mergedTris, RF_WORLD, 0u, 0u});
+    }
+    for(const PtBlasDesc& d : c->hBlas)
+    {
+      ranges.push_back(d.nodeBase);
+      ranges.push_back(d.numWide);
+      slots.push_back(RfSlots{d.slotBase, d.triCount, RF_VERTEX, d.vertexOffset, d.firstIndex});
+      numSlots = std::max(numSlots, d.slotBase + d.triCount);
+    }
+  }
+  // from here on a failure leaves no structure: the boxes may be half written
+  c->haveAccel  = false;
+  c->accelStale = false;
+  int rc;
+  if(!slots.empty())
+  {
+    char                msg[256] = "";
+    const uint32_t      numRanges = uint32_t(ranges.size() / 2);
+    std::vector<float>  rootBox(6 * size_t(numRanges), 0.f);
+    if(!c->haveRefitTable)
+    {  // once per build: the parent table, and the cost of the tree as built
+      if((rc = dev_alloc(c, c->dRefit, pt_refit_table_bytes(numNodes, numSlots, numRanges, uint32_t(slots.size())))) != PT_OK)
+        return rc;
+      double measured[2] = {0, 0};
+      if(pt_refit_prepare(c->stream, c->dRefit.p, ranges.data(), numRanges, slots.data(), uint32_t(slots.size()), numNodes, numSlots, (const WideNode*)c->dWide.p, c->refit,
+                          two ? (c->mergedTris ? 1u : 0u) : numRanges, measured, msg, sizeof(msg)) != 0)
+        return c->fail(PT_ERR_HIP, "pt_refit_accel: %s", msg);
+      c->costBuilt[0] = measured[0];
+      if(!c->haveCostBlas)  // (kept across a rebuild of the merged structure alone: earlier refits may have changed the BLASes' boxes)
+        c->costBuilt[1] = measured[1];
+      c->haveCostBlas = true;
+      c->haveRefitTable = true;
+    }
+    if(pt_refit_run(c->stream, c->refit, (const InstanceRec*)c->dInstances.p, (const float4*)c->dVertices.p, (const uint32_t*)c->dIndices.p, (TriRec*)c->dTris.p, (AlphaRec*)c->dAlphaRecs.p,
+                    (WideNode*)c->dWide.p, rootBox.data(), &info.costAfter, msg, sizeof(msg)) != 0)
+      return c->fail(PT_ERR_HIP, "pt_refit_accel: %s", msg);
+    info.costBefore = c->costBuilt[0] + c->costBuilt[1];
+    for(size_t r = 0; r < numRanges; ++r)
+      info.nodesWritten += ranges[2 * r + 1];
+    for(const RfSlots& s : slots)
+      info.slotsWritten += s.count;
+    if(!two)
+    {  // world bounds = the union of the root's slots (what bounds_from_root takes from the binary root), then the forms made from the nodes and records
+      for(int k = 0; k < 3; ++k)
+      {
+        const float mn = rootBox[k], mx = rootBox[3 + k];
+        c->scene.boundsMin[k]    = std::isfinite(mn) ? mn : 0.f;
+        c->scene.boundsInvExt[k] = (std::isfinite(mx - mn) && mx > mn) ? 1.0f / (mx - mn) : 0.f;
+      }
+      build_cnodes(c, c->numWideNodes);
+      build_shade_tris(c, c->numTris);
+      dev_free(c->dBvh);  // the binary nodes describe the old vertices
+    }
+    else if(c->mergedTris)
+      std::memcpy(c->mergedBox, rootBox.data(), sizeof(c->mergedBox));
+  }
+  if(two)
+  {  // the per-mesh bounds of the ray transform's padding, then the instance boxes and the hierarchy over them as after pt_update_instances
+     // (build_tlas makes the compact nodes of the bottom-level ranges again as well)
+    refresh_prim_bounds(c);
+    if((rc = build_tlas(c)) != PT_OK)
+      return rc;
+  }
+  HIP_TRY(c, sync_all(c));
+  c->haveAccel   = true;
+  c->warmPending = true;
+  refresh_scene_ptrs(c);
+  info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if(out)
+    *out = info;
+  return PT_OK;
+#endif
 }
 
 }  // extern "C"

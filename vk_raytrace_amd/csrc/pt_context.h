@@ -48,6 +48,24 @@ struct pt_context {
   bool     mergedOnly = false;
   std::vector<uint32_t> hInstNodeBase;  // per instance: root node of its BLAS (two-level mode, after the BLAS build)
   std::vector<float>    hPrimBound;     // per prim-mesh: max |coordinate| of its vertices (object space); bounds the rounding of the ray transform
+  // deforming meshes (pt_update_vertices / pt_refit_accel)
+  uint32_t numVertices = 0;
+  std::vector<uint32_t> hPrimMeshVerts;  // per prim-mesh: (vertexOffset, vertexCount), from pt_set_scene
+  std::vector<float>    hPositions;      // the positions of the vertex buffer, three floats per vertex: hPrimBound of a touched mesh is made again from them
+  std::vector<char>     primTouched;     // per prim-mesh: a vertex of it changed since hPrimBound was computed
+  std::vector<PtBlasDesc> hBlas;         // two-level mode: the object-space BLASes as built (slot and node bases, mesh)
+  bool     accelStale = false;           // a structure exists and pt_update_vertices changed vertices since: haveAccel is false until a refit or a build
+  DevBuf   dRefit;                       // the parent table of the current build (pt_refit.hip), made by the first refit after it
+#if PT_BVH_WIDTH == 4
+  PtRefitTable refit;
+#endif
+  bool     haveRefitTable = false;
+  // tree cost of the structure as built (pt_RefitInfo::costBefore = their sum): [0] the flat or merged hierarchy, [1] the BLASes.  Measured when the parent
+  // table is made; the BLASes' part is kept when only the merged structure is built again (pt_update_instances), because by then a refit may have changed them
+  double   costBuilt[2] = {0, 0};
+  bool     haveCostBlas = false;
+  // why a call that walks the structure is refused
+  const char* no_accel() const { return accelStale ? "with a refit pending (pt_update_vertices changed the vertices: call pt_refit_accel or pt_build_accel first)" : "before pt_set_scene / pt_build_accel"; }
   double   msBuildTlas = 0;
   bool     renderedSinceCheck = false;  // frames were launched since the traversal-stack overflow counter was last looked at
   unsigned overflowSeen = 0;           // traversal-stack overflows counted so far (check_traversal); cleared with the counters

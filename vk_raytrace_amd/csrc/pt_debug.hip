@@ -402,7 +402,7 @@ extern "C" __attribute__((visibility("default"))) long long pt_debug_accel_read(
     case PT_DUMP_CNODES: buf = &c->dCNodes; have = sizeof(CompactNode) * cnodes; break;
     case PT_DUMP_TRIS: buf = &c->dTris; have = sizeof(TriRec) * slots; break;
     case PT_DUMP_ALPHA_RECS: buf = &c->dAlphaRecs; have = sizeof(AlphaRec) * slots; break;
-    case PT_DUMP_BVH2: buf = &c->dBvh; have = two ? 0 : sizeof(BvhNode) * size_t(c->numBvhNodes); break;
+    case PT_DUMP_BVH2: buf = &c->dBvh; have = two || !c->dBvh.p ? 0 : sizeof(BvhNode) * size_t(c->numBvhNodes); break;  // (released by a refit: stale)
     case PT_DUMP_TLAS: buf = &c->dTlas; have = two ? sizeof(WideNode) * size_t(c->numTlasNodes) : 0; break;
     case PT_DUMP_CTLAS: buf = &c->dCTlas; have = two && c->haveCNodes && !c->mergedOnly ? sizeof(CompactNode) * size_t(c->numTlasNodes) : 0; break;
     case PT_DUMP_TLAS_LEAVES: buf = &c->dTlasLeaves; have = two ? sizeof(TlasLeaf) * (size_t(c->numActive) + (c->mergedTris ? 1 : 0)) : 0; break;

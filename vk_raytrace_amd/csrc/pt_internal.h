@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "pt_device.h"
+#include "pt_refit.h"
 #define PT_REFILL_BELOW_DEFAULT 48
 #ifndef PT_MIN_GENERATIONS
 #define PT_MIN_GENERATIONS 1  // persistent kernels: rays per lane below which a launch uses fewer waves (1: only waves beyond the queue
@@ -182,6 +183,31 @@ int pt_compact_nodes(hipStream_t stream, uint32_t n, const WideNode* in, Compact
 int pt_compact_node_ranges(hipStream_t stream, const uint32_t* hBaseCount, uint32_t numRanges, const WideNode* in, CompactNode* out);
 // DeviceScene::shadeTris of a flat-format structure: one 128-byte shading line per leaf slot
 void pt_launch_shade_tris(hipStream_t stream, uint32_t n, const TriRec* tris, const InstanceRec* inst, const float4* vertices, const uint32_t* indices, float4* out);
+
+// pt_refit.hip -- the refit of the kept 4-wide hierarchies after pt_update_vertices (bodies: pt_refit.h)
+#if PT_BVH_WIDTH == 4
+// The parent table of one build and the words a refit polls: views into ONE device allocation of pt_refit_table_bytes bytes that the caller owns.
+struct PtRefitTable {
+  RfParent*     parentOfNode = nullptr;  // per node: where its box lives (a range's root: {RF_NONE, range index})
+  RfParent*     parentOfSlot = nullptr;  // per leaf slot
+  unsigned int* arrive       = nullptr;  // per node: arrival counter, cleared by every refit
+  uint2*        ranges       = nullptr;  // the used node ranges (base, count)
+  RfSlots*      slots        = nullptr;  // the slot ranges, ascending
+  float*        rootBox      = nullptr;  // six floats per node range: the union of its root's slots after a refit
+  double*       costBins     = nullptr;  // RF_COST_BINS partial sums of the tree cost
+  uint32_t      numRanges = 0, numSlotRanges = 0, numNodes = 0, numSlots = 0, maxCount = 0;
+};
+size_t pt_refit_table_bytes(uint32_t numNodes, uint32_t numSlots, uint32_t numRanges, uint32_t numSlotRanges);
+// Once per build: carves the table out of dMem, writes the parent table over the used node ranges and measures the tree cost of the structure as it
+// stands in two classes: costBuilt2[0] over the first numFirstClass ranges (the flat or the merged hierarchy), costBuilt2[1] over the rest (the
+// BLASes).  Synchronises.  -1 with the reason in err.
+int pt_refit_prepare(hipStream_t stream, void* dMem, const uint32_t* hBaseCount, uint32_t numRanges, const RfSlots* hSlots, uint32_t numSlotRanges, uint32_t numNodes, uint32_t numSlots,
+                     const WideNode* dWide, PtRefitTable& T, uint32_t numFirstClass, double* costBuilt2, char* err, size_t errLen);
+// One refit: leaf records, texcoords, leaf boxes, inner boxes and order tables of every range made again from the vertices.  hRootBox: six floats per
+// node range.  Synchronises.  -1 with the reason in err.
+int pt_refit_run(hipStream_t stream, const PtRefitTable& T, const InstanceRec* dInst, const float4* dVertices, const uint32_t* dIndices, TriRec* dTris, AlphaRec* dAlpha, WideNode* dWide,
+                 float* hRootBox, double* costAfter, char* err, size_t errLen);
+#endif
 
 // pt_render.hip -- one frame of the wavefront pipeline, enqueued on `stream`
 // Per-bounce counter block (CNT_STRIDE words per bounce; zero when a sample pass starts: pt_resize clears it, k_accumulate leaves it cleared):

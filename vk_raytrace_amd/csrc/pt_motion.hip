@@ -62,7 +62,7 @@ static int prepare_instances(pt_context* c, const char* who, uint32_t planes, fl
   if(!(fabsf(missDepth) <= 3.402823466e38f))  // NaN, +-Inf
     return c->fail(PT_ERR_INVALID, "%s: miss_depth is not finite", who);
   if(!c->haveScene || !c->haveAccel)
-    return c->fail(PT_ERR_STATE, "%s before pt_set_scene / pt_build_accel", who);
+    return c->fail(PT_ERR_STATE, "%s %s", who, c->no_accel());
   if(!c->haveCamera)
     return c->fail(PT_ERR_STATE, "%s before pt_set_camera", who);
   STAGE_TRY(stage_need_image(c, who));

@@ -99,7 +99,7 @@ int path_query_checks(pt_context* c, const char* who, const pt_RtxState* st, uin
   if(st->debugging_mode == PT_DEBUG_HEATMAP)
     return c->fail(PT_ERR_INVALID, "%s: RtxState.debugging_mode = PT_DEBUG_HEATMAP (the heat map is a frame's: it colours the time its kernels spent on a pixel)", who);
   if(!c->haveScene || !c->haveAccel)
-    return c->fail(PT_ERR_STATE, "%s before pt_set_scene / pt_build_accel", who);
+    return c->fail(PT_ERR_STATE, "%s %s", who, c->no_accel());
   if(!c->haveEnv && c->scene.sunsky.in_use != 1)
     return c->fail(PT_ERR_STATE, "%s without an environment (pt_set_env) or sun & sky", who);
   if(!c->haveCamera)

@@ -52,7 +52,7 @@ extern "C" int pt_trace_rays(pt_context* c, int kind, uint32_t flags, uint64_t n
   if(n > (uint64_t(1) << 40))
     return c->fail(PT_ERR_INVALID, "pt_trace_rays: n = %llu", (unsigned long long)n);
   if(!c->haveScene || !c->haveAccel)
-    return c->fail(PT_ERR_STATE, "pt_trace_rays before pt_set_scene / pt_build_accel");
+    return c->fail(PT_ERR_STATE, "pt_trace_rays %s", c->no_accel());
   if(n == 0)
     return PT_OK;
   HIP_TRY(c, hipSetDevice(c->device));

@@ -170,6 +170,11 @@ class Peaks(C.Structure):
                 ("clockMHz", C.c_int32)]
 
 
+class RefitInfo(C.Structure):
+    """pt_RefitInfo (pt_refit_accel): host milliseconds, the tree cost as built and after this refit, what was written"""
+    _fields_ = [("ms", C.c_double), ("costBefore", C.c_double), ("costAfter", C.c_double), ("nodesWritten", C.c_uint32), ("slotsWritten", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("closestRays", C.c_uint64), ("shadowRays", C.c_uint64),
                 ("shadedHits", C.c_uint64), ("misses", C.c_uint64), ("alphaTests", C.c_uint64),

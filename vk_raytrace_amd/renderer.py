@@ -151,6 +151,19 @@ class HipRenderer(Renderer):
         arr = np.ascontiguousarray(nodes.node_array() if hasattr(nodes, "node_array") else nodes, hd.node_dtype)
         self._check(self._lib.pt_update_instances(self._ctx, arr.ctypes.data, len(arr)))
 
+    def update_vertices(self, first, vertices):
+        """Replaces vertices[first : first + len(vertices)] of the scene's vertex buffer (whole records of capi.pack_vertices' dtype).  A built
+        structure is stale afterwards: refit_accel() or build_accel() before anything walks it."""
+        arr = np.ascontiguousarray(vertices)
+        assert arr.dtype.itemsize == C.sizeof(hd.VertexAttributes), "vertices: records of 32 bytes (capi.pack_vertices)"
+        self._check(self._lib.pt_update_vertices(self._ctx, int(first), len(arr), arr.ctypes.data if len(arr) else None))
+
+    def refit_accel(self):
+        """Brings the stale structure up to date without changing its topology -> hd.RefitInfo (costAfter / costBefore says when to rebuild)."""
+        info = hd.RefitInfo()
+        self._check(self._lib.pt_refit_accel(self._ctx, C.byref(info)))
+        return info
+
     def set_variant(self, variant):
         """capi.PT_VARIANT_RAYQUERY (the reference's RayQuery renderer, default) or capi.PT_VARIANT_RTX (its RtxPipeline)."""
         self._check(self._lib.pt_set_variant(self._ctx, int(variant)))
